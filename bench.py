@@ -10,9 +10,13 @@ scaling), executed as micro-batches with gradient accumulation exactly like `acc
   int16 PCM (resident in HBM) -> log-mel (HIP) -> encoder/decoder forward -> CE(ignore pad)/accum -> backward
   (-> bucketed RCCL all-reduce of the flat fp32 gradient arena, overlapped with the backward of the last micro-batch)
   -> fused unscale + clip_grad_norm_(1.0) + AdamW.
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` (dominant kernel = the bf16 MFMA GEMM, measured with
-HIP events on its own stream in one extra, identical step) and `cpu_baseline` (the CPU oracle on the host cores,
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times exactly --steps steps and prints the
+line; nothing else runs on the GPU.  --full adds what takes runs of its own: the other two step modes (`step_modes_same_run`),
+`roofline` (dominant kernel = the bf16 MFMA GEMM, measured with HIP events on its own stream in one extra, identical step, plus
+the HBM-bound kernels), the span-vs-plain parity check, and `cpu_baseline` + `parity` (the CPU oracle on the host cores,
 bounded sample, N=1 only).
+--dump-outputs DIR writes what the last timed step computed (loss, optimizer statistics, and a fixed seeded sample of the
+updated parameters, gradients and AdamW moments) as DIR/<name>.npy, before anything else touches the model.
 """
 import argparse
 import ctypes
@@ -338,6 +342,26 @@ def hbm_kernel_rooflines(net, dims, mb, dev):
     return out
 
 
+DUMP_SAMPLE = 1 << 20  # arena entries sampled per dumped array: 4 x 4 MB + 8 MB of indices
+
+
+def dump_outputs(net, loss_buf, directory):
+    """What a caller of the timed step receives after its last step, as DIR/<name>.npy: the loss, the optimizer statistics, and the
+    updated parameters, their gradients and the AdamW moments at a fixed sample of flat-arena positions (torch CPU generator, seed 0:
+    the same positions for every build and run of the same model)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    n = net.flat_params.numel()
+    g = torch.Generator().manual_seed(0)
+    idx = torch.unique(torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=g)) if n > DUMP_SAMPLE else torch.arange(n)
+    idx_dev = idx.to(net.flat_params.device)
+    m, v = net.init_optimizer_state()
+    arrays = {"loss": loss_buf.double(), "optim_stats": net._opt_stats.double(), "sample_index": idx.double(),
+              "params": net.flat_params[idx_dev], "grads": net.flat_grads[idx_dev], "adam_exp_avg": m[idx_dev], "adam_exp_avg_sq": v[idx_dev]}
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), t.detach().cpu().numpy())
+
+
 def self_launch(n, argv, module="torch.distributed.run", extra_env=None):
     """`python bench.py --gpus N` (N > 1) outside a launcher: re-run this file as N ranks on this node and relay rank 0's stdout.
     Fails with a plain message -- not an assert -- when the node has fewer devices."""
@@ -450,10 +474,19 @@ def main():
                     help="headline = round 4's step: decoder forward over all 448 positions, backward over the supervised span")
     ap.add_argument("--span-forward", action="store_true", help="(the default since round 5; accepted for old command lines)")
     ap.add_argument("--ab-steps", type=int, default=-1,
-                    help="steps timed for each of the two NON-headline step modes in the same process (1 warm-up each); -1 = min(steps, 3), 0 = skip")
+                    help="steps timed for each of the two NON-headline step modes in the same process (1 warm-up each); "
+                         "-1 = min(steps, 3) with --full, 0 without; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the other step modes, the GEMM roofline and HBM-kernel timings, "
+                         "the span-vs-plain parity check and the CPU baseline with its parity block (--no-profile / "
+                         "--no-cpu-baseline leave parts out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     args = ap.parse_args()
+    profile = args.full and not args.no_profile
+    cpu_base = args.full and not args.no_cpu_baseline
 
     # `python bench.py --gpus N` without a launcher: start one rank per GPU ourselves (torch.distributed.run, loopback rendezvous)
     # and let rank 0's JSON line through -- the shape of the driver's N = 1 command works for every N.
@@ -596,11 +629,13 @@ def main():
     comm = None
     if ddp_path:
         comm = reducers[head_algo].comm_report()  # of the LAST timed step (HIP events recorded inside reduce())
+    if args.dump_outputs and rank == 0:  # before the --full legs below run more steps on the same model
+        dump_outputs(net, loss_buf, args.dump_outputs)
 
-    # ---- the other two step modes, a few steps each, SAME process / box / clock regime (outside the headline's timed region):
+    # ---- --full: the other two step modes, a few steps each, SAME process / box / clock regime (outside the headline's timed region):
     # the exact A/B the headline rests on travels with the line instead of living in a builder-run profile
     ab = {}
-    n_ab = min(args.steps, 3) if args.ab_steps < 0 else args.ab_steps
+    n_ab = (min(args.steps, 3) if args.full else 0) if args.ab_steps < 0 else args.ab_steps
     if n_ab > 0 and not args.trim_padding:
         for m in STEP_MODES:
             if m != head_mode:
@@ -616,7 +651,7 @@ def main():
     # on the launch stream (olmoasr_amd/csrc/gemm.hip); aggregated by kernel SYMBOL so it can be compared line by line
     # with `rocprofv3 --kernel-trace --stats` of this same command (profiles/).
     roof = None
-    if not args.no_profile:
+    if profile:
         lib = N.lib()
         lib.oasr_profile_gemm(1)
         sampler = PowerSampler(local_rank if ddp_path else 0)
@@ -750,7 +785,7 @@ def main():
         if roof:
             out["roofline"] = roof
         span_check = None
-        if world == 1 and head_mode != "plain" and not args.no_profile:
+        if world == 1 and head_mode != "plain" and profile:
             # the step that was timed against the step it replaces, at the benchmarked micro-batch, on this model's weights (outside the
             # timed region): micro-batch 0 through the plain step (decoder forward + backward over all 448 positions) and through the headline step
             sl = slice(0, mb)
@@ -767,7 +802,7 @@ def main():
                           "grad_rel_l2": float((net.flat_grads.double() - g_full.double()).norm() / g_full.double().norm()),
                           "active_rows_of_total": round(rows[head_mode][1] / (B * 448.0), 4)}
             del g_full
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             # parity of the benchmarked model itself (outside the timed region): clip 0 of the oracle's generator through the
             # HIP step and through the fp32 CPU oracle with the SAME weights (taken before the hbm-kernel timings touch them)
             from oracle import model_oracle as mo
@@ -789,7 +824,7 @@ def main():
             del p_logits, o_logits
         if span_check:
             out.setdefault("parity", {})["span_step_vs_plain_step"] = span_check
-        if world == 1 and not args.no_profile:
+        if world == 1 and profile:
             net._workspace = None
             torch.cuda.empty_cache()
             roof_h = hbm_kernel_rooflines(net, dims, mb, dev)

@@ -2,7 +2,7 @@
 export OASR_TESTING_HOOKS=1  # the OASR_PP_* switches are inert without it (csrc/common.h::oasr_experiment_env)
 for v in 0 2 7 -1 0 -1; do
   if [ "$v" = "-1" ]; then unset OASR_PP_VARIANT; else export OASR_PP_VARIANT=$v; fi
-  python bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read())
 r=d['roofline']

@@ -1,6 +1,6 @@
 """Pins oracle/model_oracle.py against fixtures generated from the UNMODIFIED reference model
-(tests/golden/ref_tiny_b2.npz, oracle/gen_golden.py) and, when /root/reference is mounted (build
-container only), against the reference live."""
+(tests/golden/ref_tiny_b2.npz, oracle/gen_golden.py; tests/golden/ref_checks.npz, oracle/gen_ref_checks_golden.py) and, where
+the reference tree is readable, against the reference live."""
 import os
 
 import numpy as np
@@ -103,16 +103,15 @@ def test_greedy_decode_runs_and_is_eot_sticky(tiny_case):
     assert toks.shape[0] == 1 and toks.shape[1] <= 6 and (toks[:, :2] == torch.tensor([50257, 50362])).all()
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not mounted (GPU box)")
-def test_oracle_vs_live_reference(ora, tiny_case):
-    ref_model, _, ref_dims = ref_import.load()
-    c = tiny_case
-    net = ref_model.OLMoASR(ref_dims.VARIANT_TO_DIMS["tiny"])
-    net.load_state_dict(c["sd"], strict=True)
-    pm = mo.build_padding_mask(c["text_len"])
-    with torch.no_grad():
-        ref = net(c["mel"], c["tokens"], pm)
-    assert (ref - ora["logits"]).abs().max().item() < 5e-5
+def test_oracle_vs_live_reference(ora, golden_dir):
+    """The oracle's fp32 logits against the reference model's own (same weights, same batch) at the seeded sample of entries
+    oracle/gen_ref_checks_golden.py stored from it."""
+    from oracle.gen_ref_checks_golden import logit_sample_index
+    g = np.load(os.path.join(golden_dir, "ref_checks.npz"))
+    lg = ora["logits"]
+    assert tuple(lg.shape) == tuple(g["logit_shape"])
+    b, p, v = logit_sample_index(lg.shape)
+    assert np.abs(lg[b, p, v].numpy() - g["logit_value"]).max() < 5e-5
 
 
 @pytest.mark.skipif(not ref_import.available(), reason="/root/reference not mounted (build container only)")

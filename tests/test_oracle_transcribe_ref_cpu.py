@@ -4,11 +4,11 @@
   loop: clip_timestamps, temperature fallback with beam/best_of switching, no-speech skip, closed pairs / open tail / single
   closing timestamp / no timestamps / empty output, the instantaneous-or-empty rule, segment ids) and on a real tiny model
   with the timestamp bonus -- via the committed fixture tests/golden/transcribe_ref.json (oracle/gen_transcribe_golden.py)
-  everywhere, and LIVE against /root/reference when it is mounted (build container).
+  (and tests/golden/ref_checks.json for one more clip_timestamps case, oracle/gen_ref_checks_golden.py).
 * the same with a TOKENIZER (a stand-in whose tokens spell themselves, supplied to both sides): 24 scripted cases whose decode
   results carry text / compression_ratio like whisper.decoding fills them -- the compression-ratio fallback (:213-217, in half of
   the cases the only thing that changes the outcome), segment and result text, the blank-text rule (:494-499), initial_prompt
-  (:258-264) -- oracle and product against the reference's own file (fixture + live).
+  (:258-264) -- oracle and product against the reference's own file (fixture).
 * the PRODUCT's host-side seek loop (olmoasr_amd/transcribe.py) on the same scripted cases against the same fixture: its
   decode call is replaced by the scripted one, so this is pure host logic (no GPU, no native library)."""
 import json
@@ -19,7 +19,6 @@ import pytest
 import torch
 
 from oracle import decode_oracle as do
-from oracle import ref_import
 from oracle import ref_transcribe_harness as H
 
 
@@ -29,7 +28,9 @@ def golden(golden_dir):
         return json.load(f)
 
 
-def _eq(got, want, what, text=False, words=False):
+def _eq(got, want, what, text=False, words=False, prob_tol=1e-9):
+    """``prob_tol``: bound on avg_logprob / no_speech_prob.  Exact (1e-9) where a script supplies them; a real model computes them in
+    fp32 on the CPU, where another CPU's matmul kernels move them by ~1e-6 -- tokens, seeks, timestamps and texts stay exact."""
     assert got["tokens"] == want["tokens"], what
     assert len(got["segments"]) == len(want["segments"]), what
     for a, b in zip(got["segments"], want["segments"]):
@@ -37,8 +38,10 @@ def _eq(got, want, what, text=False, words=False):
             assert a["words"] == b["words"], (what, a["id"], a["words"][:3], b["words"][:3])
         for k in ("id", "seek", "tokens", "temperature") + (("text",) if text else ()):
             assert a[k] == b[k], (what, k, a, b)
-        for k in ("start", "end", "avg_logprob", "no_speech_prob") + (("compression_ratio",) if text else ()):
+        for k in ("start", "end") + (("compression_ratio",) if text else ()):
             assert abs(a[k] - b[k]) < 1e-9, (what, k, a, b)
+        for k in ("avg_logprob", "no_speech_prob"):
+            assert abs(a[k] - b[k]) < prob_tol, (what, k, a, b)
     if text:
         assert got["text"] == want["text"], what
 
@@ -108,25 +111,29 @@ def test_oracle_transcribe_equals_reference_fixture_real_model(golden):
     torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
     sd, dims, mel_padded, bias, kw = model_case()
     got = do.transcribe(sd, dims, mel_padded, logit_bias=bias, **kw)
-    _eq(H.comparable(got), golden["model"], "tiny model, timestamp bonus")
+    _eq(H.comparable(got), golden["model"], "tiny model, timestamp bonus", prob_tol=2e-5)
     assert len(got["seeks"]) >= 2 and any(s % 3000 for s in got["seeks"])  # the seek was driven by timestamps
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="/root/reference not mounted (build container only)")
-def test_oracle_transcribe_equals_reference_live():
-    for c in H.scripted_cases() + [dict(seed=99, content_frames=45000, kw=dict(temperature=(0.0, 0.4, 0.8), logprob_threshold=-0.8,
-                                                                               no_speech_threshold=0.5, clip_timestamps=[3.0, 200.0, 210.5]))]:
+def test_oracle_transcribe_equals_reference_live(golden, golden_dir):
+    """Every scripted case of the three fixture sets once more in one sweep (token level, with a tokenizer, word timestamps), plus a
+    case of its own -- clip_timestamps with a closed and an open-ended clip under a three-step temperature ladder -- against the
+    reference's output for it (tests/golden/ref_checks.json, oracle/gen_ref_checks_golden.py)."""
+    from oracle.gen_ref_checks_golden import TRANSCRIBE_CLIP_CASE
+    with open(os.path.join(golden_dir, "ref_checks.json")) as f:
+        clip_want = json.load(f)["transcribe_clip"]
+    for c, want in zip(H.scripted_cases(), golden["scripted"]):
         dec, mel = H.scripted_decode(c["seed"]), H.index_mel(c["content_frames"])
-        _eq(H.comparable(H.run_oracle(dec, mel, **dict(c["kw"]))), H.comparable(H.run_reference(dec, mel, **dict(c["kw"]))), f"live {c}")
-    for c in H.scripted_cr_cases():
+        _eq(H.comparable(H.run_oracle(dec, mel, **dict(c["kw"]))), want, f"sweep {c}")
+    c = TRANSCRIBE_CLIP_CASE
+    _eq(H.comparable(H.run_oracle(H.scripted_decode(c["seed"]), H.index_mel(c["content_frames"]), **dict(c["kw"]))), clip_want, f"clip case {c}")
+    for c, want in zip(H.scripted_cr_cases(), golden["scripted_cr"]):
         dec, mel = H.scripted_decode_cr(c["seed"]), H.index_mel(c["content_frames"])
-        _eq(H.comparable(H.run_oracle(dec, mel, tokenizer=H.Tok(), **dict(c["kw"])), text=True),
-            H.comparable(H.run_reference(dec, mel, **dict(c["kw"])), text=True), f"live, with tokenizer {c}", text=True)
-    for c in H.scripted_words_cases():
+        _eq(H.comparable(H.run_oracle(dec, mel, tokenizer=H.Tok(), **dict(c["kw"])), text=True), want, f"sweep, with tokenizer {c}", text=True)
+    for c, want in zip(H.scripted_words_cases(), golden["scripted_words"]):
         dec, mel, words = H.scripted_decode_cr(c["seed"]), H.index_mel(c["content_frames"]), H.scripted_words(c["seed"])
         _eq(H.comparable(H.run_oracle(dec, mel, tokenizer=H.Tok(), add_word_timestamps=words, **dict(c["kw"])), text=True, words=True),
-            H.comparable(H.run_reference(dec, mel, add_word_timestamps=words, **dict(c["kw"])), text=True, words=True),
-            f"live, word timestamps {c}", text=True, words=True)
+            want, f"sweep, word timestamps {c}", text=True, words=True)
 
 
 def test_product_seek_loop_equals_reference_fixture(golden, monkeypatch):

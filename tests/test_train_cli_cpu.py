@@ -94,20 +94,17 @@ def test_checkpoint_pieces_load_on_the_reference_side(tt, tmp_path):
     assert sched.last_epoch == 8 and abs(opt.param_groups[0]["lr"] - 1.5e-3 * tt.lr_lambda(8, 1000)) < 1e-12
     scaler = torch.amp.GradScaler("cpu", enabled=True)
     scaler.load_state_dict(raw["scaler_state_dict"])
-    # the unmodified reference model class builds from our dims object and loads our state_dict
-    from oracle import ref_import
-    if not ref_import.available():  # /root/reference is absent on the GPU box
-        pytest.skip("reference tree not mounted")
-    ref_model, _, _ = ref_import.load()
-    model = ref_model.OLMoASR(dims=raw["dims"])
-    res = model.load_state_dict(raw["model_state_dict"], strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
+    # the unmodified reference model class at these dims loads our state_dict strictly: the same keys, the same shapes as its own
+    # state_dict (tests/golden/ref_checks.json, oracle/gen_ref_checks_golden.py, built from raw["dims"]'s values)
+    import json
+    from oracle.gen_ref_checks_golden import CKPT_DIMS
+    assert raw["dims"].__dict__ == CKPT_DIMS.__dict__
+    ref_shapes = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_checks.json")))["ckpt_state_dict"]
+    assert {k: list(v.shape) for k, v in raw["model_state_dict"].items()} == ref_shapes
     # AdamW state indices follow named_parameters() order: the committed fixture (oracle/gen_param_order.py) pins the
     # reference's order; tests/test_gpu_model.py checks the native model against the same file
-    import json
     want = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_param_order.json")))
-    ref_tiny = ref_model.OLMoASR(dims=types.SimpleNamespace(**mo.VARIANTS["tiny"].__dict__))
-    assert [n for n, _ in ref_tiny.named_parameters()] == want["tiny"]
+    assert [n for n in ref_shapes if n in set(want["tiny"])] == [n for n in want["tiny"] if n in ref_shapes]
 
 
 def test_reference_pickled_dims_load_here(tmp_path):
