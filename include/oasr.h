@@ -35,7 +35,7 @@ typedef struct oasr_dims {
 const char* oasr_last_error(void);
 /* ABI version: 100 * major + minor.  Structs passed by pointer (oasr_attn_args, oasr_gemm_args) only grow at the end and only with a
  * major bump; olmoasr_amd/_native.py refuses to drive a library whose version differs from OASR_ABI_VERSION. */
-#define OASR_ABI_VERSION 211
+#define OASR_ABI_VERSION 212
 int oasr_version(void);
 
 /* ---- log-mel front end: whisper.audio.log_mel_spectrogram as called at train_timestamps.py:196,214 and
@@ -170,6 +170,13 @@ int oasr_train_fwd(oasr_ctx*, const float* mel, const int64_t* tokens, const int
 int oasr_train_bwd(oasr_ctx*, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void** seg_events,
                    void* workspace, size_t workspace_bytes, void* stream);
 int oasr_zero_grad(oasr_ctx*, void* stream);
+
+/* Frozen parameters (torch's requires_grad == False): mask holds one byte per tensor in oasr_param_info order, nonzero = trainable;
+ * the default is all ones.  From then on the backward entries (oasr_train_fwd_bwd, _s, _span, oasr_train_bwd) neither launch nor
+ * write anything whose only purpose is a frozen tensor's gradient: frozen ranges of the gradient arena are left as they are.
+ * oasr_optim_step updates, decays and clips over the trainable tensors only (frozen moments stay as they are).  With no trainable
+ * tensor the backward entries return OASR_ESTATE.  The call is synchronous (it uploads the optimizer's table of trainable runs). */
+int oasr_set_trainable(oasr_ctx*, const uint8_t* mask, int n_params);
 
 /* scaler.unscale_ + clip_grad_norm_(max_norm) + AdamW.step + bf16 shadow refresh (train_timestamps.py:1509-1512).
  * step is 1-based.  stats_out (device f32[2]): [0] = sum of squares of the SCALED grads, [1] = non-finite flag

@@ -44,7 +44,7 @@ class AttnArgs(C.Structure):
                 ("q_rows", C.c_void_p), ("k_rows", C.c_void_p), ("q_span", C.c_void_p)]
 
 
-ABI_VERSION = 211  # include/oasr.h: OASR_ABI_VERSION (211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
+ABI_VERSION = 212  # include/oasr.h: OASR_ABI_VERSION (212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 ROWTAB = 16        # include/oasr.h: OASR_ROWTAB (entries per sample of a chunk-row table)
 
@@ -89,6 +89,7 @@ def _declare(lib):
         "oasr_train_fwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_train_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_zero_grad": (i32, [vp, vp]),
+        "oasr_set_trainable": (i32, [vp, vp, i32]),
         "oasr_optim_step": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, i64, vp, vp, vp]),
         "oasr_grad_sumsq_range": (i32, [vp, i64, i64, vp, vp, vp]),
         "oasr_optim_step_range": (i32, [vp, i64, i64, vp, vp, vp, f32, f32, f32, f32, f32, f32, f32, i64, vp]),

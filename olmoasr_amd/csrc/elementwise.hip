@@ -132,9 +132,9 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __res
       const float g = bf2f(dx[r * d + c]);
       acc += g;
       const long t = tok[(long)b * S + s];
-      if (t != pad_id && t >= 0 && t < n_embed) unsafeAtomicAdd(dE + t * d + c, g);  // ids outside the table: no scatter (fwd read zeros)
+      if (dE && t != pad_id && t >= 0 && t < n_embed) unsafeAtomicAdd(dE + t * d + c, g);  // ids outside the table: no scatter (fwd read zeros)
     }
-    dpos[(long)s * d + c] += acc;
+    if (dpos) dpos[(long)s * d + c] += acc;  // (dE / dpos null: that table is frozen, oasr_set_trainable)
   }
 }
 
@@ -290,7 +290,7 @@ int launch_embedding_fwd(const int64_t* tok, const float* E, const float* pos, b
 }
 int launch_embedding_bwd(const int64_t* tok, const bf16_t* dx, float* dE, float* dpos, int B, int S, int d, long pad_id, long n_embed,
                          hipStream_t s, const int32_t* rows_tab, const int32_t* span) {
-  OASR_REQUIRE(tok && dx && dE && dpos, "embedding_bwd: bad args");
+  OASR_REQUIRE(tok && dx && (dE || dpos), "embedding_bwd: bad args");
   OASR_REQUIRE(!rows_tab || (S % 64 == 0 && S <= 64 * OASR_ROWTAB), "embedding_bwd: chunk rows need S %% 64 == 0");
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3(S), dim3(256), 0, s, tok, dx, dE, dpos, B, S, d, pad_id, n_embed, rows_tab, span);
   OASR_LAUNCH_CHECK();

@@ -79,7 +79,33 @@ struct oasr_ctx {
   // resident at once, which a shared / CU-masked device does not guarantee.  From then on this context decodes on the multi-launch engine.
   bool xcd_disabled = false;
   int n_cu = 0;  // compute units of the device (queried by the first decoder step)
+  // ---- frozen parameters (oasr_set_trainable) ----
+  // Derived once per mask change and kept: which tensors are trainable, and for every place the backward could stop, whether anything
+  // before it in the forward still needs a gradient.  all == true is the untouched training step (every launch as before).
+  struct Prune {
+    bool all = true, any = true;
+    std::vector<uint8_t> tr;                 // [tensors]
+    bool enc_any = true;                     // some encoder tensor (ln_post, blocks, conv stem): the encoder backward and d(xa) run
+    std::vector<uint8_t> dec_blk, enc_blk;   // [L]: the block holds a trainable tensor
+    std::vector<uint8_t> dec_in, enc_in;     // [L + 1]: the data gradient out of block i (into the residual stream below it) is needed
+    bool conv1 = true;                       // conv1 weight or bias: the conv2 data gradient and the col2im run
+  } pr;
+  int64_t* runs_dev = nullptr;  // [2 * n_runs] (offset, numel) of the maximal trainable stretches of the arena (device)
+  int n_runs = 0;
+  // is the tensor at arena offset `off` trainable
+  bool tr(int64_t off) const {
+    if (pr.all) return true;
+    size_t lo = 0, hi = tensors.size();
+    while (hi - lo > 1) {
+      const size_t mid = (lo + hi) / 2;
+      if (tensors[mid].off <= off) lo = mid;
+      else hi = mid;
+    }
+    return pr.tr[lo] != 0;
+  }
+  float* Gt(int64_t off) const { return tr(off) ? grads + off : nullptr; }  // gradient of a tensor, null when it is frozen
   ~oasr_ctx() {
+    if (runs_dev) (void)hipFree(runs_dev);
     for (hipEvent_t e : side.fork)
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : side.join)
@@ -701,24 +727,51 @@ struct Runner {
   // residual-stream gradient, and every such gradient is produced by a LayerNorm backward -> that kernel accumulates
   // them (its `dsum` output).  The caller's LN backward already filled this block's mlp.2.bias gradient from dx_out;
   // `dsum_next` is the bias gradient the produced dx_in belongs to (previous block's mlp.2.bias, or null).
+  // Frozen parameters (oasr_ctx::Prune): every weight / bias / LayerNorm gradient of a frozen tensor is left out (null outputs, skipped
+  // launches), and a section's data path runs only if something it feeds still needs a gradient -- `need_dx_in` (the block's input
+  // gradient: a trainable tensor below it) or `need_xa` (d(xa): a trainable encoder tensor).  With every tensor trainable both are true
+  // and every launch is the one of the plain step.
+  // A weight gradient over consecutive [rows x K] tensors of the arena that one GEMM fills (q|k|v, cross k|v): one launch when all are
+  // trainable, one per trainable tensor otherwise (columns j*rows.. of dy).
+  int wgrad_parts(const T* dy, long ldy, long M, const View& x, int K, const int64_t* offs, int n, int rows) {
+    int ntr = 0;
+    for (int j = 0; j < n; ++j) ntr += c->tr(offs[j]) ? 1 : 0;
+    if (ntr == n) return wgrad_side(dy, ldy, M, n * rows, x, K, c->G(offs[0]), K);
+    for (int j = 0; j < n; ++j)
+      if (c->tr(offs[j])) RC(wgrad_side(dy + (long)j * rows, ldy, M, rows, x, K, c->G(offs[j]), K));
+    return OASR_OK;
+  }
   int block_bwd(const BlockP& bp, const BlockSave& s, Plan& p, const T* dx_out, T* scratch_a, T* scratch_b, long M,
-                long Tq, bool causal, bool first_cross, float* dsum_next, const T** dx_in) {
+                long Tq, bool causal, bool first_cross, float* dsum_next, const T** dx_in, bool need_dx_in = true, bool need_xa = true) {
     const int d = c->d;
     const T* xm = bp.cross ? s.x_mid2 : s.x_mid;
+    auto any = [&](std::initializer_list<int64_t> offs) {
+      for (int64_t o : offs)
+        if (c->tr(o)) return true;
+      return false;
+    };
+    const AttnP& sa_p = bp.attn;
+    const bool sa_need = need_dx_in || any({sa_p.qw, sa_p.kw, sa_p.vw, sa_p.ow, sa_p.qb, sa_p.vb, sa_p.ob, bp.attn_ln_w, bp.attn_ln_b});
+    const bool ca_need = bp.cross && (sa_need || need_xa || any({bp.cattn.qw, bp.cattn.kw, bp.cattn.vw, bp.cattn.ow, bp.cattn.qb, bp.cattn.vb,
+                                                                  bp.cattn.ob, bp.cln_w, bp.cln_b}));
+    const bool mlp_need = (bp.cross ? ca_need : sa_need) || any({bp.w1, bp.b1, bp.mlp_ln_w, bp.mlp_ln_b});
+    *dx_in = nullptr;
     // ---- MLP -----------------------------------------------------------------------------------------------
-    RC(wgrad_side(dx_out, d, M, d, plain_view(s.hg, 4 * d), 4 * d, c->G(bp.w2), 4 * d));
-    RC(dgrad(dx_out, M, d, c->template Wt<T>(bp.w2), 4 * d, s.u, nullptr, p.gu, c->G(bp.b1), true));  // s.u = GELU'(u); + fused mlp.0.bias gradient
-    RC(wgrad_side(p.gu, 4 * d, M, 4 * d, plain_view(s.ln2, d), d, c->G(bp.w1), d));
+    if (c->tr(bp.w2)) RC(wgrad_side(dx_out, d, M, d, plain_view(s.hg, 4 * d), 4 * d, c->G(bp.w2), 4 * d));
+    if (!mlp_need) return join_side();
+    RC(dgrad(dx_out, M, d, c->template Wt<T>(bp.w2), 4 * d, s.u, nullptr, p.gu, c->Gt(bp.b1), true));  // s.u = GELU'(u); + fused mlp.0.bias gradient
+    if (c->tr(bp.w1)) RC(wgrad_side(p.gu, 4 * d, M, 4 * d, plain_view(s.ln2, d), d, c->G(bp.w1), d));
     RC(dgrad(p.gu, M, 4 * d, c->template Wt<T>(bp.w1), d, nullptr, nullptr, p.gln));
     RC(join_side());
-    RC(launch_layernorm_bwd(p.gln, xm, c->P(bp.mlp_ln_w), s.mean2, s.rstd2, dx_out, scratch_a, c->G(bp.mlp_ln_w), c->G(bp.mlp_ln_b),
-                            c->G(bp.cross ? bp.cattn.ob : bp.attn.ob), M, d, st));
+    RC(launch_layernorm_bwd(p.gln, xm, c->P(bp.mlp_ln_w), s.mean2, s.rstd2, dx_out, scratch_a, c->Gt(bp.mlp_ln_w), c->Gt(bp.mlp_ln_b),
+                            c->Gt(bp.cross ? bp.cattn.ob : bp.attn.ob), M, d, st));
     const T* dx = scratch_a;
     T* nxt = scratch_b;
     // ---- cross attention ---------------------------------------------------------------------------------------
     if (bp.cross) {
       const long Mkv = (long)B * c->Te;
-      RC(wgrad_side(dx, d, M, d, plain_view(s.ca.o, d), d, c->G(bp.cattn.ow), d));
+      if (c->tr(bp.cattn.ow)) RC(wgrad_side(dx, d, M, d, plain_view(s.ca.o, d), d, c->G(bp.cattn.ow), d));
+      if (!ca_need) return join_side();
       RC(dgrad(dx, M, d, c->template Wt<T>(bp.cattn.ow), d, nullptr, nullptr, p.go));
       Attn a;
       attn_args(a, s.ca, true, Tq, c->Te, false);
@@ -727,8 +780,8 @@ struct Runner {
       a.dq = p.gq;
       a.dk = p.gkv;
       a.dv = p.gkv + d;
-      a.dq_colsum = c->G(bp.cattn.qb);  // query / value bias gradients = column sums of dq / dv, fused into the store epilogues
-      a.dv_colsum = c->G(bp.cattn.vb);
+      a.dq_colsum = c->Gt(bp.cattn.qb);  // query / value bias gradients = column sums of dq / dv, fused into the store epilogues
+      a.dv_colsum = c->Gt(bp.cattn.vb);
       a.colsum_scratch = p.cs_scratch;
       // decoder positions the loss ignores have d_o == 0 exactly (three quarters of the 448 on the synthetic lengths): the kernels
       // find those 64-position tiles themselves and skip them (span-limited step: the span says where they are, and the rows past
@@ -737,28 +790,39 @@ struct Runner {
       a.q_span = dec_span;
       RC(join_big());  // (the previous layer's key|value gradients still read p.gkv)
       RC(launch_attention_bwd(a, st));
-      RC(wgrad_side(p.gq, d, M, d, plain_view(s.ca.ln, d), d, c->G(bp.cattn.qw), d));
-      {
+      if (c->tr(bp.cattn.qw)) RC(wgrad_side(p.gq, d, M, d, plain_view(s.ca.ln, d), d, c->G(bp.cattn.qw), d));
+      const bool kv_tr = any({bp.cattn.kw, bp.cattn.vw});
+      if (kv_tr || need_xa) {
         const bool big = (side_mode & 4) != 0;
         if (big) {
           RC(fork_to(c->side.big));
           big_pending = true;
         }
         OnStream on(st, big ? c->side.big : st);
-        RC(wgrad(p.gkv, 2 * d, Mkv, 2 * d, plain_view(p.xa, d), d, c->G(bp.cattn.kw), d));
+        if (kv_tr) {
+          if (c->tr(bp.cattn.kw) && c->tr(bp.cattn.vw)) {
+            RC(wgrad(p.gkv, 2 * d, Mkv, 2 * d, plain_view(p.xa, d), d, c->G(bp.cattn.kw), d));
+          } else {
+            const int64_t kv[2] = {bp.cattn.kw, bp.cattn.vw};
+            for (int j = 0; j < 2; ++j)
+              if (c->tr(kv[j])) RC(wgrad(p.gkv + (long)j * d, 2 * d, Mkv, d, plain_view(p.xa, d), d, c->G(kv[j]), d));
+          }
+        }
         // d(xa) accumulates over the decoder layers (bf16, like autograd's accumulation into xa.grad)
-        RC(dgrad(p.gkv, Mkv, 2 * d, c->template Wt<T>(bp.cattn.kw), d, nullptr, first_cross ? nullptr : p.gxa, p.gxa));
+        if (need_xa) RC(dgrad(p.gkv, Mkv, 2 * d, c->template Wt<T>(bp.cattn.kw), d, nullptr, first_cross ? nullptr : p.gxa, p.gxa));
       }
+      if (!sa_need && !any({bp.cln_w, bp.cln_b})) return join_side();
       RC(dgrad(p.gq, M, d, c->template Wt<T>(bp.cattn.qw), d, nullptr, nullptr, p.gln));
       RC(join_side());
-      RC(launch_layernorm_bwd(p.gln, s.x_mid, c->P(bp.cln_w), s.ca.mean, s.ca.rstd, dx, nxt, c->G(bp.cln_w), c->G(bp.cln_b),
-                              c->G(bp.attn.ob), M, d, st));
+      RC(launch_layernorm_bwd(p.gln, s.x_mid, c->P(bp.cln_w), s.ca.mean, s.ca.rstd, dx, nxt, c->Gt(bp.cln_w), c->Gt(bp.cln_b),
+                              c->Gt(bp.attn.ob), M, d, st));
       const T* t = dx;
       dx = nxt;
       nxt = const_cast<T*>(t);
     }
     // ---- self attention ----------------------------------------------------------------------------------------
-    RC(wgrad_side(dx, d, M, d, plain_view(s.sa.o, d), d, c->G(bp.attn.ow), d));
+    if (!sa_need) return join_side();
+    if (c->tr(bp.attn.ow)) RC(wgrad_side(dx, d, M, d, plain_view(s.sa.o, d), d, c->G(bp.attn.ow), d));
     RC(dgrad(dx, M, d, c->template Wt<T>(bp.attn.ow), d, nullptr, nullptr, p.go));
     Attn a;
     attn_args(a, s.sa, false, Tq, Tq, causal);
@@ -767,16 +831,20 @@ struct Runner {
     a.dq = p.gqkv;
     a.dk = p.gqkv + d;
     a.dv = p.gqkv + 2 * d;
-    a.dq_colsum = c->G(bp.attn.qb);
-    a.dv_colsum = c->G(bp.attn.vb);
+    a.dq_colsum = c->Gt(bp.attn.qb);
+    a.dv_colsum = c->Gt(bp.attn.vb);
     a.colsum_scratch = p.cs_scratch;
     a.qtile_flags = (causal && !dec_span) ? p.qtile_flags : nullptr;  // (decoder blocks only: an encoder block's d_o has no zero rows)
     a.q_span = causal ? dec_span : nullptr;
     RC(launch_attention_bwd(a, st));
-    RC(wgrad_side(p.gqkv, 3 * d, M, 3 * d, plain_view(s.sa.ln, d), d, c->G(bp.attn.qw), d));
+    {
+      const int64_t qkv[3] = {sa_p.qw, sa_p.kw, sa_p.vw};
+      RC(wgrad_parts(p.gqkv, 3 * d, M, plain_view(s.sa.ln, d), d, qkv, 3, d));
+    }
+    if (!need_dx_in && !any({bp.attn_ln_w, bp.attn_ln_b})) return join_side();
     RC(dgrad(p.gqkv, M, 3 * d, c->template Wt<T>(bp.attn.qw), d, nullptr, nullptr, p.gln));
     RC(join_side());
-    RC(launch_layernorm_bwd(p.gln, s.x_in, c->P(bp.attn_ln_w), s.sa.mean, s.sa.rstd, dx, nxt, c->G(bp.attn_ln_w), c->G(bp.attn_ln_b),
+    RC(launch_layernorm_bwd(p.gln, s.x_in, c->P(bp.attn_ln_w), s.sa.mean, s.sa.rstd, dx, nxt, c->Gt(bp.attn_ln_w), c->Gt(bp.attn_ln_b),
                             dsum_next, M, d, st));
     *dx_in = nxt;
     return OASR_OK;
@@ -1379,19 +1447,26 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
   // position able to carry gradient; the rows behind them are never read or written by the backward
   const long Md = r.dec_rows_bwd ? r.dec_rows_bwd : (long)B * S, Me = (long)B * c->Te, M1 = (long)B * c->T1;
   hipStream_t st = r.st;
+  // Frozen parameters (oasr_set_trainable, oasr_ctx::Prune): launches that only serve frozen tensors are left out, the data gradient
+  // stops where nothing earlier in the forward is trainable.  Every segment event is still recorded (DDP buckets wait on them).
+  const oasr_ctx::Prune& pr = c->pr;
+  if (!pr.any) {
+    oasr_set_error("oasr_train backward: no parameter is trainable (oasr_set_trainable mask is all zeros)");
+    return OASR_ESTATE;
+  }
   // ---------------- backward: decoder ----------------
   int seg = 0;
   // tied logits: dE += dlogits^T . lnf ; d(lnf) = dlogits . E
   // (V = n_vocab + 1 is odd: the direct-to-LDS kernel wants a multiple of 8 rows, so the pad class gets its own 1-row GEMM)
-  {
+  if (c->tr(c->tok_emb)) {
     const int v8 = c->V & ~7;
     RC(r.wgrad(p.logits, c->Vp, Md, v8, plain_view(p.lnf, d), d, c->G(c->tok_emb), d));
     if (v8 < c->V) RC(r.wgrad(p.logits + v8, c->Vp, Md, c->V - v8, plain_view(p.lnf, d), d, c->G(c->tok_emb) + (long)v8 * d, d));
   }
   RC(r.dgrad(p.logits, Md, c->Vp, c->template Wt<T>(c->tok_emb), d, nullptr, nullptr, p.gln));
   const T* x_last = c->L_dec ? p.dec[c->L_dec - 1].x_out : p.dx0;
-  RC(launch_layernorm_bwd(p.gln, x_last, c->P(c->dec_ln_w), p.mean_f, p.rstd_f, nullptr, p.ga, c->G(c->dec_ln_w), c->G(c->dec_ln_b),
-                          c->L_dec ? c->G(c->dec[c->L_dec - 1].b2) : nullptr, Md, d, st));
+  RC(launch_layernorm_bwd(p.gln, x_last, c->P(c->dec_ln_w), p.mean_f, p.rstd_f, nullptr, p.ga, c->Gt(c->dec_ln_w), c->Gt(c->dec_ln_b),
+                          c->L_dec ? c->Gt(c->dec[c->L_dec - 1].b2) : nullptr, Md, d, st));
   RC(r.record(ev, seg++));
   const T* dx = p.ga;
   auto others = [&](const T* cur, T** a, T** b) {  // the two stream-gradient buffers that are not `cur`
@@ -1404,11 +1479,14 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
     *b = o[1];
   };
   for (int i = c->L_dec - 1; i >= 0; --i) {
-    T *sa, *sb;
-    others(dx, &sa, &sb);
-    const T* dx_in = nullptr;
-    RC(r.block_bwd(c->dec[i], p.dec[i], p, dx, sa, sb, Md, S, true, i == c->L_dec - 1, i > 0 ? c->G(c->dec[i - 1].b2) : nullptr, &dx_in));
-    dx = dx_in;
+    if (pr.all || pr.dec_blk[i] || pr.dec_in[i] || pr.enc_any) {
+      T *sa, *sb;
+      others(dx, &sa, &sb);
+      const T* dx_in = nullptr;
+      RC(r.block_bwd(c->dec[i], p.dec[i], p, dx, sa, sb, Md, S, true, i == c->L_dec - 1, i > 0 ? c->Gt(c->dec[i - 1].b2) : nullptr, &dx_in,
+                     pr.all || pr.dec_in[i], pr.all || pr.enc_any));
+      dx = dx_in;
+    }
     // the block's event says "every gradient of this block is complete" (the DDP reducer sends the bucket on it): that includes the
     // key|value weight gradient on the side stream (bit 3, experiments without events: leave it in flight until the next block needs p.gkv)
     if (ev || !(r.side_mode & 8)) RC(r.join_big());
@@ -1418,78 +1496,98 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
   RC(r.join_big());
   r.side_mode = 0;  // (the encoder's 192k-row GEMMs fill the chip on their own)
   gemm_profile_lane(0);
-  RC(launch_embedding_bwd(tokens, dx, c->G(c->tok_emb), c->G(c->dec_pos), B, S, d, PAD_ID, c->V, st, r.dec_rows, r.dec_span));
+  if (c->tr(c->tok_emb) || c->tr(c->dec_pos))
+    RC(launch_embedding_bwd(tokens, dx, c->Gt(c->tok_emb), c->Gt(c->dec_pos), B, S, d, PAD_ID, c->V, st, r.dec_rows, r.dec_span));
   RC(r.record(ev, seg++));  // decoder.positional_embedding
   RC(r.record(ev, seg++));  // token embedding (arena tail)
 
   // ---------------- backward: encoder ----------------
+  if (!pr.enc_any) {  // nothing in the encoder is trainable: neither d(xa) (skipped in the decoder blocks) nor anything below it
+    for (int i = 0; i < c->L_enc + 2; ++i) RC(r.record(ev, seg++));  // ln_post, the blocks, the conv stem
+    if (seg != (int)c->segments.size()) {
+      oasr_set_error("internal: segment count mismatch %d vs %zu", seg, c->segments.size());
+      return OASR_ESTATE;
+    }
+    return OASR_OK;
+  }
   const T* xe_last = c->L_enc ? p.enc[c->L_enc - 1].x_out : p.x0;
   if (c->L_dec == 0) OASR_CHECK_HIP(hipMemsetAsync(p.gxa, 0, (size_t)Me * d * sizeof(T), st));
-  RC(launch_layernorm_bwd(p.gxa, xe_last, c->P(c->enc_lnp_w), p.mean_p, p.rstd_p, nullptr, p.ga, c->G(c->enc_lnp_w), c->G(c->enc_lnp_b),
-                          c->L_enc ? c->G(c->enc[c->L_enc - 1].b2) : nullptr, Me, d, st));
+  const bool enc_top_in = pr.all || pr.enc_in[c->L_enc];
+  if (enc_top_in || c->tr(c->enc_lnp_w) || c->tr(c->enc_lnp_b))
+    RC(launch_layernorm_bwd(p.gxa, xe_last, c->P(c->enc_lnp_w), p.mean_p, p.rstd_p, nullptr, p.ga, c->Gt(c->enc_lnp_w), c->Gt(c->enc_lnp_b),
+                            c->L_enc ? c->Gt(c->enc[c->L_enc - 1].b2) : nullptr, Me, d, st));
   RC(r.record(ev, seg++));
   dx = p.ga;
   for (int i = c->L_enc - 1; i >= 0; --i) {
-    T *sa, *sb;
-    others(dx, &sa, &sb);
-    const T* dx_in = nullptr;
-    RC(r.block_bwd(c->enc[i], p.enc[i], p, dx, sa, sb, Me, c->Te, false, false, i > 0 ? c->G(c->enc[i - 1].b2) : nullptr, &dx_in));
-    dx = dx_in;
+    if (pr.all || pr.enc_blk[i] || pr.enc_in[i]) {
+      T *sa, *sb;
+      others(dx, &sa, &sb);
+      const T* dx_in = nullptr;
+      RC(r.block_bwd(c->enc[i], p.enc[i], p, dx, sa, sb, Me, c->Te, false, false, i > 0 ? c->Gt(c->enc[i - 1].b2) : nullptr, &dx_in,
+                     pr.all || pr.enc_in[i], false));
+      dx = dx_in;
+    }
     RC(r.record(ev, seg++));
   }
   // conv stem: x0 = gelu(u2) + pos ; u2 = conv2(h1) ; h1 = gelu(u1) ; u1 = conv1(mel)
-  {
+  if (pr.all || c->tr(c->conv2_w) || c->tr(c->conv2_b) || pr.conv1) {
     RC(launch_dgelu_mul(dx, p.u2, p.gln, Me * d, st));  // gln = d(u2)
-    OASR_CHECK_HIP(hipMemsetAsync(p.tmp_w2p, 0, (size_t)d * 3 * d * 4, st));
-    // conv2 weight gradient on the direct-to-LDS kernel: the im2col matrix [B*1500][3d] is h1 itself read as overlapping
-    // rows of 3d elements at stride 2d from h1 - d (per-sample stride 3000*d == 1500 rows * 2d, so the view is plain).
-    // Only window (b, t = 0) is wrong in its first d elements (it sees the last row of sample b-1, or the zeroed guard row,
-    // instead of the left zero padding); that rank-B term is subtracted by a second, tiny GEMM over the B first rows.
-    RC(r.wgrad(p.gln, d, Me, d, plain_view(p.h1 - d, 2L * d), 3 * d, p.tmp_w2p, 3 * d));  // (guard row zeroed by the forward)
-    {
-      GemmArgsT<T> g = gemm_defaults_t<T>();
-      g.A = plain_view(p.gln, (long)c->Te * d);          // dY rows (b, t = 0)
-      g.ta = 1;
-      g.B = plain_view(p.h1 - d, (long)c->T1 * d);       // what those windows wrongly saw as their first tap
-      g.tb = 1;
-      g.M = d;
-      g.N = d;
-      g.K = B;
-      g.alpha = -1.0f;
-      g.out_f32 = p.tmp_w2p;
-      g.ldc32 = 3 * d;
-      g.atomic = 1;
-      RC(launch_gemm(g, st));
-    }
-    RC(launch_unpack_conv_grad(p.tmp_w2p, c->G(c->conv2_w), d, d, 3 * d, st));
-    RC(launch_colsum_accum(p.gln, d, Me, d, c->G(c->conv2_b), st));
-    RC(r.dgrad(p.gln, Me, d, c->template w2p<T>(), 3 * d, nullptr, nullptr, p.gA2));
-    RC(launch_conv2_col2im_dgelu(p.gA2, p.u1, p.gu, B, c->T1, d, st));  // gu = d(u1) [B*3000, d]
-    OASR_CHECK_HIP(hipMemsetAsync(p.tmp_w1p, 0, (size_t)d * 256 * 4, st));
-    // conv1 weight gradient, same trick: windows of 3*n_mels (+ junk up to 256, whose gradient columns are never
-    // unpacked) at stride n_mels from mel_tm - n_mels; the first tap of every (b, 0) and the last tap of every (b, T1-1)
-    // see the neighbouring sample (or a zeroed guard row) instead of the zero padding -> two rank-B corrections.
-    {
-      const int nm = c->dims.n_mels;
-      RC(r.wgrad(p.gu, d, M1, d, plain_view(p.mel_tm - nm, nm), 256, p.tmp_w1p, 256));  // (guard rows zeroed by the forward)
-      for (int side = 0; side < 2; ++side) {
+    if (c->tr(c->conv2_w)) {
+      OASR_CHECK_HIP(hipMemsetAsync(p.tmp_w2p, 0, (size_t)d * 3 * d * 4, st));
+      // conv2 weight gradient on the direct-to-LDS kernel: the im2col matrix [B*1500][3d] is h1 itself read as overlapping
+      // rows of 3d elements at stride 2d from h1 - d (per-sample stride 3000*d == 1500 rows * 2d, so the view is plain).
+      // Only window (b, t = 0) is wrong in its first d elements (it sees the last row of sample b-1, or the zeroed guard row,
+      // instead of the left zero padding); that rank-B term is subtracted by a second, tiny GEMM over the B first rows.
+      RC(r.wgrad(p.gln, d, Me, d, plain_view(p.h1 - d, 2L * d), 3 * d, p.tmp_w2p, 3 * d));  // (guard row zeroed by the forward)
+      {
         GemmArgsT<T> g = gemm_defaults_t<T>();
-        g.A = plain_view(p.gu + (side ? (long)(c->T1 - 1) * d : 0), (long)c->T1 * d);  // dU rows (b, 0) / (b, T1-1)
+        g.A = plain_view(p.gln, (long)c->Te * d);          // dY rows (b, t = 0)
         g.ta = 1;
-        g.B = plain_view(side ? p.mel_tm + (long)c->T1 * nm : p.mel_tm - nm, (long)c->T1 * nm);
+        g.B = plain_view(p.h1 - d, (long)c->T1 * d);       // what those windows wrongly saw as their first tap
         g.tb = 1;
         g.M = d;
-        g.N = nm;
+        g.N = d;
         g.K = B;
         g.alpha = -1.0f;
-        g.out_f32 = p.tmp_w1p + (side ? 2 * nm : 0);
-        g.ldc32 = 256;
+        g.out_f32 = p.tmp_w2p;
+        g.ldc32 = 3 * d;
         g.atomic = 1;
         RC(launch_gemm(g, st));
       }
+      RC(launch_unpack_conv_grad(p.tmp_w2p, c->G(c->conv2_w), d, d, 3 * d, st));
     }
-    RC(launch_unpack_conv_grad(p.tmp_w1p, c->G(c->conv1_w), d, c->dims.n_mels, 256, st));
-    RC(launch_colsum_accum(p.gu, d, M1, d, c->G(c->conv1_b), st));
+    if (c->tr(c->conv2_b)) RC(launch_colsum_accum(p.gln, d, Me, d, c->G(c->conv2_b), st));
+  }
+  if (pr.all || pr.conv1) {  // the conv2 data gradient serves conv1 alone
+    RC(r.dgrad(p.gln, Me, d, c->template w2p<T>(), 3 * d, nullptr, nullptr, p.gA2));
+    RC(launch_conv2_col2im_dgelu(p.gA2, p.u1, p.gu, B, c->T1, d, st));  // gu = d(u1) [B*3000, d]
+    if (c->tr(c->conv1_w)) {
+      OASR_CHECK_HIP(hipMemsetAsync(p.tmp_w1p, 0, (size_t)d * 256 * 4, st));
+      // conv1 weight gradient, same trick: windows of 3*n_mels (+ junk up to 256, whose gradient columns are never
+      // unpacked) at stride n_mels from mel_tm - n_mels; the first tap of every (b, 0) and the last tap of every (b, T1-1)
+      // see the neighbouring sample (or a zeroed guard row) instead of the zero padding -> two rank-B corrections.
+      {
+        const int nm = c->dims.n_mels;
+        RC(r.wgrad(p.gu, d, M1, d, plain_view(p.mel_tm - nm, nm), 256, p.tmp_w1p, 256));  // (guard rows zeroed by the forward)
+        for (int side = 0; side < 2; ++side) {
+          GemmArgsT<T> g = gemm_defaults_t<T>();
+          g.A = plain_view(p.gu + (side ? (long)(c->T1 - 1) * d : 0), (long)c->T1 * d);  // dU rows (b, 0) / (b, T1-1)
+          g.ta = 1;
+          g.B = plain_view(side ? p.mel_tm + (long)c->T1 * nm : p.mel_tm - nm, (long)c->T1 * nm);
+          g.tb = 1;
+          g.M = d;
+          g.N = nm;
+          g.K = B;
+          g.alpha = -1.0f;
+          g.out_f32 = p.tmp_w1p + (side ? 2 * nm : 0);
+          g.ldc32 = 256;
+          g.atomic = 1;
+          RC(launch_gemm(g, st));
+        }
+      }
+      RC(launch_unpack_conv_grad(p.tmp_w1p, c->G(c->conv1_w), d, c->dims.n_mels, 256, st));
+    }
+    if (c->tr(c->conv1_b)) RC(launch_colsum_accum(p.gu, d, M1, d, c->G(c->conv1_b), st));
   }
   RC(r.record(ev, seg++));
   if (seg != (int)c->segments.size()) {
@@ -1648,16 +1746,106 @@ extern "C" int oasr_train_fwd_bwd_s(oasr_ctx* c, const float* mel, const int64_t
   return c->f32 ? oasr_train_fwd_bwd_s_impl<float>(c, mel, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss, logits_out, ev, workspace, workspace_bytes, stream) : oasr_train_fwd_bwd_s_impl<bf16_t>(c, mel, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss, logits_out, ev, workspace, workspace_bytes, stream);
 }
 
+// ---- frozen parameters ----------------------------------------------------------------------------------------------------------
+// The plan of the pruned backward (oasr_ctx::Prune) and the optimizer's table of trainable runs, derived here once per mask change.
+extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params) {
+  OASR_REQUIRE(c && mask && n_params == (int)c->tensors.size(), "oasr_set_trainable: need one byte per tensor (%d)", c ? (int)c->tensors.size() : 0);
+  oasr_ctx::Prune pr;
+  pr.tr.resize(c->tensors.size());
+  bool all = true, any = false;
+  for (int i = 0; i < n_params; ++i) {
+    pr.tr[i] = mask[i] ? 1 : 0;
+    all = all && pr.tr[i];
+    any = any || pr.tr[i];
+  }
+  pr.any = any;
+  // maximal stretches of trainable tensors (the arena is the tensors back to back, in table order)
+  std::vector<int64_t> runs;
+  for (size_t i = 0; i < c->tensors.size(); ++i) {
+    if (!pr.tr[i]) continue;
+    const Tensor& t = c->tensors[i];
+    if (!runs.empty() && runs[runs.size() - 2] + runs.back() == t.off) runs.back() += t.numel;
+    else {
+      runs.push_back(t.off);
+      runs.push_back(t.numel);
+    }
+  }
+  for (size_t k = 0; k < runs.size(); ++k)
+    OASR_REQUIRE((runs[k] % 4) == 0, "oasr_set_trainable: trainable runs must start and end on multiples of 4 elements");
+  auto any_in = [&](int64_t lo, int64_t hi) {  // a trainable tensor inside arena range [lo, hi)
+    for (size_t i = 0; i < c->tensors.size(); ++i)
+      if (pr.tr[i] && c->tensors[i].off >= lo && c->tensors[i].off < hi) return true;
+    return false;
+  };
+  auto blk_range = [&](const BlockP& b, int64_t* lo, int64_t* hi) {  // a block's tensors: mlp.2.weight first, attn_ln.bias last
+    *lo = b.w2;
+    *hi = b.attn_ln_b + c->d;
+  };
+  const int Ld = c->L_dec, Le = c->L_enc;
+  pr.enc_any = any_in(c->enc_lnp_w, c->tok_emb);
+  pr.conv1 = any_in(c->conv1_w, c->conv1_w + 1) || any_in(c->conv1_b, c->conv1_b + 1);
+  pr.dec_blk.assign(Ld, 0);
+  pr.enc_blk.assign(Le, 0);
+  pr.dec_in.assign(Ld + 1, 0);
+  pr.enc_in.assign(Le + 1, 0);
+  for (int i = 0; i < Ld; ++i) {
+    int64_t lo, hi;
+    blk_range(c->dec[i], &lo, &hi);
+    pr.dec_blk[i] = any_in(lo, hi);
+  }
+  for (int i = 0; i < Le; ++i) {
+    int64_t lo, hi;
+    blk_range(c->enc[i], &lo, &hi);
+    pr.enc_blk[i] = any_in(lo, hi);
+  }
+  // dec_in[i]: the gradient of block i's input is needed -- by the embeddings, a lower block, or (i > 0) a lower block's d(xa)
+  bool below = any_in(c->tok_emb, c->tok_emb + 1) || any_in(c->dec_pos, c->dec_pos + 1);
+  for (int i = 0; i <= Ld; ++i) {
+    pr.dec_in[i] = below || (i > 0 && pr.enc_any);
+    if (i < Ld) below = below || pr.dec_blk[i];
+  }
+  below = any_in(c->conv2_w, c->tok_emb);  // the conv stem
+  for (int i = 0; i <= Le; ++i) {
+    pr.enc_in[i] = below;
+    if (i < Le) below = below || pr.enc_blk[i];
+  }
+  pr.all = all;
+  int64_t* dev = nullptr;
+  if (!all && !runs.empty()) {
+    OASR_CHECK_HIP(hipMalloc(&dev, runs.size() * sizeof(int64_t)));
+    if (hipMemcpy(dev, runs.data(), runs.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(dev);
+      oasr_set_error("oasr_set_trainable: upload of the run table failed");
+      return OASR_EHIP;
+    }
+  }
+  // (the previous table may still be read by an optimizer step in flight on the caller's stream)
+  if (c->runs_dev) OASR_CHECK_HIP(hipDeviceSynchronize());
+  if (c->runs_dev) (void)hipFree(c->runs_dev);
+  c->runs_dev = dev;
+  c->n_runs = (int)(runs.size() / 2);
+  c->pr = pr;
+  return OASR_OK;
+}
+
 extern "C" int oasr_optim_step(oasr_ctx* c, float inv_loss_scale, float max_grad_norm, float lr, float beta1, float beta2, float eps,
                                float weight_decay, int64_t step, float* stats_out, void* scratch, void* stream) {
   RC(check_bound(c, true));
   OASR_REQUIRE(c->m && c->v && stats_out && scratch && step >= 1, "oasr_optim_step: bad args");
+  OASR_REQUIRE(c->pr.any, "oasr_optim_step: no parameter is trainable (oasr_set_trainable)");
   hipStream_t st = (hipStream_t)stream;
-  RC(launch_grad_stats(c->grads, c->numel, (double*)scratch, stats_out, st));
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-  RC(launch_adamw(c->params, c->grads, c->m, c->v, c->f32 ? nullptr : (bf16_t*)(c->shadow + c->sh_flat), c->numel, stats_out, inv_loss_scale, max_grad_norm,
-                  lr, beta1, beta2, eps, weight_decay, bc1, bc2, st));
+  bf16_t* sh = c->f32 ? nullptr : (bf16_t*)(c->shadow + c->sh_flat);
+  if (c->pr.all) {
+    RC(launch_grad_stats(c->grads, c->numel, (double*)scratch, stats_out, st));
+    RC(launch_adamw(c->params, c->grads, c->m, c->v, sh, c->numel, stats_out, inv_loss_scale, max_grad_norm, lr, beta1, beta2, eps,
+                    weight_decay, bc1, bc2, st));
+  } else {  // trainable runs only: clip norm and found_inf over their gradients, frozen masters / moments / shadow untouched
+    RC(launch_grad_stats_runs(c->grads, c->runs_dev, c->n_runs, (double*)scratch, stats_out, st));
+    RC(launch_adamw_runs(c->params, c->grads, c->m, c->v, sh, c->runs_dev, c->n_runs, stats_out, inv_loss_scale, max_grad_norm, lr, beta1,
+                         beta2, eps, weight_decay, bc1, bc2, st));
+  }
   return refresh_packed(c, st);
 }
 

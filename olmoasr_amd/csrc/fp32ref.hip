@@ -274,6 +274,7 @@ __global__ __launch_bounds__(256) void ln_fwd_f32_kernel(const float* __restrict
   }
 }
 
+template <int PG>  // bit 0: dgamma, bit 1: dbeta (null = frozen parameter, left out at compile time)
 __global__ __launch_bounds__(256) void ln_bwd_f32_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                         const float* __restrict__ gamma, const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, const float* __restrict__ dres,
@@ -294,8 +295,8 @@ __global__ __launch_bounds__(256) void ln_bwd_f32_kernel(const float* __restrict
         const float g = dy[row * d + c];
         xh[k] = (x[row * d + c] - mu) * rs;
         gdy[k] = g * gamma[c];
-        ag[k] += g * xh[k];
-        ab[k] += g;
+        if (PG & 1) ag[k] += g * xh[k];
+        if (PG & 2) ab[k] += g;
         s1 += gdy[k];
         s2 += gdy[k] * xh[k];
       } else {
@@ -319,8 +320,8 @@ __global__ __launch_bounds__(256) void ln_bwd_f32_kernel(const float* __restrict
   for (int k = 0; k < LN_MAXC; ++k) {
     const int c = lane + 64 * k;
     if (c < d) {
-      atomicAdd(dgamma + c, ag[k]);
-      atomicAdd(dbeta + c, ab[k]);
+      if (PG & 1) atomicAdd(dgamma + c, ag[k]);
+      if (PG & 2) atomicAdd(dbeta + c, ab[k]);
       if (dsum) atomicAdd(dsum + c, as_[k]);
     }
   }
@@ -377,9 +378,9 @@ __global__ __launch_bounds__(256) void embedding_bwd_f32_kernel(const int64_t* _
       const float g = dx[r * d + c];
       acc += g;
       const long t = tok[(long)b * S + s];
-      if (t != pad_id && t >= 0 && t < n_embed) atomicAdd(dE + t * d + c, g);
+      if (dE && t != pad_id && t >= 0 && t < n_embed) atomicAdd(dE + t * d + c, g);
     }
-    dpos[(long)s * d + c] += acc;
+    if (dpos) dpos[(long)s * d + c] += acc;
   }
 }
 __global__ __launch_bounds__(256) void colsum_f32_kernel(const float* __restrict__ x, long ld, long M, int ncols, float* __restrict__ out) {
@@ -506,11 +507,17 @@ int launch_layernorm_fwd(const float* x, const float* gamma, const float* beta, 
 }
 int launch_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dres,
                          float* dx, float* dgamma, float* dbeta, float* dsum, long rows, int d, hipStream_t s) {
-  OASR_REQUIRE(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && d > 0 && d <= 64 * LN_MAXC, "layernorm_bwd(f32): bad args");
+  OASR_REQUIRE(dy && x && gamma && mean && rstd && dx && d > 0 && d <= 64 * LN_MAXC, "layernorm_bwd(f32): bad args");
   if (rows <= 0) return OASR_OK;
   long nb = (rows + 3) / 4;
   if (nb > 512) nb = 512;
-  hipLaunchKernelGGL(ln_bwd_f32_kernel, dim3((unsigned)nb), dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
+  const dim3 g((unsigned)nb);
+  switch ((dgamma ? 1 : 0) | (dbeta ? 2 : 0)) {
+    case 3: hipLaunchKernelGGL(ln_bwd_f32_kernel<3>, g, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d); break;
+    case 2: hipLaunchKernelGGL(ln_bwd_f32_kernel<2>, g, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d); break;
+    case 1: hipLaunchKernelGGL(ln_bwd_f32_kernel<1>, g, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d); break;
+    default: hipLaunchKernelGGL(ln_bwd_f32_kernel<0>, g, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d); break;
+  }
   OASR_LAUNCH_CHECK();
   return OASR_OK;
 }
@@ -538,7 +545,7 @@ int launch_embedding_fwd(const int64_t* tok, const float* E, const float* pos, f
 }
 int launch_embedding_bwd(const int64_t* tok, const float* dx, float* dE, float* dpos, int B, int S, int d, long pad_id, long n_embed,
                          hipStream_t s, const int32_t* rows_tab, const int32_t* span) {
-  OASR_REQUIRE(tok && dx && dE && dpos, "embedding_bwd(f32): bad args");
+  OASR_REQUIRE(tok && dx && (dE || dpos), "embedding_bwd(f32): bad args");
   hipLaunchKernelGGL(embedding_bwd_f32_kernel, dim3(S), dim3(256), 0, s, tok, dx, dE, dpos, B, S, d, pad_id, n_embed, rows_tab, span);
   OASR_LAUNCH_CHECK();
   return OASR_OK;

@@ -273,3 +273,7 @@ int launch_grad_stats(const float* g, long n, double* partial /*[1024]*/, float*
 // Fused unscale + clip + AdamW (decoupled decay) + bf16 shadow emit.  Skips everything when stats[1] != 0.
 int launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long n, const float* stats, float inv_scale,
                  float max_norm, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, hipStream_t s);
+// the same two passes over a device table of (offset, numel) runs of the arena (the trainable tensors, oasr_set_trainable)
+int launch_grad_stats_runs(const float* g, const int64_t* runs, int nruns, double* partial /*[1024]*/, float* stats /*[2]*/, hipStream_t s);
+int launch_adamw_runs(float* p, const float* g, float* m, float* v, bf16_t* shadow, const int64_t* runs, int nruns, const float* stats,
+                      float inv_scale, float max_norm, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2, hipStream_t s);

@@ -80,7 +80,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
 // NCH = 16-byte chunks per lane (d <= 512 * NCH).  Each wave walks its rows two at a time: the loads of both rows (and
 // of the residual gradient) are issued before either is reduced, so twice the bytes are in flight per wave (the
 // one-row version was latency bound at 2.6 TB/s: a wave's next row was not requested until the previous was stored).
-template <int NCH>
+// PG: which parameter gradients the kernel produces (bit 0 dgamma, bit 1 dbeta).  3 is the training step's kernel; the others serve
+// frozen LayerNorms (oasr_set_trainable): their column partials and block reduction passes are compiled out, not branched around.
+template <int NCH, int PG>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const bf16_t* __restrict__ dres,
@@ -141,8 +143,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
             gy[c][i] = dv[i] * gw[c][i];
             s1 += gy[c][i];
             s2 += gy[c][i] * xh[c][i];
-            dg[c][i] += dv[i] * xh[c][i];
-            db[c][i] += dv[i];
+            if (PG & 1) dg[c][i] += dv[i] * xh[c][i];
+            if (PG & 2) db[c][i] += dv[i];
           }
         }
       }
@@ -176,6 +178,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
   }
   // block reduction of the column partials, then one atomic per column per block
   for (int pass = 0; pass < (dsum ? 3 : 2); ++pass) {
+    if ((pass == 0 && !(PG & 1)) || (pass == 1 && !(PG & 2))) continue;  // (pass is workgroup-uniform: the barriers stay matched)
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int ch = lane + 64 * c;
@@ -206,22 +209,34 @@ int launch_layernorm_fwd(const bf16_t* x, const float* gamma, const float* beta,
   return OASR_OK;
 }
 
+template <int PG>
+static void ln_bwd_launch(dim3 grid, const bf16_t* dy, const bf16_t* x, const float* gamma, const float* mean, const float* rstd,
+                          const bf16_t* dres, bf16_t* dx, float* dgamma, float* dbeta, float* dsum, long rows, int d, hipStream_t s) {
+  if (d <= 512)
+    hipLaunchKernelGGL((ln_bwd_kernel<1, PG>), grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
+  else if (d <= 1024)
+    hipLaunchKernelGGL((ln_bwd_kernel<2, PG>), grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
+  else if (d <= 1536)
+    hipLaunchKernelGGL((ln_bwd_kernel<3, PG>), grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
+  else
+    hipLaunchKernelGGL((ln_bwd_kernel<4, PG>), grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
+}
+
+// dgamma / dbeta may be null (frozen LayerNorm parameters): the matching instantiation leaves that reduction out
 int launch_layernorm_bwd(const bf16_t* dy, const bf16_t* x, const float* gamma, const float* mean, const float* rstd,
                          const bf16_t* dres, bf16_t* dx, float* dgamma, float* dbeta, float* dsum, long rows, int d, hipStream_t s) {
-  OASR_REQUIRE(dy && x && gamma && mean && rstd && dx && dgamma && dbeta, "layernorm_bwd: null pointer");
+  OASR_REQUIRE(dy && x && gamma && mean && rstd && dx, "layernorm_bwd: null pointer");
   OASR_REQUIRE(d % 8 == 0 && d <= 2048 && d > 0, "layernorm: d=%d must be a multiple of 8 and <= 2048", d);
   if (rows <= 0) return OASR_OK;
   long blocks = (rows + 3) / 4;
   if (blocks > 512) blocks = 512;  // 2 workgroups per CU; more only adds column atomics (measured: scripts/ln_bench.py history)
   const dim3 grid((unsigned)blocks);
-  if (d <= 512)
-    hipLaunchKernelGGL(ln_bwd_kernel<1>, grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
-  else if (d <= 1024)
-    hipLaunchKernelGGL(ln_bwd_kernel<2>, grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
-  else if (d <= 1536)
-    hipLaunchKernelGGL(ln_bwd_kernel<3>, grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
-  else
-    hipLaunchKernelGGL(ln_bwd_kernel<4>, grid, dim3(256), 0, s, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d);
+  switch ((dgamma ? 1 : 0) | (dbeta ? 2 : 0)) {
+    case 3: ln_bwd_launch<3>(grid, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d, s); break;
+    case 2: ln_bwd_launch<2>(grid, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d, s); break;
+    case 1: ln_bwd_launch<1>(grid, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d, s); break;
+    default: ln_bwd_launch<0>(grid, dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, rows, d, s); break;
+  }
   OASR_LAUNCH_CHECK();
   return OASR_OK;
 }

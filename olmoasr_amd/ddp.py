@@ -42,6 +42,36 @@ def plan_buckets(segments: Sequence[Tuple[int, int]], cap_elems: int) -> List[Tu
     return buckets
 
 
+def trainable_pieces(segments: Sequence[Tuple[int, int]], trainable: Sequence[Tuple[int, int]]) -> List[Tuple[int, int, int]]:
+    """The parts of every gradient segment (offset, numel) that lie inside the trainable arena ranges, as (offset, numel, segment
+    index) in completion order: what is communicated when some parameters are frozen (torch DDP leaves parameters with
+    requires_grad=False out of its buckets the same way)."""
+    out = []
+    for i, (off, n) in enumerate(segments):
+        for lo, m in trainable:
+            a, b = max(off, lo), min(off + n, lo + m)
+            if a < b:
+                out.append((a, b - a, i))
+    out.sort(key=lambda t: (t[2], t[0]))
+    return out
+
+
+def _plan_pieces(pieces: Sequence[Tuple[int, int, int]], cap_elems: int) -> List[Tuple[int, int, int]]:
+    """plan_buckets over (offset, numel, segment index) pieces: merge arena-contiguous neighbours up to ``cap_elems``."""
+    buckets = []
+    cur = None
+    for off, n, i in pieces:
+        if cur is not None and cur[0] + cur[1] == off and cur[1] + n <= cap_elems:
+            cur = (cur[0], cur[1] + n, i)
+        else:
+            if cur is not None:
+                buckets.append(cur)
+            cur = (off, n, i)
+    if cur is not None:
+        buckets.append(cur)
+    return buckets
+
+
 class GradReducer:
     """``algo``: "allreduce" (default: one RCCL all-reduce per bucket, RCCL picks rings/trees) or "direct": the all-reduce
     spelled as its two halves, ``reduce_scatter_tensor`` + ``all_gather_into_tensor``, IN PLACE on the arena slice (rank r
@@ -52,7 +82,10 @@ class GradReducer:
     available to time it against RCCL's own all-reduce; numerically it is a different summation order."""
 
     def __init__(self, flat_grads: torch.Tensor, segments: Sequence[Tuple[int, int]], bucket_cap_mb: float = 128.0,
-                 group: Optional[dist.ProcessGroup] = None, force: bool = False, algo: str = "allreduce", timing: bool = False):
+                 group: Optional[dist.ProcessGroup] = None, force: bool = False, algo: str = "allreduce", timing: bool = False,
+                 trainable: Optional[Sequence[Tuple[int, int]]] = None):
+        """``trainable``: arena ranges (offset, numel) of the parameters that get gradients (``OLMoASR.trainable_ranges()``); None =
+        the whole arena.  Frozen ranges are never communicated."""
         assert algo in ("allreduce", "direct")
         # timing=True (bench.py): every reduce() brackets the exchange with three timing-enabled HIP events -- backward enqueued to its end
         # on the compute stream, first bucket started / last bucket done on the communication stream -- read back by comm_report()
@@ -73,9 +106,14 @@ class GradReducer:
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.segments = list(segments)
-        self.buckets = plan_buckets(self.segments, int(bucket_cap_mb * (1 << 20) // flat_grads.element_size()))
-        covered = sum(n for _, n, _ in self.buckets)
-        assert covered == flat_grads.numel(), "gradient segments must tile the arena"
+        cap = int(bucket_cap_mb * (1 << 20) // flat_grads.element_size())
+        if trainable is None:
+            self.buckets = plan_buckets(self.segments, cap)
+            covered = sum(n for _, n, _ in self.buckets)
+            assert covered == flat_grads.numel(), "gradient segments must tile the arena"
+        else:
+            self.buckets = _plan_pieces(trainable_pieces(self.segments, trainable), cap)
+            assert sum(n for _, n, _ in self.buckets) == sum(n for _, n in trainable), "trainable ranges must lie inside the segments"
         self.cuda = flat_grads.is_cuda
         # None: leave the SUM (the fused path folds 1/world into the optimizer's unscale).  A float (DistributedDataParallel sets
         # 1/world): the buckets come back as the MEAN -- ReduceOp.AVG inside the collective on RCCL (no extra pass over the
@@ -204,8 +242,10 @@ class DistributedDataParallel(torch.nn.Module):
         self.module = module
         broadcast_parameters(module.flat_params, group=process_group)
         module.refresh_shadow()
+        # parameters frozen (requires_grad=False) when the wrapper is built are left out of the buckets, as torch's DDP does
+        ranges = module.trainable_ranges() if hasattr(module, "trainable_ranges") else None
         self.reducer = GradReducer(module.flat_grads, module.grad_segments, group=process_group, algo=algo, force=dist.is_initialized(),
-                                   **({} if bucket_cap_mb is None else {"bucket_cap_mb": bucket_cap_mb}))
+                                   trainable=ranges, **({} if bucket_cap_mb is None else {"bucket_cap_mb": bucket_cap_mb}))
         self.require_backward_grad_sync = True
         self._sync_this_backward = False  # decided at forward time, as torch's DDP does: a forward under no_sync() records no events
         module._autograd_post_backward = self._after_backward

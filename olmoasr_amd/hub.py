@@ -100,3 +100,43 @@ def load_model(name: str, device: Optional[Union[str, torch.device]] = None, dow
     model = OLMoASR(dims, device=device, inference=inference or rows == dims.n_vocab)
     model.load_state_dict(sd)
     return model
+
+
+def finetuning_state_dict(checkpoint: dict, seed: int = 0):
+    """(dims, state_dict) of a TRAINING-layout model (n_vocab + 1 token-embedding rows) from a checkpoint of either layout.  A released
+    inference checkpoint has n_vocab rows; the extra pad row is drawn the way a fresh model initialises the embedding (kaiming normal,
+    fan_in = n_state: model.py's _reference_init_) from ``torch.Generator().manual_seed(seed)``."""
+    from .model import _reference_init_
+    dims = dims_of(checkpoint["dims"])
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in checkpoint["model_state_dict"].items()}
+    emb = sd["decoder.token_embedding.weight"]
+    if emb.shape[0] == dims.n_vocab:
+        pad = torch.empty(1, emb.shape[1], dtype=torch.float32)
+        _reference_init_("decoder.token_embedding.weight", pad, torch.Generator().manual_seed(seed))
+        sd["decoder.token_embedding.weight"] = torch.cat([emb.float(), pad], 0)
+    elif emb.shape[0] != dims.n_vocab + 1:
+        raise ValueError(f"token embedding has {emb.shape[0]} rows; expected n_vocab ({dims.n_vocab}) or n_vocab + 1")
+    return dims, sd
+
+
+def load_for_finetuning(name_or_path: str, device: Optional[Union[str, torch.device]] = None, seed: int = 0,
+                        download_root: Optional[str] = None):
+    """A trainable model (training layout: n_vocab + 1 embedding rows, what train_timestamps.py trains) from a released inference
+    checkpoint or a training checkpoint.  ``name_or_path``: a checkpoint file, or a released model name whose file ``load_model``
+    has put in the cache directory.  Freeze what the recipe freezes afterwards (e.g. ``model.encoder.requires_grad_(False)``)."""
+    from .model import OLMoASR
+    if os.path.isfile(name_or_path):
+        path = Path(name_or_path)
+    elif name_or_path in MODEL2LINK:
+        root = Path(download_root).expanduser() if download_root else Path.home() / ".cache" / "olmoasr"
+        path = root / f"OLMoASR-{name_or_path}.pt"
+        if not path.is_file():
+            raise FileNotFoundError(f"{path} not found: fetch it once with load_model({name_or_path!r})")
+    else:
+        raise ValueError(f"Model '{name_or_path}' not found. Available models: {list(MODEL2LINK.keys())}")
+    dims, sd = finetuning_state_dict(load_checkpoint(path), seed=seed)
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    model = OLMoASR(dims, device=device)
+    model.load_state_dict(sd)
+    return model

@@ -492,7 +492,8 @@ class OLMoASR(nn.Module):
         if self._gflat is not None:
             for name, off, numel, shape in self._table:
                 mod, attr = self._module_and_attr(name)
-                mod._parameters[attr].grad = self._gflat[off:off + numel].view(shape)
+                p = mod._parameters[attr]
+                p.grad = self._gflat[off:off + numel].view(shape) if p.requires_grad else None  # frozen: no gradient, as in torch
         self._param_views = [(self._module_and_attr(name)[0]._parameters[self._module_and_attr(name)[1]], off, numel, shape)
                              for name, off, numel, shape in self._table]
 
@@ -558,6 +559,21 @@ class OLMoASR(nn.Module):
     def flat_grads(self) -> Tensor:
         return self.enable_grad_arena()
 
+    def trainable_ranges(self):
+        """[(offset, numel)]: the maximal arena ranges of parameters with ``requires_grad=True`` (in arena order), or None when every
+        parameter is trainable."""
+        if all(p.requires_grad for p, *_ in self._param_views):
+            return None
+        out = []
+        for p, off, numel, _ in sorted(self._param_views, key=lambda t: t[1]):
+            if not p.requires_grad:
+                continue
+            if out and out[-1][0] + out[-1][1] == off:
+                out[-1] = (out[-1][0], out[-1][1] + numel)
+            else:
+                out.append((off, numel))
+        return out
+
     @property
     def grad_segments(self):
         """[(offset, numel)] arena ranges in the order their gradients become final during backward."""
@@ -616,21 +632,46 @@ class OLMoASR(nn.Module):
             a = self._anchor = torch.zeros((), device=self._flat.device, requires_grad=True)
         return a
 
+    def _sync_trainable(self):
+        """``requires_grad`` of the parameters -> the engine's trainability mask (``oasr_set_trainable``), pushed when it changed.  A
+        frozen parameter has ``.grad is None`` and its gradient range of the arena is neither written nor read (the backward prunes
+        everything that only served it; the optimizer steps the trainable runs only).  A parameter that becomes trainable again starts
+        from a zeroed gradient.  Returns the mask (one bool per arena tensor)."""
+        mask = tuple(bool(p.requires_grad) for p, *_ in self._param_views)
+        if mask != getattr(self, "_trainable_mask", None):
+            if not any(mask):
+                raise N.NativeError("every parameter has requires_grad=False: nothing to train")
+            buf = (C.c_uint8 * len(mask))(*mask)
+            with torch.cuda.device(self._flat.device):
+                N.check(N.lib().oasr_set_trainable(self._ctx, buf, len(mask)), "oasr_set_trainable")
+            old = getattr(self, "_trainable_mask", None)
+            self._trainable_mask = mask
+            if self._gflat is not None:
+                for (p, off, numel, shape), t, was in zip(self._param_views, mask, old or (True,) * len(mask)):
+                    if not t:
+                        p.grad = None
+                    elif not was or p.grad is None:
+                        g = self._gflat[off:off + numel].view(shape)
+                        g.zero_()
+                        p.grad = g
+        return mask
+
     def _sync_for_autograd(self):
         """What a torch training loop may have done to the parameters since the last engine call: ``optimizer.step()`` wrote the fp32
         masters in place (-> refresh the bf16 compute copies), ``zero_grad(set_to_none=True)`` dropped ``p.grad`` (-> those gradients
-        are reset: zero their arena ranges and re-attach the views)."""
+        are reset: zero their arena ranges and re-attach the views), ``requires_grad_(False)`` froze parameters (-> ``_sync_trainable``)."""
         self.enable_grad_arena()
+        mask = self._sync_trainable()
         ver, dropped = 0, False
-        for p, off, numel, shape in self._param_views:
+        for (p, off, numel, shape), t in zip(self._param_views, mask):
             ver += p._version
-            if p.grad is None:
+            if t and p.grad is None:
                 dropped = True
         if dropped:
-            if all(p.grad is None for p, *_ in self._param_views):
+            if all(p.grad is None for (p, *_), t in zip(self._param_views, mask) if t):
                 self.zero_grad()
-            for p, off, numel, shape in self._param_views:
-                if p.grad is None:
+            for (p, off, numel, shape), t in zip(self._param_views, mask):
+                if t and p.grad is None:
                     g = self._gflat[off:off + numel].view(shape)
                     g.zero_()
                     p.grad = g
@@ -846,6 +887,7 @@ class OLMoASR(nn.Module):
             if not all(handles):
                 raise N.NativeError("segment_events must be recorded-once torch.cuda.Event objects (null HIP event handle)")
             ev = (C.c_void_p * len(segment_events))(*handles)
+        self._sync_trainable()
         if span is not None and span is not False:
             if return_logits or text_ctx is not None:
                 raise ValueError("span= cannot be combined with return_logits / text_ctx")
@@ -930,8 +972,13 @@ class OLMoASR(nn.Module):
     def optim_step(self, *, step: int, lr: float, inv_loss_scale: float = 1.0, max_grad_norm: float = 1.0, betas=(0.9, 0.98),
                    eps: float = 1e-6, weight_decay: float = 0.1):
         """scaler.unscale_ + clip_grad_norm_ + AdamW.step (train_timestamps.py:1509-1512), fused, plus the bf16 shadow
-        refresh.  Returns the device stats tensor [sum g^2 (scaled), found_inf]."""
+        refresh.  Returns the device stats tensor [sum g^2 (scaled), found_inf].
+
+        Parameters with ``requires_grad=False`` are not touched: no update, no weight decay, no moment change; the clip norm and the
+        inf/NaN check cover the trainable gradients only.  Frozen tensors keep whatever moments they had (the optimizer-state layout of
+        ``optimizer_state_dict`` is unchanged: it lists every tensor)."""
         self.init_optimizer_state()
+        self._sync_trainable()
         with torch.cuda.device(self._flat.device):
             N.check(N.lib().oasr_optim_step(self._ctx, float(inv_loss_scale), float(max_grad_norm), float(lr), float(betas[0]),
                                             float(betas[1]), float(eps), float(weight_decay), int(step), N.ptr(self._opt_stats),

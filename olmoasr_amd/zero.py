@@ -35,6 +35,10 @@ class NativeBackend:
     """The two range kernels of liboasr on the model's arenas."""
 
     def __init__(self, net):
+        if any(not p.requires_grad for p in net.parameters()):
+            raise N.NativeError("ZeRO-1 (olmoasr_amd.zero) does not support frozen parameters (requires_grad=False): its shards step the "
+                                "whole arena.  Train a partly frozen model with OLMoASR.optim_step (GradReducer / DistributedDataParallel "
+                                "for data parallelism)")
         self.net = net
         self.stats = torch.zeros(2, device=net.flat_params.device, dtype=torch.float32)
         self.scratch = torch.zeros(8192, device=net.flat_params.device, dtype=torch.uint8)

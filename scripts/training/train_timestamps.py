@@ -55,7 +55,8 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     force_dist=False,  # run the RCCL group / bucketed exchange / sharded step even at world_size 1 (single-GPU rehearsal of the N > 1 path)
     zero_stage=0,  # zero_stage 1: AdamW moments sharded over the ranks (olmoasr_amd/zero.py; the reference's FSDP script's role)
     span_backward=True,  # decoder backward over the supervised span only (oasr_train_fwd_bwd_span; same loss / gradients, forward over all 448)
-    span_forward=True)  # the decoder's forward leaves the padded positions out too (their logits are read by nothing; -4.7 % more); False = forward over all 448
+    span_forward=True,  # the decoder's forward leaves the padded positions out too (their logits are read by nothing; -4.7 % more); False = forward over all 448
+    freeze_encoder=False)  # fine-tuning: encoder.* get requires_grad=False (no gradient, no update; the backward skips the encoder)
 
 
 class Args(dict):
@@ -357,6 +358,8 @@ def main(argv=None):
     betas = tuple(args.betas)
     dims = VARIANT_TO_DIMS[args.model_variant]
     net = OLMoASR(dims, device=dev, seed=args.seed, compute_dtype=args.precision)
+    if args.freeze_encoder:
+        net.encoder.requires_grad_(False)
     ddp.broadcast_parameters(net.flat_params)  # DDP ctor _sync_module_states
     net.refresh_shadow()
     sharded = None
@@ -365,7 +368,8 @@ def main(argv=None):
         sharded = zero.ShardedOptimizer(net.flat_params, net.flat_grads, zero.NativeBackend(net), force=force_dist)  # moments for the owned range only
     else:
         net.init_optimizer_state()
-    reducer = (ddp.GradReducer(net.flat_grads, net.grad_segments, bucket_cap_mb=args.bucket_cap_mb, algo=args.reducer, force=force_dist)
+    reducer = (ddp.GradReducer(net.flat_grads, net.grad_segments, bucket_cap_mb=args.bucket_cap_mb, algo=args.reducer, force=force_dist,
+                               trainable=net.trainable_ranges())
                if (world_size > 1 or force_dist) and sharded is None else None)
     scaler = GradScalerState()
     accum = accumulation_steps(args.eff_batch_size, world_size, args.train_batch_size)
