@@ -35,7 +35,7 @@ typedef struct oasr_dims {
 const char* oasr_last_error(void);
 /* ABI version: 100 * major + minor.  Structs passed by pointer (oasr_attn_args, oasr_gemm_args) only grow at the end and only with a
  * major bump; olmoasr_amd/_native.py refuses to drive a library whose version differs from OASR_ABI_VERSION. */
-#define OASR_ABI_VERSION 212
+#define OASR_ABI_VERSION 213
 int oasr_version(void);
 
 /* ---- log-mel front end: whisper.audio.log_mel_spectrogram as called at train_timestamps.py:196,214 and
@@ -65,6 +65,27 @@ oasr_ctx* oasr_create_ex(const oasr_dims* dims, int embed_rows);
 #define OASR_DTYPE_F32 1
 oasr_ctx* oasr_create_ex2(const oasr_dims* dims, int embed_rows, int compute_dtype);
 int oasr_compute_dtype(const oasr_ctx*);
+/* ABI 213: LoRA adapters in weight space (peft's LoraConfig(r, lora_alpha, target_modules) on a frozen base).
+ * targets: n_targets tensor indices (oasr_param_info order of the context WITHOUT adapters) of block Linear weights -- attn / cross_attn
+ * query, key, value, out and mlp.0 / mlp.2 of any block; rank 1..OASR_LORA_MAX_RANK; scale = lora_alpha / rank.  Target j with weight
+ * W0 [out, in] gains two tensors, "<module>.lora_A" [rank, in] and "<module>.lora_B" [out, rank], and computes with the effective weight
+ *     W = W0 + scale * lora_B . lora_A
+ * (= torch.nn.utils.parametrize / minLoRA).  The adapters sit in the parameter table in target order, between the conv stem and the token
+ * embedding, and form the LAST gradient segment.  Every compute copy of an adapted tensor (the bf16 shadow slot; fp32 mode: a full fp32
+ * copy of the arena that only adapter contexts have) holds W, re-derived by oasr_refresh_shadow and at the end of oasr_optim_step, so the
+ * forward, the decode engines and the data gradients are unchanged.  The backward writes dL/dW of an adapted tensor into workspace scratch
+ * (never into W0's gradient range) and projects it: d lora_B = scale * dW . lora_A^T, d lora_A = scale * lora_B^T . dW, accumulated into the
+ * gradient arena before the last segment's event.  An adapted base weight can never be trainable (oasr_set_trainable refuses it), and an
+ * adapter context has no default mask: the backward entries and oasr_optim_step return OASR_ESTATE until oasr_set_trainable has been
+ * called.  ZeRO-1's range entries refuse adapter contexts.
+ * n_targets == 0 gives exactly oasr_create_ex2's context. */
+#define OASR_LORA_MAX_RANK 64
+oasr_ctx* oasr_create_ex3(const oasr_dims* dims, int embed_rows, int compute_dtype, const int32_t* targets, int n_targets, int rank, float scale);
+int oasr_lora_count(const oasr_ctx*); /* adapted tensors */
+/* Fold the adapters into the master weights: W0 <- W0 + scale * lora_B . lora_A (the fp32 expression the compute copy is rounded from: a
+ * model built from the merged masters has a bit-identical compute copy).  The adapters themselves are left as they are; the caller drops
+ * them (a context without adapters over the merged base weights). */
+int oasr_lora_merge(oasr_ctx*, void* stream);
 void oasr_destroy(oasr_ctx*);
 
 /* Parameter table: one flat fp32 arena in gradient-ready (reverse-backward) order; the Python modules expose
@@ -175,7 +196,8 @@ int oasr_zero_grad(oasr_ctx*, void* stream);
  * the default is all ones.  From then on the backward entries (oasr_train_fwd_bwd, _s, _span, oasr_train_bwd) neither launch nor
  * write anything whose only purpose is a frozen tensor's gradient: frozen ranges of the gradient arena are left as they are.
  * oasr_optim_step updates, decays and clips over the trainable tensors only (frozen moments stay as they are).  With no trainable
- * tensor the backward entries return OASR_ESTATE.  The call is synchronous (it uploads the optimizer's table of trainable runs). */
+ * tensor the backward entries return OASR_ESTATE.  The call is synchronous (it uploads the optimizer's table of trainable runs).
+ * ABI 213: a mask that makes an adapted base weight trainable is refused (OASR_EINVAL, oasr_create_ex3). */
 int oasr_set_trainable(oasr_ctx*, const uint8_t* mask, int n_params);
 
 /* scaler.unscale_ + clip_grad_norm_(max_norm) + AdamW.step + bf16 shadow refresh (train_timestamps.py:1509-1512).
@@ -237,6 +259,14 @@ int oasr_attention_scores(const oasr_attn_args*, int dtype, float* scores, void*
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 int oasr_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
+/* The two LoRA kernels as unit operators (the engine calls the same launchers).  merge: out = w0 + scale * B . A (w0 [rows, cols] f32,
+ * A [rank, cols], B [rows, rank]; out_dtype OASR_DTYPE_BF16 / OASR_DTYPE_F32; out may be w0 for f32).  grad: dA += scale * B^T . dW,
+ * dB += scale * dW . A^T, scratch of oasr_lora_grad_scratch_bytes. */
+int oasr_lora_merge_op(const float* w0, const float* A, const float* B, int rows, int cols, int rank, float scale, int out_dtype, void* out,
+                       void* stream);
+size_t oasr_lora_grad_scratch_bytes(int rows, int cols, int rank);
+int oasr_lora_grad_op(const float* dW, const float* A, const float* B, int rows, int cols, int rank, float scale, float* dA, float* dB,
+                      void* scratch, void* stream);
 /* Per-row token pick over fp32 logits [rows, ld] (first V columns): tok = argmax(logits + mask + mask2) with the lowest index
  * among equal maxima, logprob = log_softmax(logits + masks)[tok] (NULL to skip).  masks: additive f32 [V] (0 / -inf) or NULL.
  * = the tail of whisper.decoding GreedyDecoder.update (argmax + log_softmax gather) after SuppressBlank / SuppressTokens,

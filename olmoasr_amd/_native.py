@@ -44,9 +44,10 @@ class AttnArgs(C.Structure):
                 ("q_rows", C.c_void_p), ("k_rows", C.c_void_p), ("q_span", C.c_void_p)]
 
 
-ABI_VERSION = 212  # include/oasr.h: OASR_ABI_VERSION (212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
+ABI_VERSION = 213  # include/oasr.h: OASR_ABI_VERSION (213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 ROWTAB = 16        # include/oasr.h: OASR_ROWTAB (entries per sample of a chunk-row table)
+LORA_MAX_RANK = 64  # include/oasr.h: OASR_LORA_MAX_RANK
 
 
 def _declare(lib):
@@ -61,6 +62,12 @@ def _declare(lib):
         "oasr_create_ex": (vp, [C.POINTER(Dims), i32]),
         "oasr_create_ex2": (vp, [C.POINTER(Dims), i32, i32]),
         "oasr_compute_dtype": (i32, [vp]),
+        "oasr_create_ex3": (vp, [C.POINTER(Dims), i32, i32, vp, i32, i32, f32]),
+        "oasr_lora_count": (i32, [vp]),
+        "oasr_lora_merge": (i32, [vp, vp]),
+        "oasr_lora_merge_op": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
+        "oasr_lora_grad_scratch_bytes": (sz, [i32, i32, i32]),
+        "oasr_lora_grad_op": (i32, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp]),
         "oasr_encode": (i32, [vp, vp, i32, vp, vp, sz, vp]),
         "oasr_kv_cache_bytes": (sz, [vp, i32]),
         "oasr_decode_step_workspace_bytes": (sz, [vp, i32]),

@@ -85,6 +85,7 @@ struct oasr_ctx {
   struct Prune {
     bool all = true, any = true;
     std::vector<uint8_t> tr;                 // [tensors]
+    std::vector<uint8_t> need;               // [tensors]: tr, or an adapted base weight one of whose adapters is trainable
     bool enc_any = true;                     // some encoder tensor (ln_post, blocks, conv stem): the encoder backward and d(xa) run
     std::vector<uint8_t> dec_blk, enc_blk;   // [L]: the block holds a trainable tensor
     std::vector<uint8_t> dec_in, enc_in;     // [L + 1]: the data gradient out of block i (into the residual stream below it) is needed
@@ -92,17 +93,34 @@ struct oasr_ctx {
   } pr;
   int64_t* runs_dev = nullptr;  // [2 * n_runs] (offset, numel) of the maximal trainable stretches of the arena (device)
   int n_runs = 0;
-  // is the tensor at arena offset `off` trainable
-  bool tr(int64_t off) const {
-    if (pr.all) return true;
+  bool mask_set = false;  // oasr_set_trainable has been called (an adapter context has no default mask)
+  // ---- LoRA adapters (oasr_create_ex3) ----
+  struct Lora {
+    int64_t w, a, b;  // arena offsets: base weight [out, in], lora_A [r, in], lora_B [out, r]
+    int out, in;
+    int64_t dw;       // offset (floats) of the base weight's gradient in a training step's workspace scratch (Plan::lora_dw)
+  };
+  std::vector<Lora> lora;
+  std::vector<int> lora_of;           // [tensors]: index into `lora` of an adapted base weight, -1 otherwise
+  int lora_r = 0;
+  float lora_s = 0.f;
+  int64_t lora_dw_floats = 0, lora_part_floats = 0;  // training workspace: adapted weight gradients, lora_grad's partial sums
+  int64_t stem_end = 0;  // arena end of the conv stem (= the token embedding's offset when there are no adapters)
+  size_t sh_eff = 0;     // fp32 mode with adapters: the fp32 effective copy of the arena in the shadow (0 = none)
+  size_t tidx(int64_t off) const {  // the tensor at arena offset `off`
     size_t lo = 0, hi = tensors.size();
     while (hi - lo > 1) {
       const size_t mid = (lo + hi) / 2;
       if (tensors[mid].off <= off) lo = mid;
       else hi = mid;
     }
-    return pr.tr[lo] != 0;
+    return lo;
   }
+  // is the tensor at arena offset `off` trainable
+  bool tr(int64_t off) const { return pr.all || pr.tr[tidx(off)] != 0; }
+  // does the backward need the weight gradient of the tensor at `off`: trainable, or an adapted base weight with a trainable adapter
+  bool wn(int64_t off) const { return pr.all || pr.need[tidx(off)] != 0; }
+  int lora_at(int64_t off) const { return lora.empty() ? -1 : lora_of[tidx(off)]; }
   float* Gt(int64_t off) const { return tr(off) ? grads + off : nullptr; }  // gradient of a tensor, null when it is frozen
   ~oasr_ctx() {
     if (runs_dev) (void)hipFree(runs_dev);
@@ -115,7 +133,8 @@ struct oasr_ctx {
     if (side.stream) (void)hipStreamDestroy(side.stream);
     if (side.big) (void)hipStreamDestroy(side.big);
   }
-  // compute copy of the weight at arena offset `off`: the bf16 shadow, or -- fp32 validation -- the master weights themselves
+  // compute copy of the weight at arena offset `off`: the bf16 shadow, or -- fp32 validation -- the master weights themselves (with
+  // adapters: their fp32 effective copy).  An adapted tensor's compute copy is its effective weight W0 + s * B . A.
   template <typename T>
   const T* Wt(int64_t off) const;
   template <typename T>
@@ -130,7 +149,7 @@ struct oasr_ctx {
 template <>
 inline const bf16_t* oasr_ctx::Wt<bf16_t>(int64_t off) const { return (const bf16_t*)(shadow + sh_flat) + off; }
 template <>
-inline const float* oasr_ctx::Wt<float>(int64_t off) const { return params + off; }
+inline const float* oasr_ctx::Wt<float>(int64_t off) const { return sh_eff ? (const float*)(shadow + sh_eff) + off : params + off; }
 
 namespace {
 
@@ -243,6 +262,7 @@ struct Plan {
   // supervised-span step (oasr_train_fwd_bwd_span): chunk-row table of the decoder's token rows, spans, targets in row order
   int32_t *rows, *span_dev;
   int64_t* targets_phys;
+  float *lora_dw, *lora_part;  // adapter contexts: the adapted weights' gradients (oasr_ctx::Lora::dw) and lora_grad's partial sums
 };
 
 static void plan_attn(Arena& A, AttnSave& s, long M, long Mkv, int d, int B, int H, long Tq, bool cross, bool train) {
@@ -314,6 +334,7 @@ static void make_plan(const oasr_ctx* c, Arena& A, Plan& p, int B, int S, bool t
   p.n_valid = (int32_t*)A.raw(256);
   p.rows = p.span_dev = nullptr;
   p.targets_phys = nullptr;
+  p.lora_dw = p.lora_part = nullptr;
   if (train) {
     p.rows = (int32_t*)A.raw((size_t)B * OASR_ROWTAB * 4);
     p.span_dev = (int32_t*)A.raw((size_t)B * 4);
@@ -336,6 +357,10 @@ static void make_plan(const oasr_ctx* c, Arena& A, Plan& p, int B, int S, bool t
     p.gemm_cs_scratch = A.f32((size_t)2 * cdiv(Mmax, 256) * 4 * d + 64);
     p.tmp_w1p = A.f32((long)d * 256);
     p.tmp_w2p = A.f32((long)d * 3 * d);
+    if (!c->lora.empty()) {
+      p.lora_dw = A.f32(c->lora_dw_floats);
+      p.lora_part = A.f32(c->lora_part_floats);
+    }
     // the residual stream entering each block (block_fwd records the same pointers): a plan re-made for a backward-only call
     // (oasr_train_bwd) must be complete without having run the forward
     for (int i = 0; i < c->L_enc; ++i) p.enc[i].x_in = i ? p.enc[i - 1].x_out : p.x0;
@@ -359,6 +384,12 @@ struct Runner {
   // positions whose logits the reference computes and nothing ever reads (no supervised query attends to them, the loss ignores them).
   long dec_rows_fwd = 0;
   const float* mel_clip_max = nullptr;  // [B] or null: `mel` is oasr_log_mel_raw's output, finalized in the time-major transpose
+  float* lora_dw = nullptr;             // adapter contexts, backward: Plan::lora_dw
+  // where the weight gradient of the tensor at `off` goes: its arena range, or -- an adapted base weight, frozen -- its workspace scratch
+  float* Gw(int64_t off) const {
+    const int j = c->lora_at(off);
+    return j >= 0 ? lora_dw + c->lora[j].dw : c->G(off);
+  }
 
   int linear(const T* x, long M, int K, const T* W, int N, const float* bias, int act, const T* resid, T* out,
              T* out_pre) {
@@ -733,21 +764,22 @@ struct Runner {
   // and every launch is the one of the plain step.
   // A weight gradient over consecutive [rows x K] tensors of the arena that one GEMM fills (q|k|v, cross k|v): one launch when all are
   // trainable, one per trainable tensor otherwise (columns j*rows.. of dy).
+  // An adapted tensor's gradient goes to its scratch (Gw), so it always gets a launch of its own.
   int wgrad_parts(const T* dy, long ldy, long M, const View& x, int K, const int64_t* offs, int n, int rows) {
     int ntr = 0;
-    for (int j = 0; j < n; ++j) ntr += c->tr(offs[j]) ? 1 : 0;
+    for (int j = 0; j < n; ++j) ntr += (c->tr(offs[j]) && c->lora_at(offs[j]) < 0) ? 1 : 0;
     if (ntr == n) return wgrad_side(dy, ldy, M, n * rows, x, K, c->G(offs[0]), K);
     for (int j = 0; j < n; ++j)
-      if (c->tr(offs[j])) RC(wgrad_side(dy + (long)j * rows, ldy, M, rows, x, K, c->G(offs[j]), K));
+      if (c->wn(offs[j])) RC(wgrad_side(dy + (long)j * rows, ldy, M, rows, x, K, Gw(offs[j]), K));
     return OASR_OK;
   }
   int block_bwd(const BlockP& bp, const BlockSave& s, Plan& p, const T* dx_out, T* scratch_a, T* scratch_b, long M,
                 long Tq, bool causal, bool first_cross, float* dsum_next, const T** dx_in, bool need_dx_in = true, bool need_xa = true) {
     const int d = c->d;
     const T* xm = bp.cross ? s.x_mid2 : s.x_mid;
-    auto any = [&](std::initializer_list<int64_t> offs) {
+    auto any = [&](std::initializer_list<int64_t> offs) {  // (weights: adapted ones count -- their adapters need dW)
       for (int64_t o : offs)
-        if (c->tr(o)) return true;
+        if (c->wn(o)) return true;
       return false;
     };
     const AttnP& sa_p = bp.attn;
@@ -757,10 +789,10 @@ struct Runner {
     const bool mlp_need = (bp.cross ? ca_need : sa_need) || any({bp.w1, bp.b1, bp.mlp_ln_w, bp.mlp_ln_b});
     *dx_in = nullptr;
     // ---- MLP -----------------------------------------------------------------------------------------------
-    if (c->tr(bp.w2)) RC(wgrad_side(dx_out, d, M, d, plain_view(s.hg, 4 * d), 4 * d, c->G(bp.w2), 4 * d));
+    if (c->wn(bp.w2)) RC(wgrad_side(dx_out, d, M, d, plain_view(s.hg, 4 * d), 4 * d, Gw(bp.w2), 4 * d));
     if (!mlp_need) return join_side();
     RC(dgrad(dx_out, M, d, c->template Wt<T>(bp.w2), 4 * d, s.u, nullptr, p.gu, c->Gt(bp.b1), true));  // s.u = GELU'(u); + fused mlp.0.bias gradient
-    if (c->tr(bp.w1)) RC(wgrad_side(p.gu, 4 * d, M, 4 * d, plain_view(s.ln2, d), d, c->G(bp.w1), d));
+    if (c->wn(bp.w1)) RC(wgrad_side(p.gu, 4 * d, M, 4 * d, plain_view(s.ln2, d), d, Gw(bp.w1), d));
     RC(dgrad(p.gu, M, 4 * d, c->template Wt<T>(bp.w1), d, nullptr, nullptr, p.gln));
     RC(join_side());
     RC(launch_layernorm_bwd(p.gln, xm, c->P(bp.mlp_ln_w), s.mean2, s.rstd2, dx_out, scratch_a, c->Gt(bp.mlp_ln_w), c->Gt(bp.mlp_ln_b),
@@ -770,7 +802,7 @@ struct Runner {
     // ---- cross attention ---------------------------------------------------------------------------------------
     if (bp.cross) {
       const long Mkv = (long)B * c->Te;
-      if (c->tr(bp.cattn.ow)) RC(wgrad_side(dx, d, M, d, plain_view(s.ca.o, d), d, c->G(bp.cattn.ow), d));
+      if (c->wn(bp.cattn.ow)) RC(wgrad_side(dx, d, M, d, plain_view(s.ca.o, d), d, Gw(bp.cattn.ow), d));
       if (!ca_need) return join_side();
       RC(dgrad(dx, M, d, c->template Wt<T>(bp.cattn.ow), d, nullptr, nullptr, p.go));
       Attn a;
@@ -790,7 +822,7 @@ struct Runner {
       a.q_span = dec_span;
       RC(join_big());  // (the previous layer's key|value gradients still read p.gkv)
       RC(launch_attention_bwd(a, st));
-      if (c->tr(bp.cattn.qw)) RC(wgrad_side(p.gq, d, M, d, plain_view(s.ca.ln, d), d, c->G(bp.cattn.qw), d));
+      if (c->wn(bp.cattn.qw)) RC(wgrad_side(p.gq, d, M, d, plain_view(s.ca.ln, d), d, Gw(bp.cattn.qw), d));
       const bool kv_tr = any({bp.cattn.kw, bp.cattn.vw});
       if (kv_tr || need_xa) {
         const bool big = (side_mode & 4) != 0;
@@ -800,12 +832,12 @@ struct Runner {
         }
         OnStream on(st, big ? c->side.big : st);
         if (kv_tr) {
-          if (c->tr(bp.cattn.kw) && c->tr(bp.cattn.vw)) {
+          if (c->tr(bp.cattn.kw) && c->tr(bp.cattn.vw) && c->lora_at(bp.cattn.kw) < 0 && c->lora_at(bp.cattn.vw) < 0) {
             RC(wgrad(p.gkv, 2 * d, Mkv, 2 * d, plain_view(p.xa, d), d, c->G(bp.cattn.kw), d));
           } else {
             const int64_t kv[2] = {bp.cattn.kw, bp.cattn.vw};
             for (int j = 0; j < 2; ++j)
-              if (c->tr(kv[j])) RC(wgrad(p.gkv + (long)j * d, 2 * d, Mkv, d, plain_view(p.xa, d), d, c->G(kv[j]), d));
+              if (c->wn(kv[j])) RC(wgrad(p.gkv + (long)j * d, 2 * d, Mkv, d, plain_view(p.xa, d), d, Gw(kv[j]), d));
           }
         }
         // d(xa) accumulates over the decoder layers (bf16, like autograd's accumulation into xa.grad)
@@ -822,7 +854,7 @@ struct Runner {
     }
     // ---- self attention ----------------------------------------------------------------------------------------
     if (!sa_need) return join_side();
-    if (c->tr(bp.attn.ow)) RC(wgrad_side(dx, d, M, d, plain_view(s.sa.o, d), d, c->G(bp.attn.ow), d));
+    if (c->wn(bp.attn.ow)) RC(wgrad_side(dx, d, M, d, plain_view(s.sa.o, d), d, Gw(bp.attn.ow), d));
     RC(dgrad(dx, M, d, c->template Wt<T>(bp.attn.ow), d, nullptr, nullptr, p.go));
     Attn a;
     attn_args(a, s.sa, false, Tq, Tq, causal);
@@ -873,7 +905,9 @@ int check_bound(const oasr_ctx* c, bool need_grads) {
 }  // namespace
 
 // ================================================ C ABI ============================================================
-extern "C" oasr_ctx* oasr_create_ex2(const oasr_dims* dm, int embed_rows, int compute_dtype);
+extern "C" oasr_ctx* oasr_create_ex2(const oasr_dims* dm, int embed_rows, int compute_dtype) {
+  return oasr_create_ex3(dm, embed_rows, compute_dtype, nullptr, 0, 0, 0.f);
+}
 extern "C" oasr_ctx* oasr_create_ex(const oasr_dims* dm, int embed_rows) { return oasr_create_ex2(dm, embed_rows, OASR_DTYPE_BF16); }
 extern "C" oasr_ctx* oasr_create(const oasr_dims* dm) { return oasr_create_ex2(dm, dm ? dm->n_vocab + 1 : 0, OASR_DTYPE_BF16); }
 
@@ -881,9 +915,15 @@ extern "C" oasr_ctx* oasr_create(const oasr_dims* dm) { return oasr_create_ex2(d
 // n_vocab for the inference model (olmoasr/inf_model.py:302; checkpoints written by scripts/eval/gen_inf_ckpt.py)
 // compute_dtype: OASR_DTYPE_BF16 = the production kernels; OASR_DTYPE_F32 = the fp32 validation kernels on the same
 // schedule (reference: precision="float32", scripts/training/train_timestamps.py:2128,2220-2224)
-extern "C" oasr_ctx* oasr_create_ex2(const oasr_dims* dm, int embed_rows, int compute_dtype) {
+// targets / rank / scale: LoRA adapters on block Linear weights (include/oasr.h, ABI 213; n_targets == 0: none)
+extern "C" oasr_ctx* oasr_create_ex3(const oasr_dims* dm, int embed_rows, int compute_dtype, const int32_t* targets, int n_targets, int rank,
+                                     float scale) {
   if (compute_dtype != OASR_DTYPE_BF16 && compute_dtype != OASR_DTYPE_F32) {
     oasr_set_error("oasr_create_ex2: compute_dtype must be OASR_DTYPE_BF16 or OASR_DTYPE_F32");
+    return nullptr;
+  }
+  if (n_targets < 0 || (n_targets > 0 && (!targets || rank < 1 || rank > OASR_LORA_MAX_RANK || !(scale == scale)))) {
+    oasr_set_error("oasr_create_ex3: adapters need a target list, rank 1..%d and a finite scale", OASR_LORA_MAX_RANK);
     return nullptr;
   }
   if (!dm) {
@@ -945,9 +985,57 @@ extern "C" oasr_ctx* oasr_create_ex2(const oasr_dims* dm, int embed_rows, int co
     c->conv1_b = b.add("encoder.conv1.bias", {d});
     c->segments.push_back({s0, b.cur - s0});
   }
+  c->stem_end = b.cur;
+  if (n_targets > 0) {  // LoRA adapters: the last gradient segment, between the conv stem and the token embedding
+    static const char* kinds[] = {".query.weight", ".key.weight", ".value.weight", ".out.weight", ".mlp.0.weight", ".mlp.2.weight"};
+    const int n_base = (int)c->tensors.size();
+    c->lora_of.assign((size_t)n_base + 2 * n_targets + 1, -1);
+    c->lora_r = rank;
+    c->lora_s = scale;
+    for (int j = 0; j < n_targets; ++j) {
+      const int ti = targets[j];
+      bool ok = ti >= 0 && ti < n_base && c->lora_of[ti] < 0 && c->tensors[ti].name.find(".blocks.") != std::string::npos;
+      if (ok) {
+        const std::string& nm = c->tensors[ti].name;
+        bool kind = false;
+        for (const char* k : kinds) kind = kind || (nm.size() > strlen(k) && nm.compare(nm.size() - strlen(k), strlen(k), k) == 0);
+        ok = kind && c->tensors[ti].ndim == 2;
+      }
+      if (!ok) {
+        oasr_set_error("oasr_create_ex3: target %d (tensor %d%s%s) is not a block Linear weight (attn / cross_attn query|key|value|out, mlp.0, "
+                       "mlp.2) or is listed twice", j, ti, ti >= 0 && ti < n_base ? ": " : "", ti >= 0 && ti < n_base ? c->tensors[ti].name.c_str() : "");
+        delete c;
+        return nullptr;
+      }
+      c->lora_of[ti] = j;
+    }
+    const int64_t s0 = b.cur;
+    for (int j = 0; j < n_targets; ++j) {
+      const Tensor w = c->tensors[targets[j]];
+      const std::string mod = w.name.substr(0, w.name.size() - strlen(".weight"));
+      oasr_ctx::Lora L;
+      L.w = w.off;
+      L.out = (int)w.shape[0];
+      L.in = (int)w.shape[1];
+      L.a = b.add(mod + ".lora_A", {rank, L.in});
+      L.b = b.add(mod + ".lora_B", {L.out, rank});
+      L.dw = c->lora_dw_floats;
+      c->lora_dw_floats += (int64_t)L.out * L.in;
+      const int64_t part = (int64_t)lora_grad_scratch_floats(L.out, L.in, rank);
+      if (part > c->lora_part_floats) c->lora_part_floats = part;
+      c->lora.push_back(L);
+    }
+    c->segments.push_back({s0, b.cur - s0});
+    c->pr.all = c->pr.any = false;  // no default mask (include/oasr.h): nothing is trainable until oasr_set_trainable
+  }
   c->tok_emb = b.add("decoder.token_embedding.weight", {c->V, d});
   c->segments[emb_seg] = {c->tok_emb, (int64_t)c->V * d};
   c->numel = b.cur;
+  if (!c->lora.empty()) {
+    c->lora_of.resize(c->tensors.size(), -1);
+    c->pr.tr.assign(c->tensors.size(), 0);
+    c->pr.need.assign(c->tensors.size(), 0);
+  }
   {  // decoder layer 0's tensor offsets (decode_xcd.hip::XLayer order) + the per-layer strides: the one-launch step engine derives every
      // layer's addresses from them, so the blocks must be laid out back to back with one stride -- checked here, engine off otherwise
     auto offs = [](const BlockP& bp) {
@@ -981,11 +1069,16 @@ extern "C" oasr_ctx* oasr_create_ex2(const oasr_dims* dm, int embed_rows, int co
   off = al(off + (size_t)d * 3 * d * esz);
   c->sh_aux = off;
   off = al(off + (size_t)c->aux_floats * 4);
+  if (c->f32 && !c->lora.empty()) {  // fp32 effective copy of the whole arena (adapted slots = W0 + s * B . A)
+    c->sh_eff = off;
+    off = al(off + ((size_t)c->numel + 64) * 4);
+  }
   c->sh_total = off;
   return c;
 }
 extern "C" void oasr_destroy(oasr_ctx* c) { delete c; }
 extern "C" int oasr_compute_dtype(const oasr_ctx* c) { return c && c->f32 ? OASR_DTYPE_F32 : OASR_DTYPE_BF16; }
+extern "C" int oasr_lora_count(const oasr_ctx* c) { return c ? (int)c->lora.size() : 0; }
 extern "C" int oasr_param_count(const oasr_ctx* c) { return c ? (int)c->tensors.size() : 0; }
 extern "C" int64_t oasr_param_numel(const oasr_ctx* c) { return c ? c->numel : 0; }
 extern "C" int oasr_param_info(const oasr_ctx* c, int idx, char* name, int name_cap, int64_t* offset, int64_t* numel, int* ndim,
@@ -1045,6 +1138,18 @@ static int refresh_packed(oasr_ctx* c, hipStream_t st) {
   return OASR_OK;
 }
 
+// Adapter contexts: the compute copies of the adapted tensors = their effective weights (lora_merge of the current masters and adapters).
+// fp32 mode first copies the whole arena into the effective copy (validation mode: every tensor's operand comes from there).
+static int refresh_lora(oasr_ctx* c, hipStream_t st) {
+  if (c->lora.empty()) return OASR_OK;
+  float* eff = c->f32 ? (float*)(c->shadow + c->sh_eff) : nullptr;
+  bf16_t* flat = c->f32 ? nullptr : (bf16_t*)(c->shadow + c->sh_flat);
+  if (eff) OASR_CHECK_HIP(hipMemcpyAsync(eff, c->params, (size_t)c->numel * 4, hipMemcpyDeviceToDevice, st));
+  for (const oasr_ctx::Lora& L : c->lora)
+    RC(launch_lora_merge(c->P(L.w), c->P(L.a), c->P(L.b), L.out, L.in, c->lora_r, c->lora_s, eff ? eff + L.w : nullptr, flat ? flat + L.w : nullptr, st));
+  return OASR_OK;
+}
+
 extern "C" int oasr_refresh_shadow(oasr_ctx* c, void* stream) {
   RC(check_bound(c, false));
   hipStream_t st = (hipStream_t)stream;
@@ -1053,7 +1158,16 @@ extern "C" int oasr_refresh_shadow(oasr_ctx* c, void* stream) {
     RC(launch_cast_f32_bf16(c->params, flat, c->numel, st));
     OASR_CHECK_HIP(hipMemsetAsync(flat + c->numel, 0, ((size_t)(c->Vp - c->V) * c->d + 64) * 2, st));
   }
+  RC(refresh_lora(c, st));
   return refresh_packed(c, st);
+}
+
+extern "C" int oasr_lora_merge(oasr_ctx* c, void* stream) {
+  RC(check_bound(c, false));
+  OASR_REQUIRE(!c->lora.empty(), "oasr_lora_merge: the context has no adapters");
+  for (const oasr_ctx::Lora& L : c->lora)  // in place: every element is read and written by the same thread
+    RC(launch_lora_merge(c->P(L.w), c->P(L.a), c->P(L.b), L.out, L.in, c->lora_r, c->lora_s, c->params + L.w, nullptr, (hipStream_t)stream));
+  return OASR_OK;
 }
 
 extern "C" size_t oasr_workspace_bytes(const oasr_ctx* c, int B, int S, int mode) {
@@ -1450,10 +1564,35 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
   // Frozen parameters (oasr_set_trainable, oasr_ctx::Prune): launches that only serve frozen tensors are left out, the data gradient
   // stops where nothing earlier in the forward is trainable.  Every segment event is still recorded (DDP buckets wait on them).
   const oasr_ctx::Prune& pr = c->pr;
+  if (!c->lora.empty() && !c->mask_set) {
+    oasr_set_error("oasr_train backward: a context with adapters needs oasr_set_trainable before the first backward");
+    return OASR_ESTATE;
+  }
   if (!pr.any) {
     oasr_set_error("oasr_train backward: no parameter is trainable (oasr_set_trainable mask is all zeros)");
     return OASR_ESTATE;
   }
+  // adapters: the adapted weights' gradients of THIS micro-batch go to workspace scratch (projected into the arena at the end)
+  if (!c->lora.empty()) {
+    OASR_CHECK_HIP(hipMemsetAsync(p.lora_dw, 0, (size_t)c->lora_dw_floats * 4, st));
+    r.lora_dw = p.lora_dw;
+  }
+  // the last gradient segment of an adapter context: d lora_B = s * dW . lora_A^T, d lora_A = s * lora_B^T . dW (every dW is final here)
+  auto finish = [&](int seg) -> int {
+    if (!c->lora.empty()) {
+      for (const oasr_ctx::Lora& L : c->lora) {
+        float *ga = c->Gt(L.a), *gb = c->Gt(L.b);
+        if (ga || gb)
+          RC(launch_lora_grad(p.lora_dw + L.dw, c->P(L.a), c->P(L.b), L.out, L.in, c->lora_r, c->lora_s, ga, gb, p.lora_part, st));
+      }
+      RC(r.record(ev, seg++));
+    }
+    if (seg != (int)c->segments.size()) {
+      oasr_set_error("internal: segment count mismatch %d vs %zu", seg, c->segments.size());
+      return OASR_ESTATE;
+    }
+    return OASR_OK;
+  };
   // ---------------- backward: decoder ----------------
   int seg = 0;
   // tied logits: dE += dlogits^T . lnf ; d(lnf) = dlogits . E
@@ -1504,11 +1643,7 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
   // ---------------- backward: encoder ----------------
   if (!pr.enc_any) {  // nothing in the encoder is trainable: neither d(xa) (skipped in the decoder blocks) nor anything below it
     for (int i = 0; i < c->L_enc + 2; ++i) RC(r.record(ev, seg++));  // ln_post, the blocks, the conv stem
-    if (seg != (int)c->segments.size()) {
-      oasr_set_error("internal: segment count mismatch %d vs %zu", seg, c->segments.size());
-      return OASR_ESTATE;
-    }
-    return OASR_OK;
+    return finish(seg);
   }
   const T* xe_last = c->L_enc ? p.enc[c->L_enc - 1].x_out : p.x0;
   if (c->L_dec == 0) OASR_CHECK_HIP(hipMemsetAsync(p.gxa, 0, (size_t)Me * d * sizeof(T), st));
@@ -1590,11 +1725,7 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
     if (c->tr(c->conv1_b)) RC(launch_colsum_accum(p.gu, d, M1, d, c->G(c->conv1_b), st));
   }
   RC(r.record(ev, seg++));
-  if (seg != (int)c->segments.size()) {
-    oasr_set_error("internal: segment count mismatch %d vs %zu", seg, c->segments.size());
-    return OASR_ESTATE;
-  }
-  return OASR_OK;
+  return finish(seg);
 }
 
 template <typename T>
@@ -1752,13 +1883,20 @@ extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params
   OASR_REQUIRE(c && mask && n_params == (int)c->tensors.size(), "oasr_set_trainable: need one byte per tensor (%d)", c ? (int)c->tensors.size() : 0);
   oasr_ctx::Prune pr;
   pr.tr.resize(c->tensors.size());
+  pr.need.resize(c->tensors.size());
   bool all = true, any = false;
   for (int i = 0; i < n_params; ++i) {
     pr.tr[i] = mask[i] ? 1 : 0;
     all = all && pr.tr[i];
     any = any || pr.tr[i];
+    OASR_REQUIRE(!(pr.tr[i] && !c->lora.empty() && c->lora_of[i] >= 0),
+                 "oasr_set_trainable: %s carries a LoRA adapter and must stay frozen (merge the adapters first to train it)", c->tensors[i].name.c_str());
   }
   pr.any = any;
+  for (int i = 0; i < n_params; ++i) {  // an adapted base weight needs its weight gradient while one of its adapters is trainable
+    const int j = c->lora.empty() ? -1 : c->lora_of[i];
+    pr.need[i] = pr.tr[i] || (j >= 0 && (mask[c->tidx(c->lora[j].a)] || mask[c->tidx(c->lora[j].b)]));
+  }
   // maximal stretches of trainable tensors (the arena is the tensors back to back, in table order)
   std::vector<int64_t> runs;
   for (size_t i = 0; i < c->tensors.size(); ++i) {
@@ -1772,9 +1910,9 @@ extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params
   }
   for (size_t k = 0; k < runs.size(); ++k)
     OASR_REQUIRE((runs[k] % 4) == 0, "oasr_set_trainable: trainable runs must start and end on multiples of 4 elements");
-  auto any_in = [&](int64_t lo, int64_t hi) {  // a trainable tensor inside arena range [lo, hi)
+  auto any_in = [&](int64_t lo, int64_t hi) {  // a tensor inside arena range [lo, hi) that needs a gradient
     for (size_t i = 0; i < c->tensors.size(); ++i)
-      if (pr.tr[i] && c->tensors[i].off >= lo && c->tensors[i].off < hi) return true;
+      if (pr.need[i] && c->tensors[i].off >= lo && c->tensors[i].off < hi) return true;
     return false;
   };
   auto blk_range = [&](const BlockP& b, int64_t* lo, int64_t* hi) {  // a block's tensors: mlp.2.weight first, attn_ln.bias last
@@ -1782,7 +1920,7 @@ extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params
     *hi = b.attn_ln_b + c->d;
   };
   const int Ld = c->L_dec, Le = c->L_enc;
-  pr.enc_any = any_in(c->enc_lnp_w, c->tok_emb);
+  pr.enc_any = any_in(c->enc_lnp_w, c->stem_end);
   pr.conv1 = any_in(c->conv1_w, c->conv1_w + 1) || any_in(c->conv1_b, c->conv1_b + 1);
   pr.dec_blk.assign(Ld, 0);
   pr.enc_blk.assign(Le, 0);
@@ -1804,7 +1942,7 @@ extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params
     pr.dec_in[i] = below || (i > 0 && pr.enc_any);
     if (i < Ld) below = below || pr.dec_blk[i];
   }
-  below = any_in(c->conv2_w, c->tok_emb);  // the conv stem
+  below = any_in(c->conv2_w, c->stem_end);  // the conv stem
   for (int i = 0; i <= Le; ++i) {
     pr.enc_in[i] = below;
     if (i < Le) below = below || pr.enc_blk[i];
@@ -1825,6 +1963,7 @@ extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params
   c->runs_dev = dev;
   c->n_runs = (int)(runs.size() / 2);
   c->pr = pr;
+  c->mask_set = true;
   return OASR_OK;
 }
 
@@ -1833,6 +1972,7 @@ extern "C" int oasr_optim_step(oasr_ctx* c, float inv_loss_scale, float max_grad
   RC(check_bound(c, true));
   OASR_REQUIRE(c->m && c->v && stats_out && scratch && step >= 1, "oasr_optim_step: bad args");
   OASR_REQUIRE(c->pr.any, "oasr_optim_step: no parameter is trainable (oasr_set_trainable)");
+  OASR_REQUIRE(c->lora.empty() || c->mask_set, "oasr_optim_step: a context with adapters needs oasr_set_trainable first");
   hipStream_t st = (hipStream_t)stream;
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2 = (float)(1.0 - pow((double)beta2, (double)step));
@@ -1846,6 +1986,7 @@ extern "C" int oasr_optim_step(oasr_ctx* c, float inv_loss_scale, float max_grad
     RC(launch_adamw_runs(c->params, c->grads, c->m, c->v, sh, c->runs_dev, c->n_runs, stats_out, inv_loss_scale, max_grad_norm, lr, beta1,
                          beta2, eps, weight_decay, bc1, bc2, st));
   }
+  RC(refresh_lora(c, st));  // (adapters: the effective compute copies of the stepped masters and adapters)
   return refresh_packed(c, st);
 }
 
@@ -1857,6 +1998,7 @@ extern "C" int oasr_optim_step(oasr_ctx* c, float inv_loss_scale, float max_grad
 // range given GLOBAL statistics.
 extern "C" int oasr_grad_sumsq_range(oasr_ctx* c, int64_t off, int64_t numel, float* stats_out, void* scratch, void* stream) {
   RC(check_bound(c, true));
+  OASR_REQUIRE(c->lora.empty(), "oasr_grad_sumsq_range: ZeRO-1 does not support LoRA adapters");
   OASR_REQUIRE(stats_out && scratch && off >= 0 && numel > 0 && off + numel <= c->numel && (off % 4) == 0 && (numel % 4) == 0,
                "oasr_grad_sumsq_range: bad range [%lld, +%lld) (multiples of 4 inside the arena)", (long long)off, (long long)numel);
   return launch_grad_stats(c->grads + off, numel, (double*)scratch, stats_out, (hipStream_t)stream);
@@ -1868,6 +2010,7 @@ extern "C" int oasr_optim_step_range(oasr_ctx* c, int64_t off, int64_t numel, fl
                                      float inv_loss_scale, float max_grad_norm, float lr, float beta1, float beta2, float eps,
                                      float weight_decay, int64_t step, void* stream) {
   RC(check_bound(c, true));
+  OASR_REQUIRE(c->lora.empty(), "oasr_optim_step_range: ZeRO-1 does not support LoRA adapters");
   OASR_REQUIRE(m_shard && v_shard && stats && step >= 1 && off >= 0 && numel > 0 && off + numel <= c->numel && (off % 4) == 0 &&
                    (numel % 4) == 0,
                "oasr_optim_step_range: bad args");

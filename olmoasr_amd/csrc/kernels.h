@@ -267,6 +267,17 @@ int launch_sample_tokens_ts(const float* logits, long ld, int V, long rows, cons
                             long hist_ld, int n_hist, int ts_begin, int eot, int no_ts, int max_initial_index, float temperature,
                             const float* u, int64_t* tok, float* logprob, hipStream_t s);
 
+// ---- LoRA adapters in weight space (lora.hip) -----------------------------------------------------------------
+// out = W0 + scale * B . A  (W0 [rows][cols] fp32, A [r][cols], B [rows][r]; k sum in ascending order): exactly one of out32 (fp32, may be w0
+// itself) / out16 (bf16, the rounding of launch_cast_f32_bf16)
+int launch_lora_merge(const float* w0, const float* A, const float* B, int rows, int cols, int r, float scale, float* out32, bf16_t* out16,
+                      hipStream_t s);
+// dB += scale * dW . A^T, dA += scale * B^T . dW (dW [rows][cols] fp32 read once; deterministic two-pass reduction through `scratch`;
+// a null dA or dB is skipped)
+size_t lora_grad_scratch_floats(int rows, int cols, int r);
+int launch_lora_grad(const float* dW, const float* A, const float* B, int rows, int cols, int r, float scale, float* dA, float* dB, float* scratch,
+                     hipStream_t s);
+
 // ---- optimizer (flat fp32 arenas) ---------------------------------------------------------------------------
 // stats[0] = sum g^2 (of the *scaled* grads), stats[1] = found_inf flag (nonzero if any non-finite)
 int launch_grad_stats(const float* g, long n, double* partial /*[1024]*/, float* stats /*[2]*/, hipStream_t s);

@@ -214,7 +214,14 @@ class Linear(_ParamModule):
         ``F.linear(x, self.weight.to(x.dtype), self.bias.to(x.dtype))`` (reference model.py:97-101)."""
         from . import ops
         a = _rows_bf16(x)
-        w = ops.cast_bf16(self.weight.detach())
+        if "lora_A" in self._parameters:  # a LoRA-adapted Linear computes with W0 + s * B . A (olmoasr_amd.lora), merged as the engine merges it
+            w = torch.empty(self.out_features, self.in_features, device=a.device, dtype=torch.bfloat16)
+            with torch.cuda.device(a.device):
+                N.check(N.lib().oasr_lora_merge_op(N.ptr(self.weight.detach()), N.ptr(self.lora_A.detach()), N.ptr(self.lora_B.detach()),
+                                                   self.out_features, self.in_features, self.lora_A.shape[0], float(self.lora_scale), 0,
+                                                   N.ptr(w), N.stream_ptr()), "oasr_lora_merge_op")
+        else:
+            w = ops.cast_bf16(self.weight.detach())
         out = torch.empty(a.shape[0], self.out_features, device=a.device, dtype=torch.bfloat16)
         ops.gemm(a, w, a.shape[0], self.out_features, self.in_features, bias=self.bias.detach() if self.has_bias else None, act=act,
                  resid=_rows_bf16(resid) if resid is not None else None, out=out)
@@ -428,24 +435,9 @@ class OLMoASR(nn.Module):
         self.encoder = AudioEncoder(dims.n_mels, dims.n_audio_ctx, dims.n_audio_state, dims.n_audio_head, dims.n_audio_layer)
         self.decoder = TextDecoder(dims.n_vocab, dims.n_text_ctx, dims.n_text_state, dims.n_text_head, dims.n_text_layer,
                                    pad_row=not inference)
-        cd = N.Dims(*[getattr(dims, f[0]) for f in N.Dims._fields_])
         self._n_rows = dims.n_vocab + (0 if inference else 1)
-        self._ctx = lib.oasr_create_ex2(C.byref(cd), self._n_rows, cdt)
-        if not self._ctx:
-            raise N.NativeError("oasr_create: " + lib.oasr_last_error().decode())
-        self._numel = lib.oasr_param_numel(self._ctx)
-        self._table = []
-        for i in range(lib.oasr_param_count(self._ctx)):
-            name = C.create_string_buffer(128)
-            off, numel, ndim = C.c_int64(), C.c_int64(), C.c_int()
-            shape = (C.c_int64 * 4)()
-            N.check(lib.oasr_param_info(self._ctx, i, name, 128, C.byref(off), C.byref(numel), C.byref(ndim), shape), "param_info")
-            self._table.append((name.value.decode(), off.value, numel.value, tuple(shape[j] for j in range(ndim.value))))
-        self._segments = []
-        for i in range(lib.oasr_segment_count(self._ctx)):
-            o, m = C.c_int64(), C.c_int64()
-            N.check(lib.oasr_segment_info(self._ctx, i, C.byref(o), C.byref(m)), "segment_info")
-            self._segments.append((o.value, m.value))
+        self._cdt = cdt
+        self._open_context()
         # ---- flat arenas -----------------------------------------------------------------------------------
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
         flat = torch.empty(self._numel, dtype=torch.float32)
@@ -474,6 +466,64 @@ class OLMoASR(nn.Module):
         self.refresh_shadow()
 
     # ---- arena plumbing --------------------------------------------------------------------------------------
+    def _open_context(self, targets=(), rank=0, scale=0.0):
+        """Creates the engine context -- with LoRA adapters on the tensors ``targets`` (indices into the adapter-free table,
+        ``oasr_create_ex3``) -- and reads its parameter table and gradient segments."""
+        lib = N.lib()
+        cd = N.Dims(*[getattr(self.dims, f[0]) for f in N.Dims._fields_])
+        if targets:
+            idx = (C.c_int32 * len(targets))(*targets)
+            ctx = lib.oasr_create_ex3(C.byref(cd), self._n_rows, self._cdt, idx, len(targets), int(rank), float(scale))
+        else:
+            ctx = lib.oasr_create_ex2(C.byref(cd), self._n_rows, self._cdt)
+        if not ctx:
+            raise N.NativeError("oasr_create: " + lib.oasr_last_error().decode())
+        self._ctx = ctx
+        self._numel = lib.oasr_param_numel(self._ctx)
+        self._table = []
+        for i in range(lib.oasr_param_count(self._ctx)):
+            name = C.create_string_buffer(128)
+            off, numel, ndim = C.c_int64(), C.c_int64(), C.c_int()
+            shape = (C.c_int64 * 4)()
+            N.check(lib.oasr_param_info(self._ctx, i, name, 128, C.byref(off), C.byref(numel), C.byref(ndim), shape), "param_info")
+            self._table.append((name.value.decode(), off.value, numel.value, tuple(shape[j] for j in range(ndim.value))))
+        self._segments = []
+        for i in range(lib.oasr_segment_count(self._ctx)):
+            o, m = C.c_int64(), C.c_int64()
+            N.check(lib.oasr_segment_info(self._ctx, i, C.byref(o), C.byref(m)), "segment_info")
+            self._segments.append((o.value, m.value))
+
+    def _swap_context(self, targets, rank, scale, init_new):
+        """Re-creates the context with another adapter set (``olmoasr_amd.lora``): a new arena in the new table's layout, every tensor
+        both tables hold copied over by name, ``init_new(name, tensor)`` filling the new ones; parameters the new table lacks are removed
+        from their modules.  Gradient arena, optimizer state and data-parallel wrappers are tied to the old layout: they must not exist yet."""
+        if getattr(self, "_opt_state", None) is not None or self._gflat is not None or getattr(self, "_autograd_post_backward", None) is not None:
+            raise N.NativeError("LoRA adapters must be added / merged before the gradient arena, the optimizer state or a data-parallel "
+                                "wrapper exists (they are laid out for the current parameter table): call add_lora / merge_lora first")
+        old_ctx, old = self._ctx, {name: self._flat[off:off + numel] for name, off, numel, _ in self._table}
+        self._open_context(targets, rank, scale)
+        flat = torch.zeros(self._numel, dtype=torch.float32, device=self._flat.device)
+        new_names = set()
+        for name, off, numel, shape in self._table:
+            new_names.add(name)
+            if name in old:
+                flat[off:off + numel].copy_(old[name])
+            else:
+                init_new(name, flat[off:off + numel].view(shape))
+        for name in old:
+            if name not in new_names:
+                mod, attr = self._module_and_attr(name)
+                del mod._parameters[attr]
+        self._flat = flat
+        self._shadow = torch.zeros(N.lib().oasr_shadow_bytes(self._ctx), dtype=torch.uint8, device=flat.device)
+        self._workspace = None
+        self._trainable_mask = None
+        self._param_version = None
+        self._attach_views()
+        self._bind()
+        N.lib().oasr_destroy(old_ctx)
+        self.refresh_shadow()
+
     def _module_and_attr(self, name):
         parts = name.split(".")
         mod = self

@@ -56,7 +56,10 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     zero_stage=0,  # zero_stage 1: AdamW moments sharded over the ranks (olmoasr_amd/zero.py; the reference's FSDP script's role)
     span_backward=True,  # decoder backward over the supervised span only (oasr_train_fwd_bwd_span; same loss / gradients, forward over all 448)
     span_forward=True,  # the decoder's forward leaves the padded positions out too (their logits are read by nothing; -4.7 % more); False = forward over all 448
-    freeze_encoder=False)  # fine-tuning: encoder.* get requires_grad=False (no gradient, no update; the backward skips the encoder)
+    freeze_encoder=False,  # fine-tuning: encoder.* get requires_grad=False (no gradient, no update; the backward skips the encoder)
+    # LoRA fine-tuning (olmoasr_amd/lora.py): rank-r adapters with scale alpha / r on the modules --lora_targets selects (comma-separated
+    # fnmatch patterns), every base parameter frozen; 0 = off.  With --freeze_encoder the encoder's adapters stay frozen as well.
+    lora_rank=0, lora_alpha=32, lora_targets="*.attn.query,*.attn.value")
 
 
 class Args(dict):
@@ -109,6 +112,11 @@ def parse_args(argv=None):
                          "(train_timestamps.py:2128 default) has no native counterpart -- pass --precision bfloat16")
     if args.precision not in ("bfloat16", "float32"):
         raise SystemExit(f"--precision must be bfloat16 | float32 | float16, got {args.precision!r}")
+    if not isinstance(args.lora_rank, int) or args.lora_rank < 0:
+        raise SystemExit(f"--lora_rank must be a non-negative integer (0 = no adapters), got {args.lora_rank!r}")
+    if isinstance(args.lora_targets, str):
+        args.lora_targets = tuple(t.strip() for t in args.lora_targets.split(",") if t.strip())
+    args.lora_targets = tuple(args.lora_targets)
     return args
 
 
@@ -358,6 +366,9 @@ def main(argv=None):
     betas = tuple(args.betas)
     dims = VARIANT_TO_DIMS[args.model_variant]
     net = OLMoASR(dims, device=dev, seed=args.seed, compute_dtype=args.precision)
+    if args.lora_rank:
+        from olmoasr_amd import lora
+        lora.add_lora(net, r=args.lora_rank, alpha=args.lora_alpha, target_modules=args.lora_targets, seed=args.seed)
     if args.freeze_encoder:
         net.encoder.requires_grad_(False)
     ddp.broadcast_parameters(net.flat_params)  # DDP ctor _sync_module_states
