@@ -767,14 +767,23 @@ class OLMoASR(nn.Module):
 
     # ---- cached decoding (the reference's install_kv_cache_hooks + one decoder step per token) ------------------------
     @torch.no_grad()
-    def kv_cache_begin(self, audio_features: Tensor):
-        """Allocates the KV cache for this batch of windows and fills the cross-attention K/V of every decoder layer."""
+    def kv_cache_begin(self, audio_features: Tensor, cache: Optional[Tensor] = None, ws: Optional[Tensor] = None):
+        """Allocates the KV cache for this batch of windows and fills the cross-attention K/V of every decoder layer.
+        ``cache`` / ``ws``: caller-owned uint8 buffers of exactly oasr_kv_cache_bytes / oasr_decode_step_workspace_bytes bytes to use
+        instead (whatever they hold: decode_begin initialises what the step reads)."""
         N.require_gpu(audio_features, "audio_features")
         xa = audio_features.to(self._act_dtype).contiguous()
         B = xa.shape[0]
         lib = N.lib()
-        cache = torch.empty(lib.oasr_kv_cache_bytes(self._ctx, B), dtype=torch.uint8, device=xa.device)
-        ws = torch.empty(lib.oasr_decode_step_workspace_bytes(self._ctx, B), dtype=torch.uint8, device=xa.device)
+        bufs = {}
+        for name, buf, nbytes in (("cache", cache, lib.oasr_kv_cache_bytes(self._ctx, B)),
+                                  ("ws", ws, lib.oasr_decode_step_workspace_bytes(self._ctx, B))):
+            if buf is None:
+                buf = torch.empty(nbytes, dtype=torch.uint8, device=xa.device)
+            elif not (buf.dtype == torch.uint8 and buf.is_contiguous() and buf.numel() == nbytes and buf.device == xa.device):
+                raise ValueError(f"kv_cache_begin: {name} must be a contiguous uint8 tensor of {nbytes} bytes on {xa.device}")
+            bufs[name] = buf
+        cache, ws = bufs["cache"], bufs["ws"]
         with torch.cuda.device(xa.device):
             N.check(lib.oasr_decode_begin(self._ctx, N.ptr(xa), B, N.ptr(cache), N.stream_ptr()), "oasr_decode_begin")
         return {"cache": cache, "ws": ws, "B": B, "pos": 0}

@@ -246,3 +246,94 @@ def test_default_engine_for_one_sequence_is_the_one_launch_engine(tiny_case, wid
     two = net.kv_cache_begin(xa.repeat(2, 1, 1))  # two sequences: the multi-launch kernels by default (they spread over the chip)
     net.kv_cache_step(two, torch.tensor([50257, 50257], device=DEV))
     assert net.kv_cache_check(two) is True and int(_tail(two)[0]) == 0 and int(_tail(two)[4]) == 0
+
+
+def _window(net, xa, toks, mode, fill=None):
+    """One decode window on engine ``mode``; ``fill``: the KV cache and the step workspace are test-owned buffers holding that
+    16-bit pattern everywhere before decode_begin (which initialises the control tail, as the ABI says) -- None: the model's own."""
+    from olmoasr_amd import _native as N
+    lib = N.lib()
+    B = xa.shape[0]
+    bufs = {}
+    if fill is not None:
+        for name, nbytes in (("cache", lib.oasr_kv_cache_bytes(net._ctx, B)), ("ws", lib.oasr_decode_step_workspace_bytes(net._ctx, B))):
+            assert nbytes % 2 == 0
+            t = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+            t.view(torch.int16).fill_(fill)
+            bufs[name] = t
+    lib.oasr_decode_set_ln_fold(mode)
+    try:
+        st = net.kv_cache_begin(xa, **bufs)
+        out = [net.kv_cache_step(st, toks[:, p]) for p in range(toks.shape[1])]
+        assert net.kv_cache_check(st) is True
+        return torch.stack(out, 1)
+    finally:
+        lib.oasr_decode_set_ln_fold(-1)
+
+
+BF16_NAN, BF16_MAX = 0x7FC0, 0x7F7F
+
+
+@pytest.mark.parametrize("B", [1, 2, 5])
+def test_step_engines_ignore_what_the_cache_and_workspace_held(tiny_case, B):
+    """Self-attention rows past ``pos`` and the step workspace are whatever memory the allocator hands back.  With every byte of the
+    cache and the workspace set to bf16 NaN, then to the largest finite bf16, every engine's logits are bit-identical to the same
+    window on zero-filled buffers: a masked p = 0 never meets an unwritten row (0 * NaN = NaN), no clamp reads past ``pos``."""
+    from olmoasr_amd.model import OLMoASR
+    from oracle import model_oracle as mo
+    dims = mo.Dims(80, 1500, 384, 6, 1, 51864, 448, 384, 6, 2)
+    net = OLMoASR(_dims(dims), device=DEV, seed=21, inference=True)
+    mel = tiny_case["mel"].to(DEV)
+    mel = mel.repeat((B + 1) // 2, 1, 1)[:B] * torch.linspace(1.0, 0.8, B, device=DEV)[:, None, None]
+    xa = net.embed_audio(mel)
+    toks = torch.randint(0, 50000, (B, 7), generator=torch.Generator().manual_seed(B)).to(DEV)
+    toks[:, 0] = 50257
+    for mode in (0, 1, 2, 3, 4, 5, -1):
+        clean = _window(net, xa, toks, mode, fill=0)
+        assert torch.isfinite(clean).all(), mode
+        for fill in (BF16_NAN, BF16_MAX):
+            got = _window(net, xa, toks, mode, fill)
+            assert torch.equal(got, clean), (mode, hex(fill), float((got - clean).abs().nan_to_num(float("inf")).max()))
+
+
+@pytest.mark.parametrize("sharpen", [8, 32])
+def test_step_engines_with_one_hot_cross_attention(tiny_case, sharpen):
+    """Trained alignment heads are nearly one-hot over the 1500 frames; random-init weights never are.  With the cross-attention
+    query weights of one layer scaled x8 / x32 (scores x8 / x32; the largest weight per head and query has a median of 0.38 / over
+    0.9 over the 1500 frames), the engines keep their contract -- 0-4 bit-identical, the chip-wide engine (5)
+    within its envelope -- and track the fp32 validation context with the same weights."""
+    from olmoasr_amd.model import OLMoASR
+    from oracle import model_oracle as mo
+    dims = mo.Dims(80, 1500, 384, 6, 1, 51864, 448, 384, 6, 2)
+    sd = mo.init_state_dict(dims, seed=3)
+    for n in ("decoder.blocks.1.cross_attn.query.weight", "decoder.blocks.1.cross_attn.query.bias"):
+        sd[n] = sd[n] * sharpen
+    net = OLMoASR(_dims(dims), device=DEV, seed=0)  # (the training layout: init_state_dict's embedding has the extra pad row)
+    net.load_state_dict(sd)
+    net32 = OLMoASR(_dims(dims), device=DEV, seed=0, compute_dtype="float32")
+    net32.load_state_dict(sd)
+    mel = tiny_case["mel"][:1].to(DEV)
+    toks = torch.randint(0, 50000, (1, 9), generator=torch.Generator().manual_seed(7)).to(DEV)
+    toks[:, 0] = 50257
+    xa = net.embed_audio(mel)
+    multi = _window(net, xa, toks, 0)
+    assert torch.isfinite(multi).all()
+    for mode in (1, 2, 3, 4):
+        assert torch.equal(_window(net, xa, toks, mode), multi), mode
+    scale = float(multi.abs().max())
+    env = 0.08 + 0.02 * scale
+    wide = _window(net, xa, toks, 5)
+    assert torch.isfinite(wide).all() and float((wide - multi).abs().max()) < env, float((wide - multi).abs().max())
+    ref = _window(net32, net32.embed_audio(mel), toks, -1)
+    err = float((multi - ref).abs().max())
+    # the sharpened layer's heads: largest softmax weight over the 1500 frames, per head and query
+    from olmoasr_amd import timing
+    peak = torch.softmax(timing.cross_attention_scores(net, toks[0], xa, [1])[1].float(), -1).max(-1).values
+    print(f"one-hot cross-attention x{sharpen}: max weight per head and query median {float(peak.median()):.3g}, min {float(peak.min()):.3g}; "
+          f"max |logit| {scale:.3g}, bf16 engines vs fp32 context {err:.3g}, chip-wide vs multi-launch {float((wide - multi).abs().max()):.3g}")
+    assert float(peak.median()) > (0.3 if sharpen == 8 else 0.9)
+    # against fp32: bf16 rounding of q and k moves a score of |s| nats by up to ~|s| 2^-7, and at x32 the sharpened scores reach tens of
+    # nats -- the weights of a near-one-hot head then move by tens of percent; the envelope doubles there (measured 0.10 at x8, 0.28 at x32)
+    lim = env if sharpen == 8 else 2 * env
+    assert err < lim, err
+    assert float((wide - ref).abs().max()) < lim
