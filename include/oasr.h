@@ -35,7 +35,7 @@ typedef struct oasr_dims {
 const char* oasr_last_error(void);
 /* ABI version: 100 * major + minor.  Structs passed by pointer (oasr_attn_args, oasr_gemm_args) only grow at the end and only with a
  * major bump; olmoasr_amd/_native.py refuses to drive a library whose version differs from OASR_ABI_VERSION. */
-#define OASR_ABI_VERSION 213
+#define OASR_ABI_VERSION 214
 int oasr_version(void);
 
 /* ---- log-mel front end: whisper.audio.log_mel_spectrogram as called at train_timestamps.py:196,214 and
@@ -108,7 +108,9 @@ int oasr_refresh_shadow(oasr_ctx*, void* stream); /* after params changed outsid
 
 #define OASR_MODE_INFER 0
 #define OASR_MODE_TRAIN 1
-size_t oasr_workspace_bytes(const oasr_ctx*, int B, int S, int mode);
+#define OASR_MODE_TRAIN_ENC 2 /* ABI 214: the workspace of the staged encoder entries (oasr_train_encode / _encode_bwd; S is not used) */
+#define OASR_MODE_TRAIN_DEC 3 /* ABI 214: the workspace of the staged decoder entries (oasr_train_decode / _decode_bwd / oasr_train_dec_fwd_bwd) */
+size_t oasr_workspace_bytes(const oasr_ctx*, int B, int S, int mode); /* 0 for an unknown mode */
 
 /* OLMoASR.forward(mel, tokens, padding_mask) (olmoasr/model.py:856-887).  mel f32 [B,80,2*n_audio_ctx]; tokens i64 [B,S];
  * text_len i32 [B] = first padded key column of the reference's column-only padding mask (train_timestamps.py:314-315),
@@ -191,6 +193,34 @@ int oasr_train_fwd(oasr_ctx*, const float* mel, const int64_t* tokens, const int
 int oasr_train_bwd(oasr_ctx*, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void** seg_events,
                    void* workspace, size_t workspace_bytes, void* stream);
 int oasr_zero_grad(oasr_ctx*, void* stream);
+
+/* ABI 214: the same training step in two stages, for torch.autograd through model.encoder(mel) and model.decoder(tokens, xa) (the reference's
+ * AudioEncoder / TextDecoder as ordinary modules).  Each stage has a workspace of its own (OASR_MODE_TRAIN_ENC / _DEC bytes) that holds one
+ * forward's saved activations until that stage's backward: the pair shares B (and S, tokens, text_len), and nothing else may use that
+ * workspace in between.  The forwards are the fused training forward's (oasr_train_fwd: training-mode GELU epilogue), cut at xa, so
+ * encode -> decode gives bit-identical logits to it.  The backwards are the two halves of its backward: parameter gradients are ACCUMULATED
+ * into the bound arena under the trainability mask (a stage's backward writes its own stage's tensors and, with adapters, projects its own
+ * stage's adapters only).  An input gradient that is asked for is computed even through frozen blocks, and then an all-zero mask is accepted
+ * (saliency on a frozen model); otherwise a mask with no trainable tensor is refused (OASR_ESTATE).
+ *   train_encode:     mel f32 [B, n_mels, 2*n_audio_ctx] -> xa_out [B, n_audio_ctx, d] in the compute dtype.
+ *   train_encode_bwd: dxa (compute dtype, as xa) -> encoder gradients; dmel_out: NULL, or f32 [B, n_mels, 2*n_audio_ctx] = d(loss)/d(mel)
+ *                     (the bf16 engine's cast of mel counts as the identity, as autocast's does).
+ *   train_decode:     tokens i64 [B, S], xa (compute dtype, copied into the workspace), text_len i32 [B] -> logits_out f32 [B, S, rows].
+ *   train_decode_bwd: dlogits f32 [B, S, rows] -> decoder gradients; dxa_out: NULL, or d(loss)/d(xa) [B, n_audio_ctx, d] in the compute
+ *                     dtype, summed over the decoder layers from the top one down. */
+int oasr_train_encode(oasr_ctx*, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream);
+int oasr_train_encode_bwd(oasr_ctx*, const void* dxa, int B, float* dmel_out, void* workspace, size_t workspace_bytes, void* stream);
+int oasr_train_decode(oasr_ctx*, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S, float* logits_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int oasr_train_decode_bwd(oasr_ctx*, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void* dxa_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* ABI 214: the fused micro-step of the decoder alone, from a given encoder output xa (compute dtype) -- a frozen encoder's features
+ * computed once and reused.  span_host: NULL (= oasr_train_fwd_bwd_s over S positions) or the host [B] array of oasr_train_fwd_bwd_span
+ * (then S = n_text_ctx and span_forward = OASR_SPAN_FORWARD_*).  Loss, events and gradients as those entries; every segment event is
+ * recorded, the encoder's at once.  OASR_ESTATE if an encoder tensor (or an encoder adapter) is trainable.  Workspace: OASR_MODE_TRAIN_DEC. */
+int oasr_train_dec_fwd_bwd(oasr_ctx*, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                           const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
+                           int accumulate_loss, void** seg_events, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Frozen parameters (torch's requires_grad == False): mask holds one byte per tensor in oasr_param_info order, nonzero = trainable;
  * the default is all ones.  From then on the backward entries (oasr_train_fwd_bwd, _s, _span, oasr_train_bwd) neither launch nor

@@ -44,8 +44,9 @@ class AttnArgs(C.Structure):
                 ("q_rows", C.c_void_p), ("k_rows", C.c_void_p), ("q_span", C.c_void_p)]
 
 
-ABI_VERSION = 213  # include/oasr.h: OASR_ABI_VERSION (213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
+ABI_VERSION = 214  # include/oasr.h: OASR_ABI_VERSION (214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
+MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
 ROWTAB = 16        # include/oasr.h: OASR_ROWTAB (entries per sample of a chunk-row table)
 LORA_MAX_RANK = 64  # include/oasr.h: OASR_LORA_MAX_RANK
 
@@ -96,6 +97,11 @@ def _declare(lib):
         "oasr_train_fwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_train_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_zero_grad": (i32, [vp, vp]),
+        "oasr_train_encode": (i32, [vp, vp, i32, vp, vp, sz, vp]),
+        "oasr_train_encode_bwd": (i32, [vp, vp, i32, vp, vp, sz, vp]),
+        "oasr_train_decode": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+        "oasr_train_decode_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+        "oasr_train_dec_fwd_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, vp, vp, sz, vp]),
         "oasr_set_trainable": (i32, [vp, vp, i32]),
         "oasr_optim_step": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, i64, vp, vp, vp]),
         "oasr_grad_sumsq_range": (i32, [vp, i64, i64, vp, vp, vp]),

@@ -89,6 +89,7 @@ struct oasr_ctx {
     bool enc_any = true;                     // some encoder tensor (ln_post, blocks, conv stem): the encoder backward and d(xa) run
     std::vector<uint8_t> dec_blk, enc_blk;   // [L]: the block holds a trainable tensor
     std::vector<uint8_t> dec_in, enc_in;     // [L + 1]: the data gradient out of block i (into the residual stream below it) is needed
+    std::vector<uint8_t> dec_below;          // [L + 1]: dec_in without d(xa): a tensor below block i (a lower block, the embeddings) is trainable
     bool conv1 = true;                       // conv1 weight or bias: the conv2 data gradient and the col2im run
   } pr;
   int64_t* runs_dev = nullptr;  // [2 * n_runs] (offset, numel) of the maximal trainable stretches of the arena (device)
@@ -226,6 +227,9 @@ struct Arena {
     if (_rc) return _rc; \
   } while (0)
 
+// Plans of the training step (Engine::make_plan): the fused step's, or one stage's of the staged autograd entries
+enum { STAGE_ALL = 0, STAGE_ENC = 1, STAGE_DEC = 2 };
+
 // Everything below is written once for both compute dtypes: T = bf16_t (production) or float (validation).
 template <typename T>
 struct Engine {
@@ -278,14 +282,22 @@ static void plan_attn(Arena& A, AttnSave& s, long M, long Mkv, int d, int B, int
 
 // In inference mode the per-layer buffers are shared between layers (allocated once); in training each layer
 // gets its own slots because the backward needs them.
-static void make_plan(const oasr_ctx* c, Arena& A, Plan& p, int B, int S, bool train) {
+// stage (training plans only): STAGE_ALL = the fused step's plan (encoder + decoder, backward temporaries for the larger of the two);
+// STAGE_ENC / STAGE_DEC = the plan of one stage of the staged autograd entries (oasr_train_encode* / oasr_train_decode*): the encoder's
+// saved activations and encoder-sized backward temporaries (+ the d(mel) columns), or the decoder's own copy of xa, its saved activations
+// and temporaries sized by the decoder rows (+ d(xa)).  A stage plan has no slot for the other stage (null pointers).
+static void make_plan(const oasr_ctx* c, Arena& A, Plan& p, int B, int S, bool train, int stage = STAGE_ALL) {
   const int d = c->d;
   const long Me = (long)B * c->Te, M1 = (long)B * c->T1, Md = (long)B * S;
-  p.mel_tm = A.template act<T>(M1 * c->dims.n_mels + 2 * 256) + 256;  // zeroed guard rows on both sides (conv1 weight gradient windows)
-  p.u1 = A.template act<T>(M1 * d);
-  p.h1 = A.template act<T>(M1 * d + d) + d;  // one zeroed time row in front: the conv2 weight gradient reads h1 as overlapping windows from h1 - d
-  p.u2 = A.template act<T>(Me * d);
-  p.x0 = A.template act<T>(Me * d);
+  const bool enc = stage != STAGE_DEC, dec = stage != STAGE_ENC;
+  p = Plan();
+  if (enc) {
+    p.mel_tm = A.template act<T>(M1 * c->dims.n_mels + 2 * 256) + 256;  // zeroed guard rows on both sides (conv1 weight gradient windows)
+    p.u1 = A.template act<T>(M1 * d);
+    p.h1 = A.template act<T>(M1 * d + d) + d;  // one zeroed time row in front: the conv2 weight gradient reads h1 as overlapping windows from h1 - d
+    p.u2 = A.template act<T>(Me * d);
+    p.x0 = A.template act<T>(Me * d);
+  }
   auto plan_block = [&](BlockSave& s, long M, long Tq, bool cross) {
     plan_attn(A, s.sa, M, 0, d, B, c->H, Tq, false, train);
     s.x_mid = A.template act<T>(M * d);
@@ -304,7 +316,8 @@ static void make_plan(const oasr_ctx* c, Arena& A, Plan& p, int B, int S, bool t
   };
   p.enc.resize(c->L_enc);
   p.dec.resize(c->L_dec);
-  if (train) {
+  if (!enc) {
+  } else if (train) {
     for (auto& s : p.enc) plan_block(s, Me, c->Te, false);
   } else {
     BlockSave s0, s1;
@@ -313,58 +326,70 @@ static void make_plan(const oasr_ctx* c, Arena& A, Plan& p, int B, int S, bool t
     s1.x_out = A.template act<T>(Me * d);  // ping-pong the residual stream
     for (int i = 0; i < c->L_enc; ++i) p.enc[i] = (i & 1) ? s1 : s0;
   }
-  p.xa = A.template act<T>(Me * d);
-  p.mean_p = A.f32(Me);
-  p.rstd_p = A.f32(Me);
-  p.dx0 = A.template act<T>(Md * d);
-  if (train) {
-    for (auto& s : p.dec) plan_block(s, Md, S, true);
-  } else {
-    BlockSave s0, s1;
-    plan_block(s0, Md, S, true);
-    s1 = s0;
-    s1.x_out = A.template act<T>(Md * d);
-    for (int i = 0; i < c->L_dec; ++i) p.dec[i] = (i & 1) ? s1 : s0;
+  p.xa = A.template act<T>(Me * d);  // (decoder stage: its own copy of the caller's xa)
+  if (enc) {
+    p.mean_p = A.f32(Me);
+    p.rstd_p = A.f32(Me);
   }
-  p.lnf = A.template act<T>(Md * d);
-  p.mean_f = A.f32(Md);
-  p.rstd_f = A.f32(Md);
-  p.logits = A.template act<T>(Md * c->Vp);
-  p.row_loss = A.f32(Md);
-  p.n_valid = (int32_t*)A.raw(256);
-  p.rows = p.span_dev = nullptr;
-  p.targets_phys = nullptr;
-  p.lora_dw = p.lora_part = nullptr;
+  if (dec) {
+    p.dx0 = A.template act<T>(Md * d);
+    if (train) {
+      for (auto& s : p.dec) plan_block(s, Md, S, true);
+    } else {
+      BlockSave s0, s1;
+      plan_block(s0, Md, S, true);
+      s1 = s0;
+      s1.x_out = A.template act<T>(Md * d);
+      for (int i = 0; i < c->L_dec; ++i) p.dec[i] = (i & 1) ? s1 : s0;
+    }
+    p.lnf = A.template act<T>(Md * d);
+    p.mean_f = A.f32(Md);
+    p.rstd_f = A.f32(Md);
+    p.logits = A.template act<T>(Md * c->Vp);
+    p.row_loss = A.f32(Md);
+    p.n_valid = (int32_t*)A.raw(256);
+  }
   if (train) {
-    p.rows = (int32_t*)A.raw((size_t)B * OASR_ROWTAB * 4);
-    p.span_dev = (int32_t*)A.raw((size_t)B * 4);
-    p.targets_phys = (int64_t*)A.raw((size_t)Md * 8);
-    const long Mmax = Me > Md ? Me : Md;
+    if (dec) {
+      p.rows = (int32_t*)A.raw((size_t)B * OASR_ROWTAB * 4);
+      p.span_dev = (int32_t*)A.raw((size_t)B * 4);
+      p.targets_phys = (int64_t*)A.raw((size_t)Md * 8);
+    }
+    const long Mmax = stage == STAGE_ENC ? Me : stage == STAGE_DEC ? Md : (Me > Md ? Me : Md);
     p.ga = A.template act<T>(Mmax * d);
     p.gb = A.template act<T>(Mmax * d);
     p.gc = A.template act<T>(Mmax * d);
     p.gln = A.template act<T>(Mmax * d);
     p.gqkv = A.template act<T>(Mmax * 3 * d);
     p.go = A.template act<T>(Mmax * d);
-    p.gu = A.template act<T>(M1 * d > Mmax * 4 * d ? M1 * d : Mmax * 4 * d);  // also holds dpre1 [B*3000, d]
-    p.gxa = A.template act<T>(Me * d);
-    p.gkv = A.template act<T>(Me * 2 * d);
-    p.gq = A.template act<T>(Md * d);
-    p.gA2 = A.template act<T>(Me * 3 * d);
-    p.delta = A.f32((long)B * c->H * c->Te);
-    p.cs_scratch = A.f32(attn_colsum_scratch_floats(B, c->H, c->Te, c->Te));  // (the largest of the three attention shapes)
-    p.qtile_flags = (int32_t*)A.f32((size_t)B * c->H * ((S + 63) / 64) + 16);
+    p.gu = A.template act<T>(enc && M1 * d > Mmax * 4 * d ? M1 * d : Mmax * 4 * d);  // also holds dpre1 [B*3000, d]
+    if (dec) {
+      p.gxa = A.template act<T>(Me * d);
+      p.gkv = A.template act<T>(Me * 2 * d);
+      p.gq = A.template act<T>(Md * d);
+    }
+    if (enc)  // (encoder stage: also the d(mel) columns [B*3000, 256] of the conv1 data gradient)
+      p.gA2 = A.template act<T>(stage == STAGE_ENC && M1 * 256 > Me * 3 * d ? M1 * 256 : Me * 3 * d);
+    p.delta = A.f32((long)B * c->H * (stage == STAGE_DEC ? S : c->Te));
+    // (the largest of the three attention shapes)
+    p.cs_scratch = A.f32(stage == STAGE_DEC ? attn_colsum_scratch_floats(B, c->H, S, S > c->Te ? S : c->Te)
+                                            : attn_colsum_scratch_floats(B, c->H, c->Te, c->Te));
+    if (dec) p.qtile_flags = (int32_t*)A.f32((size_t)B * c->H * ((S + 63) / 64) + 16);
     p.gemm_cs_scratch = A.f32((size_t)2 * cdiv(Mmax, 256) * 4 * d + 64);
-    p.tmp_w1p = A.f32((long)d * 256);
-    p.tmp_w2p = A.f32((long)d * 3 * d);
+    if (enc) {
+      p.tmp_w1p = A.f32((long)d * 256);
+      p.tmp_w2p = A.f32((long)d * 3 * d);
+    }
     if (!c->lora.empty()) {
       p.lora_dw = A.f32(c->lora_dw_floats);
       p.lora_part = A.f32(c->lora_part_floats);
     }
     // the residual stream entering each block (block_fwd records the same pointers): a plan re-made for a backward-only call
     // (oasr_train_bwd) must be complete without having run the forward
-    for (int i = 0; i < c->L_enc; ++i) p.enc[i].x_in = i ? p.enc[i - 1].x_out : p.x0;
-    for (int i = 0; i < c->L_dec; ++i) p.dec[i].x_in = i ? p.dec[i - 1].x_out : p.dx0;
+    if (enc)
+      for (int i = 0; i < c->L_enc; ++i) p.enc[i].x_in = i ? p.enc[i - 1].x_out : p.x0;
+    if (dec)
+      for (int i = 0; i < c->L_dec; ++i) p.dec[i].x_in = i ? p.dec[i - 1].x_out : p.dx0;
   }
 }
 
@@ -1171,14 +1196,16 @@ extern "C" int oasr_lora_merge(oasr_ctx* c, void* stream) {
 }
 
 extern "C" size_t oasr_workspace_bytes(const oasr_ctx* c, int B, int S, int mode) {
-  if (!c || B <= 0 || S <= 0) return 0;
+  if (!c || B <= 0 || S <= 0 || mode < OASR_MODE_INFER || mode > OASR_MODE_TRAIN_DEC) return 0;
+  const bool train = mode != OASR_MODE_INFER;
+  const int stage = mode == OASR_MODE_TRAIN_ENC ? STAGE_ENC : mode == OASR_MODE_TRAIN_DEC ? STAGE_DEC : STAGE_ALL;
   Arena A(nullptr, 0);
   if (c->f32) {
     Engine<float>::Plan p;
-    Engine<float>::make_plan(c, A, p, B, S, mode == OASR_MODE_TRAIN);
+    Engine<float>::make_plan(c, A, p, B, S, train, stage);
   } else {
     Engine<bf16_t>::Plan p;
-    Engine<bf16_t>::make_plan(c, A, p, B, S, mode == OASR_MODE_TRAIN);
+    Engine<bf16_t>::make_plan(c, A, p, B, S, train, stage);
   }
   return A.cur + 4096;
 }
@@ -1553,48 +1580,21 @@ extern "C" int oasr_train_fwd_bwd(oasr_ctx* c, const float* mel, const int64_t* 
 // the reference spends their share of the decoder on exact zeros (train_timestamps.py:318-329 pads every sample to 448).
 // The backward half of a training micro-step: p.logits holds d(loss)/d(logits) (bf16 engine: bf16 [Md, Vp]) on entry -- written in
 // place by the fused cross-entropy (oasr_train_fwd_bwd*) or converted from the caller's fp32 tensor (oasr_train_bwd, the
-// torch.autograd path) -- and every saved activation of the forward is still in the workspace.
+// torch.autograd path) -- and every saved activation of the forward is still in the workspace.  It runs in two halves (train_backward
+// below calls both).  backward_decoder starts from p.logits and ends at the token / positional embeddings; with `xa_grad` it
+// leaves d(xa) in p.gxa.  backward_encoder starts from d(xa) = `gxa` and ends at the conv stem; with `dmel` it also writes d(mel) (fp32
+// [B, n_mels, T1]: the conv1 data gradient, which no parameter needs).  A requested input gradient forces the data gradient it needs through
+// every block of its stage, whatever the trainability mask prunes (the staged autograd entries, oasr_train_encode_bwd / _decode_bwd); the
+// fused step asks for d(xa) exactly when an encoder tensor needs a gradient, and never for d(mel).
 template <typename T>
-static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename Engine<T>::Plan& p, const int64_t* tokens, int B, int S, void** ev) {
+static int backward_decoder(oasr_ctx* c, typename Engine<T>::Runner& r, typename Engine<T>::Plan& p, const int64_t* tokens, int B, int S,
+                            void** ev, int& seg, bool xa_grad) {
   const int d = c->d;
   // Md: the decoder's token rows the backward runs over -- all B*S, or (supervised-span step) the leading rows that hold every
   // position able to carry gradient; the rows behind them are never read or written by the backward
-  const long Md = r.dec_rows_bwd ? r.dec_rows_bwd : (long)B * S, Me = (long)B * c->Te, M1 = (long)B * c->T1;
+  const long Md = r.dec_rows_bwd ? r.dec_rows_bwd : (long)B * S;
   hipStream_t st = r.st;
-  // Frozen parameters (oasr_set_trainable, oasr_ctx::Prune): launches that only serve frozen tensors are left out, the data gradient
-  // stops where nothing earlier in the forward is trainable.  Every segment event is still recorded (DDP buckets wait on them).
   const oasr_ctx::Prune& pr = c->pr;
-  if (!c->lora.empty() && !c->mask_set) {
-    oasr_set_error("oasr_train backward: a context with adapters needs oasr_set_trainable before the first backward");
-    return OASR_ESTATE;
-  }
-  if (!pr.any) {
-    oasr_set_error("oasr_train backward: no parameter is trainable (oasr_set_trainable mask is all zeros)");
-    return OASR_ESTATE;
-  }
-  // adapters: the adapted weights' gradients of THIS micro-batch go to workspace scratch (projected into the arena at the end)
-  if (!c->lora.empty()) {
-    OASR_CHECK_HIP(hipMemsetAsync(p.lora_dw, 0, (size_t)c->lora_dw_floats * 4, st));
-    r.lora_dw = p.lora_dw;
-  }
-  // the last gradient segment of an adapter context: d lora_B = s * dW . lora_A^T, d lora_A = s * lora_B^T . dW (every dW is final here)
-  auto finish = [&](int seg) -> int {
-    if (!c->lora.empty()) {
-      for (const oasr_ctx::Lora& L : c->lora) {
-        float *ga = c->Gt(L.a), *gb = c->Gt(L.b);
-        if (ga || gb)
-          RC(launch_lora_grad(p.lora_dw + L.dw, c->P(L.a), c->P(L.b), L.out, L.in, c->lora_r, c->lora_s, ga, gb, p.lora_part, st));
-      }
-      RC(r.record(ev, seg++));
-    }
-    if (seg != (int)c->segments.size()) {
-      oasr_set_error("internal: segment count mismatch %d vs %zu", seg, c->segments.size());
-      return OASR_ESTATE;
-    }
-    return OASR_OK;
-  };
-  // ---------------- backward: decoder ----------------
-  int seg = 0;
   // tied logits: dE += dlogits^T . lnf ; d(lnf) = dlogits . E
   // (V = n_vocab + 1 is odd: the direct-to-LDS kernel wants a multiple of 8 rows, so the pad class gets its own 1-row GEMM)
   if (c->tr(c->tok_emb)) {
@@ -1618,12 +1618,14 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
     *b = o[1];
   };
   for (int i = c->L_dec - 1; i >= 0; --i) {
-    if (pr.all || pr.dec_blk[i] || pr.dec_in[i] || pr.enc_any) {
+    // the gradient of block i's input: for a trainable tensor below it, or for a lower block's d(xa)
+    const bool need_in = pr.all || pr.dec_below[i] || (i > 0 && xa_grad);
+    if (pr.all || pr.dec_blk[i] || need_in || xa_grad) {
       T *sa, *sb;
       others(dx, &sa, &sb);
       const T* dx_in = nullptr;
       RC(r.block_bwd(c->dec[i], p.dec[i], p, dx, sa, sb, Md, S, true, i == c->L_dec - 1, i > 0 ? c->Gt(c->dec[i - 1].b2) : nullptr, &dx_in,
-                     pr.all || pr.dec_in[i], pr.all || pr.enc_any));
+                     need_in, xa_grad));
       dx = dx_in;
     }
     // the block's event says "every gradient of this block is complete" (the DDP reducer sends the bucket on it): that includes the
@@ -1639,33 +1641,50 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
     RC(launch_embedding_bwd(tokens, dx, c->Gt(c->tok_emb), c->Gt(c->dec_pos), B, S, d, PAD_ID, c->V, st, r.dec_rows, r.dec_span));
   RC(r.record(ev, seg++));  // decoder.positional_embedding
   RC(r.record(ev, seg++));  // token embedding (arena tail)
+  if (xa_grad && c->L_dec == 0) OASR_CHECK_HIP(hipMemsetAsync(p.gxa, 0, (size_t)B * c->Te * d * sizeof(T), st));
+  return OASR_OK;
+}
 
-  // ---------------- backward: encoder ----------------
-  if (!pr.enc_any) {  // nothing in the encoder is trainable: neither d(xa) (skipped in the decoder blocks) nor anything below it
+template <typename T>
+static int backward_encoder(oasr_ctx* c, typename Engine<T>::Runner& r, typename Engine<T>::Plan& p, const T* gxa, int B, void** ev, int& seg,
+                            float* dmel) {
+  const int d = c->d;
+  const long Me = (long)B * c->Te, M1 = (long)B * c->T1;
+  hipStream_t st = r.st;
+  const oasr_ctx::Prune& pr = c->pr;
+  if (!pr.enc_any && !dmel) {  // nothing in the encoder is trainable and no d(mel): neither d(xa) (skipped in the decoder blocks) nor anything below it
     for (int i = 0; i < c->L_enc + 2; ++i) RC(r.record(ev, seg++));  // ln_post, the blocks, the conv stem
-    return finish(seg);
+    return OASR_OK;
   }
   const T* xe_last = c->L_enc ? p.enc[c->L_enc - 1].x_out : p.x0;
-  if (c->L_dec == 0) OASR_CHECK_HIP(hipMemsetAsync(p.gxa, 0, (size_t)Me * d * sizeof(T), st));
-  const bool enc_top_in = pr.all || pr.enc_in[c->L_enc];
+  const bool enc_top_in = pr.all || pr.enc_in[c->L_enc] || dmel;
   if (enc_top_in || c->tr(c->enc_lnp_w) || c->tr(c->enc_lnp_b))
-    RC(launch_layernorm_bwd(p.gxa, xe_last, c->P(c->enc_lnp_w), p.mean_p, p.rstd_p, nullptr, p.ga, c->Gt(c->enc_lnp_w), c->Gt(c->enc_lnp_b),
+    RC(launch_layernorm_bwd(gxa, xe_last, c->P(c->enc_lnp_w), p.mean_p, p.rstd_p, nullptr, p.ga, c->Gt(c->enc_lnp_w), c->Gt(c->enc_lnp_b),
                             c->L_enc ? c->Gt(c->enc[c->L_enc - 1].b2) : nullptr, Me, d, st));
   RC(r.record(ev, seg++));
-  dx = p.ga;
+  const T* dx = p.ga;
+  auto others = [&](const T* cur, T** a, T** b) {
+    T* all[3] = {p.ga, p.gb, p.gc};
+    int n = 0;
+    T* o[2] = {nullptr, nullptr};
+    for (int j = 0; j < 3; ++j)
+      if (all[j] != cur && n < 2) o[n++] = all[j];
+    *a = o[0];
+    *b = o[1];
+  };
   for (int i = c->L_enc - 1; i >= 0; --i) {
-    if (pr.all || pr.enc_blk[i] || pr.enc_in[i]) {
+    if (pr.all || pr.enc_blk[i] || pr.enc_in[i] || dmel) {
       T *sa, *sb;
       others(dx, &sa, &sb);
       const T* dx_in = nullptr;
       RC(r.block_bwd(c->enc[i], p.enc[i], p, dx, sa, sb, Me, c->Te, false, false, i > 0 ? c->Gt(c->enc[i - 1].b2) : nullptr, &dx_in,
-                     pr.all || pr.enc_in[i], false));
+                     pr.all || pr.enc_in[i] || dmel, false));
       dx = dx_in;
     }
     RC(r.record(ev, seg++));
   }
   // conv stem: x0 = gelu(u2) + pos ; u2 = conv2(h1) ; h1 = gelu(u1) ; u1 = conv1(mel)
-  if (pr.all || c->tr(c->conv2_w) || c->tr(c->conv2_b) || pr.conv1) {
+  if (pr.all || c->tr(c->conv2_w) || c->tr(c->conv2_b) || pr.conv1 || dmel) {
     RC(launch_dgelu_mul(dx, p.u2, p.gln, Me * d, st));  // gln = d(u2)
     if (c->tr(c->conv2_w)) {
       OASR_CHECK_HIP(hipMemsetAsync(p.tmp_w2p, 0, (size_t)d * 3 * d * 4, st));
@@ -1693,7 +1712,7 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
     }
     if (c->tr(c->conv2_b)) RC(launch_colsum_accum(p.gln, d, Me, d, c->G(c->conv2_b), st));
   }
-  if (pr.all || pr.conv1) {  // the conv2 data gradient serves conv1 alone
+  if (pr.all || pr.conv1 || dmel) {  // the conv2 data gradient serves conv1 (and d(mel)) alone
     RC(r.dgrad(p.gln, Me, d, c->template w2p<T>(), 3 * d, nullptr, nullptr, p.gA2));
     RC(launch_conv2_col2im_dgelu(p.gA2, p.u1, p.gu, B, c->T1, d, st));  // gu = d(u1) [B*3000, d]
     if (c->tr(c->conv1_w)) {
@@ -1723,31 +1742,96 @@ static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename E
       RC(launch_unpack_conv_grad(p.tmp_w1p, c->G(c->conv1_w), d, c->dims.n_mels, 256, st));
     }
     if (c->tr(c->conv1_b)) RC(launch_colsum_accum(p.gu, d, M1, d, c->G(c->conv1_b), st));
+    if (dmel) {
+      // d(mel): the conv1 data gradient as columns dcol [B*T1, 256] = d(u1) . w1p (gA2 is free again), then folded back onto the mel
+      // frames -- taps that fall into the zero padding or the neighbouring sample are dropped (conv_grad.hip).  The bf16 engine's cast of
+      // mel to bf16 counts as the identity here, as autocast's cast does.
+      RC(r.dgrad(p.gu, M1, d, c->template w1p<T>(), 256, nullptr, nullptr, p.gA2));
+      RC(launch_conv1_col2im_mel(p.gA2, dmel, B, c->T1, c->dims.n_mels, st));
+    }
   }
   RC(r.record(ev, seg++));
-  return finish(seg);
+  return OASR_OK;
+}
+
+// adapter contexts: the adapted weights' gradients of THIS micro-batch go to workspace scratch (projected into the arena at the end)
+template <typename T>
+static int backward_begin(oasr_ctx* c, typename Engine<T>::Runner& r, typename Engine<T>::Plan& p) {
+  if (!c->lora.empty()) {
+    OASR_CHECK_HIP(hipMemsetAsync(p.lora_dw, 0, (size_t)c->lora_dw_floats * 4, r.st));
+    r.lora_dw = p.lora_dw;
+  }
+  return OASR_OK;
+}
+// the last gradient segment of an adapter context: d lora_B = s * dW . lora_A^T, d lora_A = s * lora_B^T . dW (every dW is final here).
+// A stage's backward projects the adapters of its own stage's weights only (the other stage's scratch was never written).
+template <typename T>
+static int backward_finish(oasr_ctx* c, typename Engine<T>::Runner& r, typename Engine<T>::Plan& p, void** ev, int seg, int stage) {
+  if (!c->lora.empty()) {
+    for (const oasr_ctx::Lora& L : c->lora) {
+      const bool in_enc = L.w >= c->enc_lnp_w && L.w < c->stem_end;
+      if ((stage == STAGE_ENC && !in_enc) || (stage == STAGE_DEC && in_enc)) continue;
+      float *ga = c->Gt(L.a), *gb = c->Gt(L.b);
+      if (ga || gb)
+        RC(launch_lora_grad(p.lora_dw + L.dw, c->P(L.a), c->P(L.b), L.out, L.in, c->lora_r, c->lora_s, ga, gb, p.lora_part, r.st));
+    }
+    RC(r.record(ev, seg++));
+  }
+  if (stage == STAGE_ALL && seg != (int)c->segments.size()) {
+    oasr_set_error("internal: segment count mismatch %d vs %zu", seg, c->segments.size());
+    return OASR_ESTATE;
+  }
+  return OASR_OK;
+}
+// refusals shared by every backward entry.  The fused ones need a trainable tensor; a stage backward that returns an input gradient does not
+// (saliency on a frozen model).
+static int backward_check(const oasr_ctx* c, bool input_grad) {
+  if (!c->lora.empty() && !c->mask_set) {
+    oasr_set_error("oasr_train backward: a context with adapters needs oasr_set_trainable before the first backward");
+    return OASR_ESTATE;
+  }
+  if (!c->pr.any && !input_grad) {
+    oasr_set_error("oasr_train backward: no parameter is trainable (oasr_set_trainable mask is all zeros)");
+    return OASR_ESTATE;
+  }
+  return OASR_OK;
+}
+
+template <typename T>
+static int train_backward(oasr_ctx* c, typename Engine<T>::Runner& r, typename Engine<T>::Plan& p, const int64_t* tokens, int B, int S, void** ev) {
+  // Frozen parameters (oasr_set_trainable, oasr_ctx::Prune): launches that only serve frozen tensors are left out, the data gradient
+  // stops where nothing earlier in the forward is trainable.  Every segment event is still recorded (DDP buckets wait on them).
+  RC(backward_check(c, false));
+  RC(backward_begin<T>(c, r, p));
+  int seg = 0;
+  RC(backward_decoder<T>(c, r, p, tokens, B, S, ev, seg, c->pr.all || c->pr.enc_any));
+  RC(backward_encoder<T>(c, r, p, p.gxa, B, ev, seg, nullptr));
+  return backward_finish<T>(c, r, p, ev, seg, STAGE_ALL);
 }
 
 template <typename T>
 static int oasr_train_fwd_bwd_s_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets,
                                     const int32_t* text_len, int B, int S, float loss_scale, float inv_accum, float* loss_out,
                                     int accumulate_loss, float* logits_out, void** ev, void* workspace, size_t workspace_bytes,
-                                    void* stream, const float* mel_clip_max = nullptr) {
+                                    void* stream, const float* mel_clip_max = nullptr, const void* xa_in = nullptr) {
   RC(check_bound(c, true));
   OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_fwd_bwd: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
-  OASR_REQUIRE(mel && tokens && targets && text_len && loss_out && workspace && B > 0, "oasr_train_fwd_bwd: bad args");
-  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN), "oasr_train_fwd_bwd: workspace too small");
+  OASR_REQUIRE((mel || xa_in) && tokens && targets && text_len && loss_out && workspace && B > 0, "oasr_train_fwd_bwd: bad args");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, xa_in ? OASR_MODE_TRAIN_DEC : OASR_MODE_TRAIN), "oasr_train_fwd_bwd: workspace too small");
   const long Md = (long)B * S;
   Arena A(workspace, workspace_bytes);
   typename Engine<T>::Plan p;
-  Engine<T>::make_plan(c, A, p, B, S, true);
+  Engine<T>::make_plan(c, A, p, B, S, true, xa_in ? STAGE_DEC : STAGE_ALL);
   typename Engine<T>::Runner r{c, (hipStream_t)stream, B, S, text_len};
   r.train = true;
   r.cs_scratch = p.gemm_cs_scratch;
   r.mel_clip_max = mel_clip_max;  // un-finalized log-mel (oasr_log_mel_raw): the floor / scale lines ride in the encoder's transpose
   hipStream_t st = r.st;
   // ---------------- forward ----------------
-  RC(r.encoder_fwd(p, mel));
+  if (xa_in)  // (oasr_train_dec_fwd_bwd: the decoder on the caller's encoder output)
+    OASR_CHECK_HIP(hipMemcpyAsync(p.xa, xa_in, (size_t)B * c->Te * c->d * sizeof(T), hipMemcpyDeviceToDevice, st));
+  else
+    RC(r.encoder_fwd(p, mel));
   RC(r.decoder_fwd(p, tokens));
   if (logits_out) RC(launch_logits_to_f32(p.logits, c->Vp, Md, c->V, logits_out, st));
   RC(launch_count_valid(targets, Md, PAD_ID, c->V, p.n_valid, st));
@@ -1773,12 +1857,12 @@ template <typename T>
 static int oasr_train_fwd_bwd_span_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
                                        const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
                                        float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
+                                       size_t workspace_bytes, void* stream, const void* xa_in = nullptr) {
   const int S = c->S_max;
   const long Md = (long)B * S;
   Arena A(workspace, workspace_bytes);
   typename Engine<T>::Plan p;
-  Engine<T>::make_plan(c, A, p, B, S, true);
+  Engine<T>::make_plan(c, A, p, B, S, true, xa_in ? STAGE_DEC : STAGE_ALL);
   typename Engine<T>::Runner r{c, (hipStream_t)stream, B, S, text_len};
   r.train = true;
   r.cs_scratch = p.gemm_cs_scratch;
@@ -1793,7 +1877,10 @@ static int oasr_train_fwd_bwd_span_impl(oasr_ctx* c, const float* mel, const int
   r.mel_clip_max = mel_clip_max;
   if (const int mode = span_side_streams()) RC(r.side_begin(mode));
   // ---------------- forward (every position, unless the caller opted out of the padded ones) ----------------
-  RC(r.encoder_fwd(p, mel));
+  if (xa_in)
+    OASR_CHECK_HIP(hipMemcpyAsync(p.xa, xa_in, (size_t)B * c->Te * c->d * sizeof(T), hipMemcpyDeviceToDevice, st));
+  else
+    RC(r.encoder_fwd(p, mel));
   RC(r.decoder_fwd(p, tokens));
   // loss over the active rows (the other rows' targets are ignore_index: they add nothing to the sum and nothing to the count)
   RC(launch_count_valid(targets, Md, PAD_ID, c->V, p.n_valid, st));
@@ -1877,6 +1964,135 @@ extern "C" int oasr_train_fwd_bwd_s(oasr_ctx* c, const float* mel, const int64_t
   return c->f32 ? oasr_train_fwd_bwd_s_impl<float>(c, mel, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss, logits_out, ev, workspace, workspace_bytes, stream) : oasr_train_fwd_bwd_s_impl<bf16_t>(c, mel, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss, logits_out, ev, workspace, workspace_bytes, stream);
 }
 
+// ---- the training step in two stages, for torch.autograd through model.encoder / model.decoder -------------------
+// Each stage has a workspace plan of its own (OASR_MODE_TRAIN_ENC / _DEC) that holds one forward's saved activations until its backward.
+// The forwards are the fused training forward's (train = true: the MLP epilogue saves GELU'(u)), cut at xa: encode then decode runs the
+// kernels of oasr_train_fwd on the same inputs, plus one copy of xa into the decoder's plan.  The backwards are the two halves of
+// train_backward, started from the caller's d(logits) / d(xa); a requested input gradient (d(xa), d(mel)) is computed even where the mask
+// would prune it, and an all-frozen mask is accepted when one is requested.
+template <typename T>
+static int oasr_train_encode_impl(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  Arena A(workspace, workspace_bytes);
+  typename Engine<T>::Plan p;
+  Engine<T>::make_plan(c, A, p, B, 1, true, STAGE_ENC);
+  typename Engine<T>::Runner r{c, (hipStream_t)stream, B, 1, nullptr};
+  r.train = true;
+  r.cs_scratch = p.gemm_cs_scratch;
+  RC(r.encoder_fwd(p, mel));
+  OASR_CHECK_HIP(hipMemcpyAsync(xa_out, p.xa, (size_t)B * c->Te * c->d * sizeof(T), hipMemcpyDeviceToDevice, r.st));
+  return OASR_OK;
+}
+template <typename T>
+static int oasr_train_encode_bwd_impl(oasr_ctx* c, const void* dxa, int B, float* dmel_out, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  RC(backward_check(c, dmel_out != nullptr));
+  Arena A(workspace, workspace_bytes);
+  typename Engine<T>::Plan p;
+  Engine<T>::make_plan(c, A, p, B, 1, true, STAGE_ENC);
+  typename Engine<T>::Runner r{c, (hipStream_t)stream, B, 1, nullptr};
+  r.train = true;
+  r.cs_scratch = p.gemm_cs_scratch;
+  RC(backward_begin<T>(c, r, p));
+  int seg = 0;
+  RC(backward_encoder<T>(c, r, p, (const T*)dxa, B, nullptr, seg, dmel_out));
+  return backward_finish<T>(c, r, p, nullptr, seg, STAGE_ENC);
+}
+template <typename T>
+static int oasr_train_decode_impl(oasr_ctx* c, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S, float* logits_out,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  Arena A(workspace, workspace_bytes);
+  typename Engine<T>::Plan p;
+  Engine<T>::make_plan(c, A, p, B, S, true, STAGE_DEC);
+  typename Engine<T>::Runner r{c, (hipStream_t)stream, B, S, text_len};
+  r.train = true;
+  r.cs_scratch = p.gemm_cs_scratch;
+  OASR_CHECK_HIP(hipMemcpyAsync(p.xa, xa, (size_t)B * c->Te * c->d * sizeof(T), hipMemcpyDeviceToDevice, r.st));
+  RC(r.decoder_fwd(p, tokens));
+  return launch_logits_to_f32(p.logits, c->Vp, (long)B * S, c->V, logits_out, r.st);
+}
+template <typename T>
+static int oasr_train_decode_bwd_impl(oasr_ctx* c, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S,
+                                      void* dxa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(backward_check(c, dxa_out != nullptr));
+  Arena A(workspace, workspace_bytes);
+  typename Engine<T>::Plan p;
+  Engine<T>::make_plan(c, A, p, B, S, true, STAGE_DEC);
+  typename Engine<T>::Runner r{c, (hipStream_t)stream, B, S, text_len};
+  r.train = true;
+  r.cs_scratch = p.gemm_cs_scratch;
+  RC(launch_dlogits_from_f32(dlogits, c->V, (long)B * S, c->Vp, p.logits, r.st));
+  RC(backward_begin<T>(c, r, p));
+  int seg = 0;
+  RC(backward_decoder<T>(c, r, p, tokens, B, S, nullptr, seg, dxa_out != nullptr));
+  // d(xa) in the compute dtype, summed over the decoder layers in block_bwd's order (top layer first)
+  if (dxa_out) OASR_CHECK_HIP(hipMemcpyAsync(dxa_out, p.gxa, (size_t)B * c->Te * c->d * sizeof(T), hipMemcpyDeviceToDevice, r.st));
+  return backward_finish<T>(c, r, p, nullptr, seg, STAGE_DEC);
+}
+extern "C" int oasr_train_encode(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(mel && xa_out && workspace && B > 0, "oasr_train_encode: bad args (mel, xa_out and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, 1, OASR_MODE_TRAIN_ENC), "oasr_train_encode: workspace too small");
+  return c->f32 ? oasr_train_encode_impl<float>(c, mel, B, xa_out, workspace, workspace_bytes, stream)
+                : oasr_train_encode_impl<bf16_t>(c, mel, B, xa_out, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_encode_bwd(oasr_ctx* c, const void* dxa, int B, float* dmel_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(dxa && workspace && B > 0, "oasr_train_encode_bwd: bad args (dxa and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, 1, OASR_MODE_TRAIN_ENC), "oasr_train_encode_bwd: workspace too small");
+  return c->f32 ? oasr_train_encode_bwd_impl<float>(c, dxa, B, dmel_out, workspace, workspace_bytes, stream)
+                : oasr_train_encode_bwd_impl<bf16_t>(c, dxa, B, dmel_out, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_decode(oasr_ctx* c, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S, float* logits_out,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_decode: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
+  OASR_REQUIRE(tokens && xa && text_len && logits_out && workspace && B > 0,
+               "oasr_train_decode: bad args (tokens, xa, text_len, logits_out and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_decode: workspace too small");
+  return c->f32 ? oasr_train_decode_impl<float>(c, tokens, xa, text_len, B, S, logits_out, workspace, workspace_bytes, stream)
+                : oasr_train_decode_impl<bf16_t>(c, tokens, xa, text_len, B, S, logits_out, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_decode_bwd(oasr_ctx* c, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void* dxa_out,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_decode_bwd: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
+  OASR_REQUIRE(tokens && text_len && dlogits && workspace && B > 0,
+               "oasr_train_decode_bwd: bad args (tokens, text_len, dlogits and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_decode_bwd: workspace too small");
+  return c->f32 ? oasr_train_decode_bwd_impl<float>(c, tokens, text_len, dlogits, B, S, dxa_out, workspace, workspace_bytes, stream)
+                : oasr_train_decode_bwd_impl<bf16_t>(c, tokens, text_len, dlogits, B, S, dxa_out, workspace, workspace_bytes, stream);
+}
+// The fused loss step of the decoder alone, from the caller's encoder output (a frozen encoder whose xa is computed once and reused):
+// oasr_train_fwd_bwd_s / _span with the encoder forward replaced by a copy of xa.  Every segment event is recorded; the encoder's at once,
+// as the frozen-encoder step records them.
+extern "C" int oasr_train_dec_fwd_bwd(oasr_ctx* c, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                      const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
+                                      int accumulate_loss, void** ev, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(xa && tokens && targets && text_len && loss_out && workspace && B > 0 && S > 0 && S <= c->S_max,
+               "oasr_train_dec_fwd_bwd: bad args (xa, tokens, targets, text_len, loss_out and workspace are required, 0 < S <= n_text_ctx)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_dec_fwd_bwd: workspace too small");
+  if (c->pr.enc_any) {
+    oasr_set_error("oasr_train_dec_fwd_bwd: an encoder tensor is trainable -- the step from a given xa has no encoder backward (freeze the "
+                   "encoder, or use oasr_train_fwd_bwd*)");
+    return OASR_ESTATE;
+  }
+  const bool chunked = (c->S_max % 64) == 0 && c->S_max <= 64 * OASR_ROWTAB && B <= 512;
+  if (span_host && chunked) {
+    OASR_REQUIRE(S == c->S_max, "oasr_train_dec_fwd_bwd: a span step covers the whole context (S = %d, n_text_ctx = %d)", S, c->S_max);
+    OASR_REQUIRE(span_forward == OASR_SPAN_FORWARD_ALL || span_forward == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_dec_fwd_bwd: span_forward");
+    return c->f32 ? oasr_train_fwd_bwd_span_impl<float>(c, nullptr, tokens, targets, text_len, span_host, span_forward, nullptr, B, loss_scale,
+                                                        inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, xa)
+                  : oasr_train_fwd_bwd_span_impl<bf16_t>(c, nullptr, tokens, targets, text_len, span_host, span_forward, nullptr, B, loss_scale,
+                                                         inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, xa);
+  }
+  // (no span, or no chunking for this shape: the plain step, same results)
+  return c->f32 ? oasr_train_fwd_bwd_s_impl<float>(c, nullptr, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss,
+                                                   nullptr, ev, workspace, workspace_bytes, stream, nullptr, xa)
+                : oasr_train_fwd_bwd_s_impl<bf16_t>(c, nullptr, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss,
+                                                    nullptr, ev, workspace, workspace_bytes, stream, nullptr, xa);
+}
+
 // ---- frozen parameters ----------------------------------------------------------------------------------------------------------
 // The plan of the pruned backward (oasr_ctx::Prune) and the optimizer's table of trainable runs, derived here once per mask change.
 extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params) {
@@ -1938,7 +2154,9 @@ extern "C" int oasr_set_trainable(oasr_ctx* c, const uint8_t* mask, int n_params
   }
   // dec_in[i]: the gradient of block i's input is needed -- by the embeddings, a lower block, or (i > 0) a lower block's d(xa)
   bool below = any_in(c->tok_emb, c->tok_emb + 1) || any_in(c->dec_pos, c->dec_pos + 1);
+  pr.dec_below.assign(Ld + 1, 0);
   for (int i = 0; i <= Ld; ++i) {
+    pr.dec_below[i] = below;
     pr.dec_in[i] = below || (i > 0 && pr.enc_any);
     if (i < Ld) below = below || pr.dec_blk[i];
   }

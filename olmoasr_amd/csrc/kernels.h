@@ -219,6 +219,10 @@ int launch_colsum_accum(const bf16_t* x, long ld, long M, int ncols, float* out,
 // conv2 input-gradient fold + conv1 GELU backward: dpre1[b,t,c] = gelu'(u1) * sum of the dA windows covering t
 int launch_conv2_col2im_dgelu(const bf16_t* dA /*[B*T2][3d]*/, const bf16_t* u1 /*[B*T1][d]*/, bf16_t* dpre1, int B, int T1,
                               int d, hipStream_t s);
+// conv1 input gradient (conv_grad.hip): dcol [B*T1][256] = the conv1 data gradient as im2col columns (k*n_mels + c) -> fp32 channel-major
+//   dmel[b][c][t] = sum_{k=0..2, 0 <= t+1-k < T1} dcol[b*T1 + t+1-k][k*n_mels + c]   (taps in the zero padding / the next sample dropped)
+int launch_conv1_col2im_mel(const bf16_t* dcol, float* dmel, int B, int T1, int n_mels, hipStream_t s);
+int launch_conv1_col2im_mel(const float* dcol, float* dmel, int B, int T1, int n_mels, hipStream_t s);
 // dst(f32) += src(f32) over n  (grad of the fp32 sinusoid buffer is not needed; used for misc accumulations)
 int launch_axpy_f32(const float* src, float* dst, long n, float a, hipStream_t s);
 // fp32 validation overloads (fp32ref.hip): same contracts with fp32 activations

@@ -44,12 +44,18 @@ def sinusoids(length, channels, max_timescale=10000):
 class _ParamModule(nn.Module):
     """Leaf holder: parameters are attached later as views of the flat arena.
 
-    The engine runs whole stacks (``model.encoder(mel)``, ``model.decoder(tokens, xa[, kv_cache])``, ``OLMoASR.forward`` /
-    ``loss_and_backward``): that is the hot path.  The per-module ``forward``s of the reference (``LayerNorm`` model.py:14-39,
-    ``Linear`` :42-101, ``Conv1d`` :104-196, ``MultiHeadAttention`` :266-345, ``ResidualAttentionBlock`` :485-528) exist below as
-    INFERENCE-ONLY compositions of the same native operators (bf16 MFMA GEMMs with fused bias / GELU / residual epilogues,
-    LayerNorm and flash-attention kernels) for code that walks the module tree -- probing one block, feature extraction, a
-    layer-wise comparison with a reference checkpoint.  They return tensors without a grad_fn; training goes through the engine."""
+    The engine runs whole stacks: that is the hot path.  Three of them are differentiable, as in the reference:
+      * ``OLMoASR.forward`` (``model(mel, tokens, mask)``) in training mode: the fused training step cut at the logits (``_TrainStep``);
+      * ``model.encoder(mel)`` and ``model.decoder(tokens, xa, padding_mask=...)`` (no ``kv_cache``): the same step in two stages
+        (``_EncoderStage`` / ``_DecoderStage``).  With autograd enabled, the model in training mode and some
+        parameter of the stage -- or its input -- requiring grad, they return tensors with a grad_fn; their backward accumulates into
+        ``p.grad`` and returns d(mel) / d(xa) to inputs that require grad.  Otherwise they are ``embed_audio`` / ``logits``: no graph.
+    ``embed_audio``, ``logits``, the cached ``model.decoder(..., kv_cache=cache)`` path, ``loss_and_backward`` (its own fused backward) and
+    decoding are inference-only or fused.  The per-module ``forward``s of the reference (``LayerNorm`` model.py:14-39, ``Linear``
+    :42-101, ``Conv1d`` :104-196, ``MultiHeadAttention`` :266-345, ``ResidualAttentionBlock`` :485-528) exist below as INFERENCE-ONLY
+    compositions of the same native operators (bf16 MFMA GEMMs with fused bias / GELU / residual epilogues, LayerNorm and
+    flash-attention kernels) for code that walks the module tree -- probing one block, feature extraction, a layer-wise comparison with a
+    reference checkpoint.  They return tensors without a grad_fn."""
 
     def forward(self, *a, **k):  # pragma: no cover
         raise N.NativeError(f"{type(self).__name__}.forward: the native engine runs whole stacks -- call model.encoder(mel), "
@@ -182,6 +188,72 @@ class _TrainStep(torch.autograd.Function):
         if post is not None:
             post()  # ddp.DistributedDataParallel: bucketed all-reduce of the arena, overlapped through the segment events
         return None, None, None, None, None
+
+
+class _EncoderStage(torch.autograd.Function):
+    """``model.encoder(mel)`` with a grad_fn: oasr_train_encode keeps the encoder's saved activations in the model's encoder-stage workspace
+    (not the one ``_TrainStep`` and the inference calls share), backward hands d(xa) to oasr_train_encode_bwd, which accumulates the
+    encoder's gradients into the arena and returns d(mel) when ``mel`` requires grad."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, mel):
+        B = mel.shape[0]
+        mel_c = mel.detach().float().contiguous()
+        ws = model._stage_ws("enc", B, 1)
+        xa = torch.empty(B, model.dims.n_audio_ctx, model.dims.n_audio_state, device=mel.device, dtype=model._act_dtype)
+        with torch.cuda.device(mel.device):
+            N.check(N.lib().oasr_train_encode(model._ctx, N.ptr(mel_c), B, N.ptr(xa), N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_train_encode")
+        ctx.model, ctx.gen, ctx.B = model, model._stage_forward("enc"), B
+        return xa
+
+    @staticmethod
+    def backward(ctx, dxa):
+        model, B = ctx.model, ctx.B
+        ws = model._stage_backward_ws("enc", ctx.gen, "model.encoder")
+        dxa = dxa.to(model._act_dtype).contiguous()
+        dmel = (torch.empty(B, model.dims.n_mels, 2 * model.dims.n_audio_ctx, device=dxa.device, dtype=torch.float32)
+                if ctx.needs_input_grad[2] else None)
+        with torch.cuda.device(dxa.device):
+            N.check(N.lib().oasr_train_encode_bwd(model._ctx, N.ptr(dxa), B, N.ptr(dmel), N.ptr(ws), ws.numel(), N.stream_ptr()),
+                    "oasr_train_encode_bwd")
+        model._stage_gen["enc"] += 1  # consumed
+        return None, None, dmel
+
+
+class _DecoderStage(torch.autograd.Function):
+    """``model.decoder(tokens, xa, padding_mask=...)`` with a grad_fn: oasr_train_decode copies ``xa`` into the decoder-stage workspace and
+    keeps the decoder's saved activations there; backward hands d(logits) to oasr_train_decode_bwd, which accumulates the decoder's
+    gradients into the arena and returns d(xa) when ``xa`` requires grad."""
+
+    @staticmethod
+    def forward(ctx, anchor, model, tokens, xa, text_len):
+        B, S = tokens.shape
+        xa_c = xa.detach().to(model._act_dtype).contiguous()
+        tokens = tokens.to(torch.int64).contiguous()
+        text_len = (torch.full((B,), S, dtype=torch.int32, device=tokens.device) if text_len is None else text_len.to(torch.int32).contiguous())
+        ws = model._stage_ws("dec", B, S)
+        logits = torch.empty(B, S, model._n_rows, device=tokens.device, dtype=torch.float32)
+        with torch.cuda.device(tokens.device):
+            N.check(N.lib().oasr_train_decode(model._ctx, N.ptr(tokens), N.ptr(xa_c), N.ptr(text_len), B, S, N.ptr(logits), N.ptr(ws),
+                                              ws.numel(), N.stream_ptr()), "oasr_train_decode")
+        ctx.model, ctx.gen = model, model._stage_forward("dec")
+        ctx.save_for_backward(tokens, text_len)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        model = ctx.model
+        ws = model._stage_backward_ws("dec", ctx.gen, "model.decoder")
+        tokens, text_len = ctx.saved_tensors
+        B, S = tokens.shape
+        dlogits = dlogits.float().contiguous()
+        dxa = (torch.empty(B, model.dims.n_audio_ctx, model.dims.n_audio_state, device=dlogits.device, dtype=model._act_dtype)
+               if ctx.needs_input_grad[3] else None)
+        with torch.cuda.device(dlogits.device):
+            N.check(N.lib().oasr_train_decode_bwd(model._ctx, N.ptr(tokens), N.ptr(text_len), N.ptr(dlogits), B, S, N.ptr(dxa), N.ptr(ws),
+                                                  ws.numel(), N.stream_ptr()), "oasr_train_decode_bwd")
+        model._stage_gen["dec"] += 1  # consumed
+        return None, None, None, dxa, None
 
 
 class _HookHandle:
@@ -355,8 +427,18 @@ class AudioEncoder(_ParamModule):
         self.ln_post = LayerNorm(n_state)
 
     def forward(self, x: Tensor, verbose: bool = False):
-        """AudioEncoder.forward (olmoasr/model.py:571-623): mel [B, n_mels, 3000] -> [B, n_audio_ctx, n_state]."""
-        return self._engine().embed_audio(x)
+        """AudioEncoder.forward (olmoasr/model.py:571-623): mel [B, n_mels, 3000] -> [B, n_audio_ctx, n_state] in the compute dtype.
+
+        Differentiable (``_EncoderStage``) when autograd is enabled, the model is in training mode (and not ``inference``) and an encoder
+        parameter or ``x`` requires grad: then it runs the training-mode forward of ``model(mel, ...)`` (in bf16 its GELU epilogue rounds
+        differently from ``embed_audio``'s).  Otherwise it is ``embed_audio``."""
+        m = self._engine()
+        if m._stage_wants_grad(self, x):
+            N.require_gpu(x, "mel")
+            assert x.shape[1:] == (m.dims.n_mels, 2 * m.dims.n_audio_ctx), "incorrect audio shape"
+            m._stage_begin(x.requires_grad)
+            return _EncoderStage.apply(m._autograd_anchor(), m, x)
+        return m.embed_audio(x)
 
 
 class TextDecoder(_ParamModule):
@@ -370,9 +452,23 @@ class TextDecoder(_ParamModule):
                 verbose: bool = False):
         """TextDecoder.forward (olmoasr/model.py:688-775): fp32 logits [B, n_tokens, rows].  ``kv_cache`` is the dict of
         ``install_kv_cache_hooks``: empty on the first call (all prompt tokens are consumed), afterwards only the new
-        tokens are passed (whisper's PyTorchInference.logits feeds ``tokens[:, -1:]``)."""
+        tokens are passed (whisper's PyTorchInference.logits feeds ``tokens[:, -1:]``).
+
+        Without ``kv_cache`` it is differentiable (``_DecoderStage``) when autograd is enabled, the model is in training mode (and not
+        ``inference``) and a decoder parameter or ``xa`` requires grad: the training-mode decoder of ``model(mel, ...)`` on the given ``xa``.
+        Otherwise it is ``logits``.  The ``kv_cache`` path never records a graph."""
         m = self._engine()
         if kv_cache is None:
+            if m._stage_wants_grad(self, xa):
+                N.require_gpu(x, "tokens")
+                N.require_gpu(xa, "xa")
+                assert xa.shape == (x.shape[0], m.dims.n_audio_ctx, m.dims.n_audio_state), "incorrect audio feature shape"
+                text_len = None
+                if padding_mask is not None:
+                    text_len = padding_mask.to(torch.int32) if padding_mask.dim() == 1 else m._text_len_from_mask(padding_mask)
+                    text_len = text_len.to(x.device).contiguous()
+                m._stage_begin(xa.requires_grad)
+                return _DecoderStage.apply(m._autograd_anchor(), m, x, xa, text_len)
             return m.logits(x, xa, padding_mask)
         entry = next(iter(kv_cache.values()), None)
         if entry is None:
@@ -457,6 +553,8 @@ class OLMoASR(nn.Module):
         self._gflat = None
         self._shadow = torch.zeros(lib.oasr_shadow_bytes(self._ctx), dtype=torch.uint8, device=device)
         self._workspace = None
+        self._stage_workspace = {}  # "enc" / "dec": the staged autograd entries' own workspaces (allocated on first use)
+        self._stage_gen = {"enc": 0, "dec": 0}
         import weakref
         for sub in (self.encoder, self.decoder):  # stack-level forward()s call back into the engine (no module cycle)
             sub.__dict__["_owner"] = weakref.ref(self)
@@ -517,6 +615,7 @@ class OLMoASR(nn.Module):
         self._flat = flat
         self._shadow = torch.zeros(N.lib().oasr_shadow_bytes(self._ctx), dtype=torch.uint8, device=flat.device)
         self._workspace = None
+        self._stage_workspace = {}
         self._trainable_mask = None
         self._param_version = None
         self._attach_views()
@@ -558,6 +657,7 @@ class OLMoASR(nn.Module):
             self._gflat = fn(self._gflat).contiguous()
         self._shadow = self._shadow.to(self._flat.device)
         self._workspace = None
+        self._stage_workspace = {}
         if getattr(self, "_opt_state", None) is not None:  # optimizer arenas follow the parameters
             self._opt_state = tuple(fn(t).contiguous() for t in self._opt_state)
             self._opt_stats = self._opt_stats.to(self._flat.device)
@@ -636,6 +736,41 @@ class OLMoASR(nn.Module):
             self._workspace = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
         return self._workspace
 
+    # ---- staged autograd (model.encoder / model.decoder with a grad_fn) -------------------------------------------------------
+    def _stage_wants_grad(self, stage_module, inp) -> bool:
+        """``forward``'s rule for its training path, per stage: autograd on, training mode, and something in the stage to differentiate."""
+        if not (torch.is_grad_enabled() and self.training and not self.inference):
+            return False
+        return bool(getattr(inp, "requires_grad", False)) or any(p.requires_grad for p in stage_module.parameters())
+
+    def _stage_begin(self, input_grad: bool):
+        if getattr(self, "_autograd_post_backward", None) is not None:
+            raise N.NativeError("model.encoder / model.decoder with autograd under olmoasr_amd.ddp.DistributedDataParallel: the wrapper reduces "
+                                "gradients after the backward of model(mel, tokens, mask) only -- train through model(mel, tokens, mask) (or "
+                                "loss_and_backward + GradReducer), or call the stages under torch.no_grad()")
+        self._sync_for_autograd(allow_none=input_grad)
+
+    def _stage_ws(self, stage, B, S):
+        mode = N.MODE_TRAIN_ENC if stage == "enc" else N.MODE_TRAIN_DEC
+        need = N.lib().oasr_workspace_bytes(self._ctx, B, S, mode)
+        ws = self._stage_workspace.get(stage)
+        if ws is None or ws.numel() < need:
+            self._stage_workspace[stage] = None
+            ws = self._stage_workspace[stage] = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
+        return ws
+
+    def _stage_forward(self, stage) -> int:
+        self._stage_gen[stage] += 1
+        return self._stage_gen[stage]
+
+    def _stage_backward_ws(self, stage, gen, what):
+        ws = self._stage_workspace.get(stage)
+        if gen != self._stage_gen[stage] or ws is None:
+            raise RuntimeError(f"{what} backward: the activations of this forward are gone -- the engine keeps ONE forward's activations per "
+                               "stage (in the stage's workspace) and a later forward of the same stage or a previous backward through this "
+                               "graph used them; run forward and backward in pairs (gradient accumulation: forward/backward per micro-batch)")
+        return ws
+
     # ---- reference API ---------------------------------------------------------------------------------------
     @staticmethod
     def _text_len_from_mask(padding_mask: Tensor) -> Tensor:
@@ -682,15 +817,16 @@ class OLMoASR(nn.Module):
             a = self._anchor = torch.zeros((), device=self._flat.device, requires_grad=True)
         return a
 
-    def _sync_trainable(self):
+    def _sync_trainable(self, allow_none: bool = False):
         """``requires_grad`` of the parameters -> the engine's trainability mask (``oasr_set_trainable``), pushed when it changed.  A
         frozen parameter has ``.grad is None`` and its gradient range of the arena is neither written nor read (the backward prunes
         everything that only served it; the optimizer steps the trainable runs only).  A parameter that becomes trainable again starts
-        from a zeroed gradient.  Returns the mask (one bool per arena tensor)."""
+        from a zeroed gradient.  Returns the mask (one bool per arena tensor).  ``allow_none``: a stage call that returns an input gradient
+        (saliency on a frozen model) may run with no trainable parameter."""
         mask = tuple(bool(p.requires_grad) for p, *_ in self._param_views)
+        if not any(mask) and not allow_none:
+            raise N.NativeError("every parameter has requires_grad=False: nothing to train")
         if mask != getattr(self, "_trainable_mask", None):
-            if not any(mask):
-                raise N.NativeError("every parameter has requires_grad=False: nothing to train")
             buf = (C.c_uint8 * len(mask))(*mask)
             with torch.cuda.device(self._flat.device):
                 N.check(N.lib().oasr_set_trainable(self._ctx, buf, len(mask)), "oasr_set_trainable")
@@ -706,12 +842,12 @@ class OLMoASR(nn.Module):
                         p.grad = g
         return mask
 
-    def _sync_for_autograd(self):
+    def _sync_for_autograd(self, allow_none: bool = False):
         """What a torch training loop may have done to the parameters since the last engine call: ``optimizer.step()`` wrote the fp32
         masters in place (-> refresh the bf16 compute copies), ``zero_grad(set_to_none=True)`` dropped ``p.grad`` (-> those gradients
         are reset: zero their arena ranges and re-attach the views), ``requires_grad_(False)`` froze parameters (-> ``_sync_trainable``)."""
         self.enable_grad_arena()
-        mask = self._sync_trainable()
+        mask = self._sync_trainable(allow_none)
         ver, dropped = 0, False
         for (p, off, numel, shape), t in zip(self._param_views, mask):
             ver += p._version
@@ -904,7 +1040,8 @@ class OLMoASR(nn.Module):
     def loss_and_backward(self, mel: Tensor, tokens: Tensor, targets: Tensor, text_len: Tensor, *, loss_scale: float = 1.0,
                           accumulation_steps: int = 1, loss_out: Optional[Tensor] = None, accumulate_loss: bool = False,
                           return_logits: bool = False, segment_events=None, text_ctx: Optional[int] = None, span=None,
-                          span_forward: Optional[bool] = None, mel_clip_max: Optional[Tensor] = None):
+                          span_forward: Optional[bool] = None, mel_clip_max: Optional[Tensor] = None,
+                          audio_features: Optional[Tensor] = None):
         """forward + F.cross_entropy(ignore_index=51864)/accumulation_steps + backward of (loss * loss_scale)
         (train_timestamps.py:1440-1454).  Gradients accumulate into ``flat_grads``.  Returns (loss tensor [1], logits|None).
 
@@ -922,8 +1059,26 @@ class OLMoASR(nn.Module):
 
         ``text_ctx`` (opt-in, not in the reference): run the decoder over the first ``text_ctx`` positions only.  With
         ``text_ctx >= max(text_len)`` the loss and gradients equal the full-context ones (the rest is padding the
-        reference computes and then ignores); logits are returned for those positions only."""
-        for t, nm in ((mel, "mel"), (tokens, "tokens"), (targets, "targets"), (text_len, "text_len")):
+        reference computes and then ignores); logits are returned for those positions only.
+
+        ``audio_features`` (with ``mel=None``): the step of a frozen encoder from its given output xa [B, n_audio_ctx, n_audio_state]
+        (``oasr_train_dec_fwd_bwd``): the decoder's forward, loss and backward only -- for features computed once (``embed_audio``, or
+        ``model.encoder(mel)`` in training mode for the bits the fused step computes) and reused every epoch.  ``span``, ``span_forward``,
+        ``segment_events``, ``loss_scale`` and ``accumulation_steps`` work as above; an encoder parameter that requires grad, ``mel_clip_max``,
+        ``text_ctx`` and ``return_logits`` raise ``ValueError``."""
+        if audio_features is not None:
+            if mel is not None:
+                raise ValueError("loss_and_backward: pass mel=None with audio_features (the step starts from the encoder output)")
+            if mel_clip_max is not None or text_ctx is not None or return_logits:
+                raise ValueError("loss_and_backward(audio_features=...): mel_clip_max / text_ctx / return_logits do not apply to the step from "
+                                 "given encoder features")
+            if any(p.requires_grad for p in self.encoder.parameters()):
+                raise ValueError("loss_and_backward(audio_features=...): an encoder parameter requires grad, but the step from given features "
+                                 "has no encoder backward -- freeze the encoder (requires_grad_(False)) or pass mel")
+            N.require_gpu(audio_features, "audio_features")
+        else:
+            N.require_gpu(mel, "mel")
+        for t, nm in ((tokens, "tokens"), (targets, "targets"), (text_len, "text_len")):
             N.require_gpu(t, nm)
         self.enable_grad_arena()
         B, S = tokens.shape
@@ -931,14 +1086,20 @@ class OLMoASR(nn.Module):
         if text_ctx is not None:
             S = max(1, min(int(text_ctx), S))
             tokens, targets = tokens[:, :S], targets[:, :S]
-        mel = mel.float().contiguous()
+        xa = None
+        if audio_features is not None:
+            xa = audio_features.detach().to(self._act_dtype).contiguous()
+            assert xa.shape == (B, self.dims.n_audio_ctx, self.dims.n_audio_state), "incorrect audio feature shape"
+        else:
+            mel = mel.float().contiguous()
+        dev = xa.device if xa is not None else mel.device
         tokens = tokens.to(torch.int64).contiguous()
         targets = targets.to(torch.int64).contiguous()
         text_len = text_len.to(torch.int32).contiguous()
-        ws = self._ws(B, S, 1)
+        ws = self._ws(B, S, N.MODE_TRAIN_DEC if xa is not None else N.MODE_TRAIN)
         if loss_out is None:
-            loss_out = torch.zeros(1, device=mel.device, dtype=torch.float32)
-        logits = torch.empty(B, S, self.dims.n_vocab + 1, device=mel.device, dtype=torch.float32) if return_logits else None
+            loss_out = torch.zeros(1, device=dev, dtype=torch.float32)
+        logits = torch.empty(B, S, self.dims.n_vocab + 1, device=dev, dtype=torch.float32) if return_logits else None
         ev = None
         if segment_events is not None:
             assert len(segment_events) == len(self._segments)
@@ -947,6 +1108,19 @@ class OLMoASR(nn.Module):
                 raise N.NativeError("segment_events must be recorded-once torch.cuda.Event objects (null HIP event handle)")
             ev = (C.c_void_p * len(segment_events))(*handles)
         self._sync_trainable()
+        if xa is not None:
+            span_h = None
+            if span is not None and span is not False:
+                span_h = self.supervised_span(targets, text_len) if span is True else torch.as_tensor(span, dtype=torch.int32, device="cpu")
+                span_h = span_h.to(torch.int32).contiguous()
+                assert span_h.numel() == B and not span_h.is_cuda
+            with torch.cuda.device(dev):
+                N.check(N.lib().oasr_train_dec_fwd_bwd(self._ctx, N.ptr(xa), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
+                                                       None if span_h is None else C.c_void_p(span_h.data_ptr()),
+                                                       int(span_forward is None or bool(span_forward)), B, S, float(loss_scale),
+                                                       1.0 / accumulation_steps, N.ptr(loss_out), int(accumulate_loss), ev, N.ptr(ws),
+                                                       ws.numel(), N.stream_ptr()), "oasr_train_dec_fwd_bwd")
+            return loss_out, None
         if span is not None and span is not False:
             if return_logits or text_ctx is not None:
                 raise ValueError("span= cannot be combined with return_logits / text_ctx")
