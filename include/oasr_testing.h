@@ -48,6 +48,16 @@ int oasr_xcd_offsets_ok_debug(const int64_t* layer0, long long lstride, long lon
 int oasr_attention_set_pingpong(int on);
 int oasr_gemm_set_stagger(int sleeps, int phases); /* experiments: first-wave phase stagger of the 256x256 kernel (0 = off) */
 int oasr_gemm_force_general(int on); /* tests: route every GEMM through the register-staged general kernel */
+/* tests: oasr_gemm with the launch options only the engine sets (csrc/kernels.h GemmArgs): colsum_scratch -- fp32 [2 * ceil(M/256)][N] partial
+ * rows for the fused column sums instead of atomics; atomic_on_pp -- split-K / atomic output on the 256x256 ping-pong kernel (M, N % 256 == 0);
+ * raster_gm -- tile rows per L2 group (0 = default); stagger, stagger_phases -- first-wave stagger of the ping-pong kernel (0 = the automatic rule). */
+int oasr_test_gemm(const oasr_gemm_args* a, float* colsum_scratch, int atomic_on_pp, int raster_gm, int stagger, int stagger_phases, void* stream);
+/* tests: which kernels ran.  One text line per GEMM launch since oasr_profile_gemm(1), in launch order (oasr_profile_gemm_collect clears them):
+ * "symbol\tM\tN\tK\tta\ttb\tflags\tsplit_k\tatomic\tatomic_on_pp\tscratch\tstagger\tstagger_phases\tpersistent\tlane\n" -- flags: the epilogue flag word
+ * of csrc/gemm.hip (EPI_BIAS = 1, RESID 2, U 4, UDERIV 8, PRE 16, OUT 32, GELU 64, DERIV 128, POS 256, SCALE 512, NT_ST 1024, NT_LD 2048); scratch: a
+ * colsum_scratch came with colsum (the fused kernels then write partial rows instead of atomics); stagger: as the launch carried it (automatic rule applied); persistent: ping-pong kernel launched with
+ * one workgroup per CU.  Returns the number of records (< 0: `cap` bytes do not hold them).  Does not synchronise. */
+int oasr_profile_gemm_records(char* buf, int cap);
 int oasr_profile_gemm_collect(double* ms4, double* flops4, int64_t* count4, char* by_symbol /* "symbol\tlaunches\tms\tflops\n"... or NULL */, int cap);
 int oasr_probe_lds_oob(const void* src_u16 /*[512]*/, void* dst_u16 /*[512]*/, void* stream);
 int oasr_probe_tr16(const void* src_bf16 /*[16][64]*/, void* dst_bf16 /*[64 lanes][4]*/, void* stream);

@@ -107,6 +107,8 @@ def _declare(lib):
         "oasr_grad_sumsq_range": (i32, [vp, i64, i64, vp, vp, vp]),
         "oasr_optim_step_range": (i32, [vp, i64, i64, vp, vp, vp, f32, f32, f32, f32, f32, f32, f32, i64, vp]),
         "oasr_gemm": (i32, [C.POINTER(GemmArgs), vp]),
+        "oasr_test_gemm": (i32, [C.POINTER(GemmArgs), vp, i32, i32, i32, i32, vp]),
+        "oasr_profile_gemm_records": (i32, [C.c_char_p, i32]),
         "oasr_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, vp]),
         "oasr_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
         "oasr_attention_fwd": (i32, [C.POINTER(AttnArgs), vp]),

@@ -23,9 +23,9 @@ static OperandView to_view(const oasr_operand& o) {
   return OperandView{(const bf16_t*)o.ptr, (long)o.ld, o.rpb, (long)o.bstride, o.lead, o.kvalid, o.trail_from};
 }
 
-extern "C" int oasr_gemm(const oasr_gemm_args* a, void* stream) {
+static int to_gemm(const oasr_gemm_args* a, GemmArgs& g) {
   OASR_REQUIRE(a, "oasr_gemm: null args");
-  GemmArgs g = gemm_defaults();
+  g = gemm_defaults();
   g.A = to_view(a->A);
   g.B = to_view(a->B);
   g.M = a->M;
@@ -53,6 +53,26 @@ extern "C" int oasr_gemm(const oasr_gemm_args* a, void* stream) {
   g.split_k = a->split_k < 1 ? 1 : a->split_k;
   g.dgelu_deriv = a->dgelu_deriv;
   OASR_REQUIRE(a->act >= 0 && a->act <= 2, "oasr_gemm: act must be 0 (none), 1 (GELU) or 2 (GELU, out_pre = GELU')");
+  return OASR_OK;
+}
+
+extern "C" int oasr_gemm(const oasr_gemm_args* a, void* stream) {
+  GemmArgs g;
+  const int rc = to_gemm(a, g);
+  return rc ? rc : launch_gemm(g, (hipStream_t)stream);
+}
+
+// tests (include/oasr_testing.h): oasr_gemm plus the launch options only the engine sets
+extern "C" int oasr_test_gemm(const oasr_gemm_args* a, float* colsum_scratch, int atomic_on_pp, int raster_gm, int stagger, int stagger_phases,
+                              void* stream) {
+  GemmArgs g;
+  const int rc = to_gemm(a, g);
+  if (rc) return rc;
+  g.colsum_scratch = colsum_scratch;
+  g.atomic_on_pp = atomic_on_pp;
+  g.raster_gm = raster_gm;
+  g.stagger = stagger;
+  g.stagger_phases = stagger_phases;
   return launch_gemm(g, (hipStream_t)stream);
 }
 
@@ -94,6 +114,11 @@ extern "C" int oasr_gemm_force_general(int on) {
   OASR_HOOK_GATE("oasr_gemm_force_general");
   gemm_force_general(on);
   return OASR_OK;
+}
+extern "C" int oasr_profile_gemm_records(char* buf, int cap) {
+  const int n = gemm_profile_records(buf, cap);
+  OASR_REQUIRE(n >= 0, "oasr_profile_gemm_records: %d bytes do not hold the launch records", cap);
+  return n;
 }
 extern "C" int oasr_profile_gemm_collect(double* ms4, double* flops4, int64_t* count4, char* by_symbol, int cap) {
   OASR_REQUIRE(ms4 && flops4 && count4, "profile_collect: null");

@@ -44,6 +44,8 @@ struct GemmProfile {
     int M = 0, N = 0, K = 0, epi = 0;  // shape + epilogue summary (bit 0 bias, 1 residual, 2 GELU, 3 GELU' input, 4 colsum, 5 atomic/split-K)
     int lane = 0;                      // 0 = the caller's stream with the chip to itself, 1 = a lowest-priority side stream of the span step,
                                        // 2 = the caller's stream while side-stream filler is in flight (gemm_profile_lane)
+    // what the launch was, for tests that must know which kernel ran and how (gemm_profile_records)
+    int ta = 0, tb = 0, flags = 0, split_k = 1, atomic = 0, atomic_on_pp = 0, scratch = 0, stagger = 0, stagger_phases = 0, persistent = 0;
   };
   std::vector<Rec> recs;
   int lane = 0;
@@ -452,7 +454,7 @@ enum : unsigned {
   EPI_BIAS = 1, EPI_RESID = 2, EPI_U = 4, EPI_UDERIV = 8, EPI_PRE = 16, EPI_OUT = 32, EPI_GELU = 64, EPI_DERIV = 128, EPI_POS = 256,
   EPI_SCALE = 512, EPI_NT_ST = 1024, EPI_NT_LD = 2048, EPI_PARTIAL = 4096
 };
-__device__ __forceinline__ unsigned epi_flags_of(const GemmArgs& p, bool partial) {
+__host__ __device__ __forceinline__ unsigned epi_flags_of(const GemmArgs& p, bool partial) {
   return (p.bias ? EPI_BIAS : 0) | (p.resid ? EPI_RESID : 0) | (p.dgelu_u ? EPI_U : 0) | (p.dgelu_deriv ? EPI_UDERIV : 0) |
          (p.out_pre ? EPI_PRE : 0) | (p.out ? EPI_OUT : 0) | (p.act != 0 ? EPI_GELU : 0) | (p.act == 2 ? EPI_DERIV : 0) |
          (p.pos ? EPI_POS : 0) | (p.alpha != 1.0f ? EPI_SCALE : 0) | ((p.epi_flags & 1) ? EPI_NT_ST : 0) |
@@ -468,6 +470,23 @@ constexpr unsigned EPI_MODES[] = {
     EPI_OUT | EPI_U | EPI_UDERIV,                         // dgrad through GELU (saved derivative)
 };
 constexpr int EPI_NMODES = (int)(sizeof(EPI_MODES) / sizeof(EPI_MODES[0]));
+
+// profile record of one launch: kind = layout index 2*ta + tb, the epilogue summary bench.py's by-shape lines print, and the launch facts
+GemmProfile::Rec gemm_rec(const GemmArgs& a, double flops, const char* name, bool persistent = false) {
+  GemmProfile::Rec r{(a.ta ? 2 : 0) + (a.tb ? 1 : 0), flops, name, a.M, a.N, a.K,
+                     (a.bias ? 1 : 0) | (a.resid ? 2 : 0) | (a.act ? 4 : 0) | (a.dgelu_u ? 8 : 0) | (a.colsum ? 16 : 0) | (a.atomic ? 32 : 0)};
+  r.ta = a.ta ? 1 : 0;
+  r.tb = a.tb ? 1 : 0;
+  r.flags = (int)epi_flags_of(a, false);
+  r.split_k = a.split_k;
+  r.atomic = a.atomic;
+  r.atomic_on_pp = a.atomic_on_pp;
+  r.scratch = (a.colsum && a.colsum_scratch) ? 1 : 0;
+  r.stagger = a.stagger;
+  r.stagger_phases = a.stagger_phases;
+  r.persistent = persistent ? 1 : 0;
+  return r;
+}
 
 // stg: this wave's staging tile, 8-row groups of 1 KiB placed GS bytes apart; bias_lds: 64 floats of wave-private LDS.
 template <bool CSUM, int GS, bool PF, int MODE>
@@ -1263,8 +1282,7 @@ int launch_fast_cfg(const GemmArgs& a, hipStream_t stream) {
     auto tf = [](bool b) { return b ? "true" : "false"; };
     static const std::string name = std::string("oasr_gemm_fast_kernel<") + tf(TA) + ", " + tf(TB) + ", " + std::to_string(FBN) + ", " +
                                     std::to_string(NWN) + ", " + std::to_string(NSTAGE) + ", " + tf(SWAP) + ", " + tf(CSUM) + ">";
-    g_prof.push({(TA ? 2 : 0) + (TB ? 1 : 0), 2.0 * (double)a.M * (double)a.N * (double)a.K, name.c_str(), a.M, a.N, a.K,
-                           (a.bias ? 1 : 0) | (a.resid ? 2 : 0) | (a.act ? 4 : 0) | (a.dgelu_u ? 8 : 0) | (a.colsum ? 16 : 0) | (a.atomic ? 32 : 0)});
+    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * (double)a.N * (double)a.K, name.c_str()));
     OASR_CHECK_HIP(hipEventRecord(e0, stream));
   }
   hipLaunchKernelGGL((oasr_gemm_fast_kernel<TA, TB, FBN, NWN, NSTAGE, SWAP, CSUM>), grid, dim3(128 * NWN), lds, stream, a);
@@ -1321,8 +1339,7 @@ int launch_pp_variant(const GemmArgs& a, hipStream_t stream) {
     auto tf = [](bool b) { return b ? "true" : "false"; };
     static const std::string name = std::string("oasr_gemm_pp_kernel<") + tf(TA) + ", " + tf(TB) + ", " + tf(SWAP) + ", " + tf(CSUM) +
                                     ", " + std::to_string(DMA) + ">";
-    g_prof.push({(TA ? 2 : 0) + (TB ? 1 : 0), 2.0 * (double)a.M * (double)a.N * (double)a.K, name.c_str(), a.M, a.N, a.K,
-                           (a.bias ? 1 : 0) | (a.resid ? 2 : 0) | (a.act ? 4 : 0) | (a.dgelu_u ? 8 : 0) | (a.colsum ? 16 : 0) | (a.atomic ? 32 : 0)});
+    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * (double)a.N * (double)a.K, name.c_str(), can_persist && want == 1));
     OASR_CHECK_HIP(hipEventRecord(e0, stream));
   }
   hipLaunchKernelGGL((oasr_gemm_pp_kernel<TA, TB, SWAP, CSUM, DMA>), grid, dim3(512), lds, stream, pa);
@@ -1377,7 +1394,7 @@ int launch_skinny(const GemmArgs& a, hipStream_t stream) {
     }
     e0 = g_prof.events[2 * idx];
     e1 = g_prof.events[2 * idx + 1];
-    g_prof.push({0, 2.0 * (double)a.M * (double)a.N * (double)a.K, a.M <= 32 ? "gemm_skinny_kernel<1>" : "gemm_skinny_kernel<2>"});
+    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * (double)a.N * (double)a.K, a.M <= 32 ? "gemm_skinny_kernel<1>" : "gemm_skinny_kernel<2>"));
     OASR_CHECK_HIP(hipEventRecord(e0, stream));
   }
   if (a.M <= 32)
@@ -1453,7 +1470,7 @@ int launch_t(const GemmArgs& a, hipStream_t stream) {
     const double kk = a.A.rpb ? (double)(a.ta ? a.K : a.A.kvalid) : (double)a.K;
     const double nn = (a.B.rpb && a.tb) ? (double)a.B.kvalid : (double)a.N;
     static const std::string name = std::string("gemm_kernel<") + (TA ? "true" : "false") + ", " + (TB ? "true" : "false") + ">";
-    g_prof.push({(TA ? 2 : 0) + (TB ? 1 : 0), 2.0 * (double)a.M * nn * kk, name.c_str()});
+    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * nn * kk, name.c_str()));
     OASR_CHECK_HIP(hipEventRecord(e0, stream));
   }
   hipLaunchKernelGGL((gemm_kernel<TA, TB>), grid, dim3(256), lds, stream, a);
@@ -1501,6 +1518,9 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   OASR_REQUIRE((a.N % 4) == 0, "gemm: N (%d) must be a multiple of 4", a.N);
   OASR_REQUIRE((a.A.ld % 8) == 0 && (a.B.ld % 8) == 0, "gemm: operand leading dims must be multiples of 8 (16-byte loads)");
   OASR_REQUIRE(a.ta || (a.K % 8) == 0 || a.A.rpb, "gemm: K must be a multiple of 8 for k-contiguous A");
+  // (a k-contiguous operand is fetched in 16-byte chunks that are bounds-checked at their first element: a last chunk that straddles K
+  //  would bring in up to 7 elements past it, and NaN / Inf there survives the other operand's zero fill)
+  OASR_REQUIRE(a.tb || (a.K % 8) == 0 || a.B.rpb, "gemm: K must be a multiple of 8 for k-contiguous B");
   OASR_REQUIRE(!a.ta || (a.M % 8) == 0 || true, "gemm");
   OASR_REQUIRE(a.split_k >= 1, "gemm: split_k");
   OASR_REQUIRE(a.split_k == 1 || (a.atomic && a.out_f32 && !a.out && !a.out_pre), "gemm: split_k > 1 needs atomic fp32 output only");
@@ -1595,6 +1615,22 @@ int gemm_profile_collect(double ms[4], double flops[4], long count[4], char* by_
   }
   g_prof.recs.clear();
   return OASR_OK;
+}
+
+// Tests: one text line per launch recorded since gemm_profile_enable(1) (collect() clears them), in launch order:
+// "symbol\tM\tN\tK\tta\ttb\tepilogue flag word\tsplit_k\tatomic\tatomic_on_pp\tcolsum_scratch used\tstagger\tstagger_phases\tpersistent\tlane\n".
+// Does not synchronise.  Returns the number of records, or -1 when `cap` bytes do not hold them.
+int gemm_profile_records(char* buf, int cap) {
+  std::string out;
+  for (const GemmProfile::Rec& r : g_prof.recs) {
+    char line[512];
+    snprintf(line, sizeof(line), "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", r.name, r.M, r.N, r.K, r.ta, r.tb, r.flags, r.split_k,
+             r.atomic, r.atomic_on_pp, r.scratch, r.stagger, r.stagger_phases, r.persistent, r.lane);
+    out += line;
+  }
+  if (!buf || (size_t)cap <= out.size()) return -1;
+  memcpy(buf, out.c_str(), out.size() + 1);
+  return (int)g_prof.recs.size();
 }
 
 void gemm_force_general(int on) {

@@ -80,6 +80,7 @@ void gemm_force_general(int on);  // tests: disable the direct-to-LDS fast path
 void gemm_set_variant(int dma_in_mma);  // experiments: ping-pong kernel issues its DMA pieces between the MFMAs
 void gemm_set_stagger(int sleeps, int phases);  // experiments: first-wave phase stagger of the ping-pong kernel
 int gemm_profile_collect(double ms[4], double flops[4], long count[4], char* by_symbol, int cap);
+int gemm_profile_records(char* buf, int cap);  // tests: one text line per recorded launch (kernel symbol, shape, layout, epilogue flags, launch options)
 template <typename T>
 static inline GemmArgsT<T> gemm_defaults_t() {
   GemmArgsT<T> g;

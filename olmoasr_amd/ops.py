@@ -15,8 +15,10 @@ def _op(t, ld=None, rpb=0, bstride=0, lead=0, kvalid=0, trail_from=0):
 
 def gemm(A, B, M, N_, K, *, ta=False, tb=False, a_view=None, b_view=None, bias=None, act=0, pos=None, pos_period=0,
          dgelu_u=None, resid=None, out=None, out_pre=None, ldc=None, out_f32=None, beta=0.0, atomic=False, split_k=1,
-         alpha=1.0, colsum=None, dgelu_deriv=False):
-    """C[M,N] = epilogue(alpha * sum_k A(m,k) B(n,k)); see olmoasr_amd/csrc/kernels.h GemmArgs."""
+         alpha=1.0, colsum=None, dgelu_deriv=False, ldc32=None, colsum_scratch=None, atomic_on_pp=None, raster_gm=None, stagger=None,
+         stagger_phases=None):
+    """C[M,N] = epilogue(alpha * sum_k A(m,k) B(n,k)); see olmoasr_amd/csrc/kernels.h GemmArgs.  The last five keywords are the launch
+    options only the engine sets; giving any of them routes the call through oasr_test_gemm (include/oasr_testing.h)."""
     g = N.GemmArgs()
     g.A = a_view if a_view is not None else _op(A)
     g.B = b_view if b_view is not None else _op(B)
@@ -33,11 +35,30 @@ def gemm(A, B, M, N_, K, *, ta=False, tb=False, a_view=None, b_view=None, bias=N
     g.out_pre = out_pre.data_ptr() if out_pre is not None else None
     g.ldc = ldc if ldc is not None else (out.stride(0) if out is not None else (out_pre.stride(0) if out_pre is not None else 0))
     g.out_f32 = out_f32.data_ptr() if out_f32 is not None else None
-    g.ldc32 = out_f32.stride(0) if out_f32 is not None else 0
+    g.ldc32 = ldc32 if ldc32 is not None else (out_f32.stride(0) if out_f32 is not None else 0)
     g.beta, g.atomic, g.split_k = beta, int(atomic), split_k
     g.colsum = colsum.data_ptr() if colsum is not None else None
     g.dgelu_deriv = int(dgelu_deriv)
-    N.check(N.lib().oasr_gemm(C.byref(g), N.stream_ptr()), "oasr_gemm")
+    engine_only = (colsum_scratch, atomic_on_pp, raster_gm, stagger, stagger_phases)
+    if all(x is None for x in engine_only):
+        N.check(N.lib().oasr_gemm(C.byref(g), N.stream_ptr()), "oasr_gemm")
+    else:
+        N.check(N.lib().oasr_test_gemm(C.byref(g), N.ptr(colsum_scratch), int(atomic_on_pp or 0), int(raster_gm or 0), int(stagger or 0),
+                                       int(stagger_phases or 0), N.stream_ptr()), "oasr_test_gemm")
+
+
+def gemm_launch_records():
+    """The GEMM launches since ``lib().oasr_profile_gemm(1)`` as dicts (include/oasr_testing.h: oasr_profile_gemm_records)."""
+    buf = C.create_string_buffer(1 << 22)
+    n = N.lib().oasr_profile_gemm_records(buf, len(buf))
+    N.check(0 if n >= 0 else n, "oasr_profile_gemm_records")
+    keys = ("M", "N", "K", "ta", "tb", "flags", "split_k", "atomic", "atomic_on_pp", "scratch", "stagger", "stagger_phases", "persistent", "lane")
+    recs = []
+    for line in buf.value.decode().splitlines():
+        f = line.split("\t")
+        recs.append(dict(zip(keys, map(int, f[1:])), symbol=f[0]))
+    assert len(recs) == n
+    return recs
 
 
 def layernorm_fwd(x, gamma, beta):
