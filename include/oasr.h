@@ -35,7 +35,7 @@ typedef struct oasr_dims {
 const char* oasr_last_error(void);
 /* ABI version: 100 * major + minor.  Structs passed by pointer (oasr_attn_args, oasr_gemm_args) only grow at the end and only with a
  * major bump; olmoasr_amd/_native.py refuses to drive a library whose version differs from OASR_ABI_VERSION. */
-#define OASR_ABI_VERSION 214
+#define OASR_ABI_VERSION 215
 int oasr_version(void);
 
 /* ---- log-mel front end: whisper.audio.log_mel_spectrogram as called at train_timestamps.py:196,214 and
@@ -232,7 +232,12 @@ int oasr_set_trainable(oasr_ctx*, const uint8_t* mask, int n_params);
 
 /* scaler.unscale_ + clip_grad_norm_(max_norm) + AdamW.step + bf16 shadow refresh (train_timestamps.py:1509-1512).
  * step is 1-based.  stats_out (device f32[2]): [0] = sum of squares of the SCALED grads, [1] = non-finite flag
- * (step skipped when nonzero, like GradScaler).  scratch: >= 8192 bytes device. */
+ * (step skipped when nonzero, like GradScaler).  scratch: >= 8192 bytes device.
+ * Overflow of the norm: the squares are formed in fp32 (their sum in double), so a FINITE scaled gradient above sqrt(FLT_MAX) = 1.8e19 makes
+ * stats[0] +inf without raising the non-finite flag.  The clip coefficient is then max_norm / inf = 0: the step runs with every gradient taken
+ * as zero -- moments decay, weight decay and the momentum term still apply -- where torch would run a clipped step.  Loss scaling keeps
+ * healthy gradients twelve orders of magnitude below that; a caller that can see such values should treat stats[0] == inf as found_inf.
+ * The range and run-table forms (oasr_grad_sumsq_range, frozen tensors) behave the same.  Pinned by tests/test_gpu_optimizer_planted.py. */
 int oasr_optim_step(oasr_ctx*, float inv_loss_scale, float max_grad_norm, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int64_t step, float* stats_out, void* scratch, void* stream);
 

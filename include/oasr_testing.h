@@ -67,6 +67,39 @@ int oasr_probe_tr16(const void* src_bf16 /*[16][64]*/, void* dst_bf16 /*[64 lane
 int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                           int64_t* targets_rows_out, int64_t* active_rows_out, void* stream);
 
+/* tests (tests/test_gpu_glue_ops.py): the glue launchers of csrc/kernels.h as unit operators -- the kernels between the GEMMs and the attention
+ * that the training step reaches only inside a whole-model run.  Contracts: csrc/kernels.h, argument for argument.  dtype = OASR_DTYPE_BF16 (the
+ * production kernel) / OASR_DTYPE_F32 (the fp32 validation overload): the type of every `void*` activation; float* arguments are fp32 in both.
+ * They change no process state, so they need no OASR_TESTING_HOOKS opt-in.
+ *   embedding_fwd  x[row(b, s)] = E[tok[b, s]] + pos[s] (ids outside [0, n_embed): pos[s] alone); rows: optional chunk-row table [B][OASR_ROWTAB]
+ *   embedding_bwd  dE[tok] += dx (not for pad_id / ids outside the table), dpos[s] += sum_b dx; dE or dpos may be null; span (with rows):
+ *                  positions s >= span[b] are not read
+ *   colsum         out[n] += sum_m x[m][n], x [M][ld], columns [0, ncols)
+ *   conv2_col2im_dgelu  dpre1[b, t] = gelu'(u1[b, t]) * (the conv2 windows dA [B*T1/2][3][d] folded onto input row t)
+ *   conv1_col2im_mel    dmel f32 [B][n_mels][T1] = the conv1 windows dcol [B*T1][256] folded onto the frames
+ *   mel_to_time_major   mel f32 [B][n_mels][T] -> [B][T][n_mels]; clip_max (optional [B]): max(x, clip_max[b] - 8), (x + 4) / 4 on the way
+ *   pack_conv_weight    w f32 [co][ci][3] -> [co][ldk], k = kk * ci + c, zero padded;  unpack_conv_grad: dw[co][ci][3] += g [co][ldk]
+ *   pack_embedding      e f32 [rows][d] -> bf16 [rows_pad][d], rows past `rows` zero
+ *   dgelu_mul           out = dy * gelu'(u) over n elements (bf16: n % 8 == 0)
+ *   dlogits_from_f32    src f32 [rows][V] -> [rows][ld], columns >= V zero;  logits_to_f32: [rows][ld] -> f32 [rows][V]
+ *   layernorm_bwd       oasr_layernorm_bwd with dsum (optional [d]: += column sums of the stored dx) and nullable dgamma / dbeta */
+int oasr_test_embedding_fwd(const int64_t* tok, const float* E, const float* pos, void* x, int dtype, int B, int S, int d, int64_t n_embed,
+                            const int32_t* rows, void* stream);
+int oasr_test_embedding_bwd(const int64_t* tok, const void* dx, int dtype, float* dE, float* dpos, int B, int S, int d, int64_t pad_id,
+                            int64_t n_embed, const int32_t* rows, const int32_t* span, void* stream);
+int oasr_test_colsum(const void* x, int dtype, int64_t ld, int64_t M, int ncols, float* out, void* stream);
+int oasr_test_conv2_col2im_dgelu(const void* dA, const void* u1, void* dpre1, int dtype, int B, int T1, int d, void* stream);
+int oasr_test_conv1_col2im_mel(const void* dcol, int dtype, float* dmel, int B, int T1, int n_mels, void* stream);
+int oasr_test_mel_to_time_major(const float* mel, void* out, int dtype, int B, int n_mels, int T, const float* clip_max, void* stream);
+int oasr_test_pack_conv_weight(const float* w, void* dst, int dtype, int co, int ci, int ldk, void* stream);
+int oasr_test_unpack_conv_grad(const float* g, float* dw, int co, int ci, int ldk, void* stream);
+int oasr_test_pack_embedding(const float* e, void* dst, int rows, int rows_pad, int d, void* stream);
+int oasr_test_dgelu_mul(const void* dy, const void* u, void* out, int dtype, int64_t n, void* stream);
+int oasr_test_dlogits_from_f32(const float* src, int V, int64_t rows, int64_t ld, void* dst, int dtype, void* stream);
+int oasr_test_logits_to_f32(const void* logits, int dtype, int64_t ld, int64_t rows, int V, float* out, void* stream);
+int oasr_test_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dres, void* dx,
+                            float* dgamma, float* dbeta, float* dsum, int dtype, int64_t rows, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

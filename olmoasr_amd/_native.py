@@ -44,7 +44,7 @@ class AttnArgs(C.Structure):
                 ("q_rows", C.c_void_p), ("k_rows", C.c_void_p), ("q_span", C.c_void_p)]
 
 
-ABI_VERSION = 214  # include/oasr.h: OASR_ABI_VERSION (214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
+ABI_VERSION = 215  # include/oasr.h: OASR_ABI_VERSION (215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
 ROWTAB = 16        # include/oasr.h: OASR_ROWTAB (entries per sample of a chunk-row table)
@@ -94,6 +94,19 @@ def _declare(lib):
         "oasr_log_mel_raw": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
         "oasr_sizeof_attn_args": (sz, []),
         "oasr_test_span_tables": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "oasr_test_embedding_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp]),
+        "oasr_test_embedding_bwd": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i64, i64, vp, vp, vp]),
+        "oasr_test_colsum": (i32, [vp, i32, i64, i64, i32, vp, vp]),
+        "oasr_test_conv2_col2im_dgelu": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+        "oasr_test_conv1_col2im_mel": (i32, [vp, i32, vp, i32, i32, i32, vp]),
+        "oasr_test_mel_to_time_major": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+        "oasr_test_pack_conv_weight": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+        "oasr_test_unpack_conv_grad": (i32, [vp, vp, i32, i32, i32, vp]),
+        "oasr_test_pack_embedding": (i32, [vp, vp, i32, i32, i32, vp]),
+        "oasr_test_dgelu_mul": (i32, [vp, vp, vp, i32, i64, vp]),
+        "oasr_test_dlogits_from_f32": (i32, [vp, i32, i64, i64, vp, i32, vp]),
+        "oasr_test_logits_to_f32": (i32, [vp, i32, i64, i64, i32, vp, vp]),
+        "oasr_test_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp]),
         "oasr_train_fwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_train_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_zero_grad": (i32, [vp, vp]),

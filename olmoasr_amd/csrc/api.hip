@@ -206,6 +206,89 @@ extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, con
   return rc;
 }
 
+// ---- tests (include/oasr_testing.h): the glue launchers of kernels.h as unit operators.  Thin: the launchers check their own arguments;
+// dtype selects the bf16 production kernel or the fp32 validation overload, as in oasr_attention_scores. --------------------------------
+#define OASR_TEST_DTYPE(name) \
+  OASR_REQUIRE(dtype == OASR_DTYPE_BF16 || dtype == OASR_DTYPE_F32, name ": dtype %d (0 = bf16, 1 = fp32 activations)", dtype)
+
+extern "C" int oasr_test_embedding_fwd(const int64_t* tok, const float* E, const float* pos, void* x, int dtype, int B, int S, int d,
+                                       int64_t n_embed, const int32_t* rows, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_embedding_fwd");
+  if (dtype == OASR_DTYPE_BF16) return launch_embedding_fwd(tok, E, pos, (bf16_t*)x, B, S, d, (long)n_embed, (hipStream_t)stream, rows);
+  return launch_embedding_fwd(tok, E, pos, (float*)x, B, S, d, (long)n_embed, (hipStream_t)stream, rows);
+}
+extern "C" int oasr_test_embedding_bwd(const int64_t* tok, const void* dx, int dtype, float* dE, float* dpos, int B, int S, int d, int64_t pad_id,
+                                       int64_t n_embed, const int32_t* rows, const int32_t* span, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_embedding_bwd");
+  OASR_REQUIRE(!span || rows, "oasr_test_embedding_bwd: span comes with a chunk-row table");
+  if (dtype == OASR_DTYPE_BF16)
+    return launch_embedding_bwd(tok, (const bf16_t*)dx, dE, dpos, B, S, d, (long)pad_id, (long)n_embed, (hipStream_t)stream, rows, span);
+  return launch_embedding_bwd(tok, (const float*)dx, dE, dpos, B, S, d, (long)pad_id, (long)n_embed, (hipStream_t)stream, rows, span);
+}
+extern "C" int oasr_test_colsum(const void* x, int dtype, int64_t ld, int64_t M, int ncols, float* out, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_colsum");
+  if (dtype == OASR_DTYPE_BF16) return launch_colsum_accum((const bf16_t*)x, (long)ld, (long)M, ncols, out, (hipStream_t)stream);
+  return launch_colsum_accum((const float*)x, (long)ld, (long)M, ncols, out, (hipStream_t)stream);
+}
+extern "C" int oasr_test_conv2_col2im_dgelu(const void* dA, const void* u1, void* dpre1, int dtype, int B, int T1, int d, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_conv2_col2im_dgelu");
+  OASR_REQUIRE(B > 0 && T1 > 0 && d > 0, "oasr_test_conv2_col2im_dgelu: bad shape (B=%d T1=%d d=%d)", B, T1, d);
+  if (dtype == OASR_DTYPE_BF16) return launch_conv2_col2im_dgelu((const bf16_t*)dA, (const bf16_t*)u1, (bf16_t*)dpre1, B, T1, d, (hipStream_t)stream);
+  return launch_conv2_col2im_dgelu((const float*)dA, (const float*)u1, (float*)dpre1, B, T1, d, (hipStream_t)stream);
+}
+extern "C" int oasr_test_conv1_col2im_mel(const void* dcol, int dtype, float* dmel, int B, int T1, int n_mels, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_conv1_col2im_mel");
+  if (dtype == OASR_DTYPE_BF16) return launch_conv1_col2im_mel((const bf16_t*)dcol, dmel, B, T1, n_mels, (hipStream_t)stream);
+  return launch_conv1_col2im_mel((const float*)dcol, dmel, B, T1, n_mels, (hipStream_t)stream);
+}
+extern "C" int oasr_test_mel_to_time_major(const float* mel, void* out, int dtype, int B, int n_mels, int T, const float* clip_max, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_mel_to_time_major");
+  OASR_REQUIRE(B > 0 && n_mels > 0 && T > 0, "oasr_test_mel_to_time_major: bad shape (B=%d n_mels=%d T=%d)", B, n_mels, T);
+  if (dtype == OASR_DTYPE_BF16) return launch_mel_to_time_major(mel, (bf16_t*)out, B, n_mels, T, (hipStream_t)stream, clip_max);
+  return launch_mel_to_time_major(mel, (float*)out, B, n_mels, T, (hipStream_t)stream, clip_max);
+}
+extern "C" int oasr_test_pack_conv_weight(const float* w, void* dst, int dtype, int co, int ci, int ldk, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_pack_conv_weight");
+  OASR_REQUIRE(co > 0 && ci > 0, "oasr_test_pack_conv_weight: bad shape (co=%d ci=%d)", co, ci);
+  if (dtype == OASR_DTYPE_BF16) return launch_pack_conv_weight(w, (bf16_t*)dst, co, ci, ldk, (hipStream_t)stream);
+  return launch_pack_conv_weight(w, (float*)dst, co, ci, ldk, (hipStream_t)stream);
+}
+extern "C" int oasr_test_unpack_conv_grad(const float* g, float* dw, int co, int ci, int ldk, void* stream) {
+  OASR_REQUIRE(co > 0 && ci > 0, "oasr_test_unpack_conv_grad: bad shape (co=%d ci=%d)", co, ci);
+  return launch_unpack_conv_grad(g, dw, co, ci, ldk, (hipStream_t)stream);
+}
+extern "C" int oasr_test_pack_embedding(const float* e, void* dst, int rows, int rows_pad, int d, void* stream) {
+  OASR_REQUIRE(rows > 0 && d > 0, "oasr_test_pack_embedding: bad shape (rows=%d d=%d)", rows, d);
+  return launch_pack_embedding(e, (bf16_t*)dst, rows, rows_pad, d, (hipStream_t)stream);
+}
+extern "C" int oasr_test_dgelu_mul(const void* dy, const void* u, void* out, int dtype, int64_t n, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_dgelu_mul");
+  OASR_REQUIRE(n > 0, "oasr_test_dgelu_mul: n = %lld", (long long)n);
+  if (dtype == OASR_DTYPE_BF16) return launch_dgelu_mul((const bf16_t*)dy, (const bf16_t*)u, (bf16_t*)out, (long)n, (hipStream_t)stream);
+  return launch_dgelu_mul((const float*)dy, (const float*)u, (float*)out, (long)n, (hipStream_t)stream);
+}
+extern "C" int oasr_test_dlogits_from_f32(const float* src, int V, int64_t rows, int64_t ld, void* dst, int dtype, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_dlogits_from_f32");
+  OASR_REQUIRE(rows > 0 && V > 0, "oasr_test_dlogits_from_f32: bad shape");
+  if (dtype == OASR_DTYPE_BF16) return launch_dlogits_from_f32(src, V, (long)rows, (long)ld, (bf16_t*)dst, (hipStream_t)stream);
+  return launch_dlogits_from_f32(src, V, (long)rows, (long)ld, (float*)dst, (hipStream_t)stream);
+}
+extern "C" int oasr_test_logits_to_f32(const void* logits, int dtype, int64_t ld, int64_t rows, int V, float* out, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_logits_to_f32");
+  OASR_REQUIRE(logits && out && rows > 0 && V > 0 && V <= ld, "oasr_test_logits_to_f32: bad args");
+  if (dtype == OASR_DTYPE_BF16) return launch_logits_to_f32((const bf16_t*)logits, (long)ld, (long)rows, V, out, (hipStream_t)stream);
+  return launch_logits_to_f32((const float*)logits, (long)ld, (long)rows, V, out, (hipStream_t)stream);
+}
+extern "C" int oasr_test_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dres,
+                                       void* dx, float* dgamma, float* dbeta, float* dsum, int dtype, int64_t rows, int d, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_layernorm_bwd");
+  if (dtype == OASR_DTYPE_BF16)
+    return launch_layernorm_bwd((const bf16_t*)dy, (const bf16_t*)x, gamma, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, dgamma, dbeta, dsum,
+                                (long)rows, d, (hipStream_t)stream);
+  return launch_layernorm_bwd((const float*)dy, (const float*)x, gamma, mean, rstd, (const float*)dres, (float*)dx, dgamma, dbeta, dsum, (long)rows, d,
+                              (hipStream_t)stream);
+}
+
 extern "C" int oasr_cross_entropy(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                                   int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream) {
   hipStream_t st = (hipStream_t)stream;

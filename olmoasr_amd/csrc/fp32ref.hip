@@ -22,7 +22,11 @@ inline unsigned grid_for(long work_items, int per_block = 256, int cap = 4096) {
 
 __device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float dgelu_exact(float x) {
-  return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * expf(-0.5f * x * x) * 0.3989422804014327f;
+  // Phi(x) through erfc on the negative side: 1 + erf(x / sqrt 2) cancels there (half of Phi's digits are gone at x = -3, all of them by
+  // x = -5.5), and Phi(x) + x pdf(x) is a difference of two small terms for x < 0 (tests/test_gpu_glue_ops.py holds each term to 4 * 2^-24)
+  const float z = x * 0.70710678118654752f;
+  const float cdf = x < 0.f ? 0.5f * erfcf(-z) : 0.5f * (1.0f + erff(z));
+  return cdf + x * expf(-0.5f * x * x) * 0.3989422804014327f;
 }
 
 // ---- GEMM ----------------------------------------------------------------------------------------------------

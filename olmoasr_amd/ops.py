@@ -345,3 +345,76 @@ def sample_tokens(logits, temperature, uniforms, *, history=None, n_history=None
                                        int(eot), int(no_timestamps), -1 if max_initial_index is None else int(max_initial_index),
                                        float(temperature), N.ptr(uniforms), N.ptr(tok), N.ptr(lp), N.stream_ptr()), "oasr_sample_tokens")
     return tok, lp
+
+
+# ---- unit operators of the glue kernels (include/oasr_testing.h: oasr_test_*; used by tests/test_gpu_glue_ops.py) -----------------------
+# Every wrapper takes the caller's own (possibly guard-banded, pre-filled) output tensors and passes base addresses through: nothing is
+# allocated or zeroed here, so a test sees exactly what the kernel wrote.  The activation dtype (bf16 / fp32) selects the kernel.
+def _dt(t):
+    assert t.dtype in (BF, torch.float32), t.dtype
+    return 0 if t.dtype == BF else 1
+
+
+def embedding_fwd_(tok, E, pos, x, n_embed, rows=None):
+    """x[row(b, s)] = E[tok[b, s]] + pos[s]; tok int64 [B, S]; x: the output allocation (bf16 or fp32), rows: chunk-row table or None."""
+    B, S = tok.shape
+    N.check(N.lib().oasr_test_embedding_fwd(N.ptr(tok), N.ptr(E), N.ptr(pos), N.ptr(x), _dt(x), B, S, E.shape[1], int(n_embed), N.ptr(rows),
+                                            N.stream_ptr()), "oasr_test_embedding_fwd")
+
+
+def embedding_bwd_(tok, dx, dE, dpos, pad_id, n_embed, d, rows=None, span=None):
+    """dE[tok] += dx, dpos[s] += sum_b dx (either may be None); dx: activation rows [*, d]."""
+    B, S = tok.shape
+    N.check(N.lib().oasr_test_embedding_bwd(N.ptr(tok), N.ptr(dx), _dt(dx), N.ptr(dE), N.ptr(dpos), B, S, d, int(pad_id), int(n_embed),
+                                            N.ptr(rows), N.ptr(span), N.stream_ptr()), "oasr_test_embedding_bwd")
+
+
+def colsum_(x, ld, M, ncols, out):
+    N.check(N.lib().oasr_test_colsum(N.ptr(x), _dt(x), ld, M, ncols, N.ptr(out), N.stream_ptr()), "oasr_test_colsum")
+
+
+def conv2_col2im_dgelu_(dA, u1, dpre1, B, T1, d):
+    assert dA.dtype == u1.dtype == dpre1.dtype
+    N.check(N.lib().oasr_test_conv2_col2im_dgelu(N.ptr(dA), N.ptr(u1), N.ptr(dpre1), _dt(dA), B, T1, d, N.stream_ptr()),
+            "oasr_test_conv2_col2im_dgelu")
+
+
+def conv1_col2im_mel_(dcol, dmel, B, T1, n_mels):
+    N.check(N.lib().oasr_test_conv1_col2im_mel(N.ptr(dcol), _dt(dcol), N.ptr(dmel), B, T1, n_mels, N.stream_ptr()), "oasr_test_conv1_col2im_mel")
+
+
+def mel_to_time_major_(mel, out, B, n_mels, T, clip_max=None):
+    N.check(N.lib().oasr_test_mel_to_time_major(N.ptr(mel), N.ptr(out), _dt(out), B, n_mels, T, N.ptr(clip_max), N.stream_ptr()),
+            "oasr_test_mel_to_time_major")
+
+
+def pack_conv_weight_(w, dst, co, ci, ldk):
+    N.check(N.lib().oasr_test_pack_conv_weight(N.ptr(w), N.ptr(dst), _dt(dst), co, ci, ldk, N.stream_ptr()), "oasr_test_pack_conv_weight")
+
+
+def unpack_conv_grad_(g, dw, co, ci, ldk):
+    N.check(N.lib().oasr_test_unpack_conv_grad(N.ptr(g), N.ptr(dw), co, ci, ldk, N.stream_ptr()), "oasr_test_unpack_conv_grad")
+
+
+def pack_embedding_(e, dst, rows, rows_pad, d):
+    N.check(N.lib().oasr_test_pack_embedding(N.ptr(e), N.ptr(dst), rows, rows_pad, d, N.stream_ptr()), "oasr_test_pack_embedding")
+
+
+def dgelu_mul_(dy, u, out, n):
+    assert dy.dtype == u.dtype == out.dtype
+    N.check(N.lib().oasr_test_dgelu_mul(N.ptr(dy), N.ptr(u), N.ptr(out), _dt(dy), n, N.stream_ptr()), "oasr_test_dgelu_mul")
+
+
+def dlogits_from_f32_(src, V, rows, ld, dst):
+    N.check(N.lib().oasr_test_dlogits_from_f32(N.ptr(src), V, rows, ld, N.ptr(dst), _dt(dst), N.stream_ptr()), "oasr_test_dlogits_from_f32")
+
+
+def logits_to_f32_(logits, ld, rows, V, out):
+    N.check(N.lib().oasr_test_logits_to_f32(N.ptr(logits), _dt(logits), ld, rows, V, N.ptr(out), N.stream_ptr()), "oasr_test_logits_to_f32")
+
+
+def layernorm_bwd_(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum):
+    """launch_layernorm_bwd as the engine calls it: dx written, dgamma / dbeta / dsum (each may be None) ACCUMULATED into the caller's tensors."""
+    rows, d = x.shape
+    N.check(N.lib().oasr_test_layernorm_bwd(N.ptr(dy), N.ptr(x), N.ptr(gamma), N.ptr(mean), N.ptr(rstd), N.ptr(dres), N.ptr(dx), N.ptr(dgamma),
+                                            N.ptr(dbeta), N.ptr(dsum), _dt(x), rows, d, N.stream_ptr()), "oasr_test_layernorm_bwd")
