@@ -291,6 +291,42 @@ int oasr_attention_bwd(const oasr_attn_args*, void* stream);
  * matrix; word-level timestamp alignment (whisper.timing.find_alignment, called from olmoasr/transcribe.py:410-419) reads it from the
  * cross-attention of the upper decoder layers. */
 int oasr_attention_scores(const oasr_attn_args*, int dtype, float* scores, void* stream);
+/* Word-timestamp alignment on the device (olmoasr_amd/timing.py::find_alignment = whisper.timing.find_alignment, the part after the
+ * decoder passes; csrc/align.hip).  Both operators add entry points only: OASR_ABI_VERSION is unchanged, and a binding checks
+ * oasr_sizeof_align_args like oasr_sizeof_attn_args.
+ *
+ * oasr_alignment_matrix: the per-layer score tensors qk[l] = f32 [H, n_tok, Tk], exactly as oasr_attention_scores wrote them (B = 1), are read
+ * IN PLACE -- head h of layer l takes part when bit h of head_mask[l] is set; no stacked copy is made, and unselected heads and frames
+ * >= n_frames are never read.  out f32 [n_tok, n_frames] (row stride ldo):
+ *     out[i, j] = mean over the selected heads h of  median_w( z_h[i, reflect(j - w/2 .. j + w/2)] )
+ *     z_h[i, j] = (p_h[i, j] - mean_i p_h[., j]) / std_i p_h[., j]        (population std over ALL n_tok rows)
+ *     p_h[i, .] = softmax over j < n_frames of qk_scale * qk_h[i, j]
+ * with w = medfilt_width (odd, 1 .. 15; 7 is whisper's), reflect padding -k -> k, F-1+k -> F-1-k, and NO filter when n_frames <= w / 2
+ * (median_filter's own rule).  1 <= n_frames <= Tk, 1 <= n_layers <= OASR_ALIGN_MAX_LAYERS, H <= 32.  fp32 throughout (the column sums in
+ * double), heads added in ascending (layer, head) order: deterministic.  A column of zero variance is outside the contract (NaN / inf).
+ * workspace: oasr_alignment_workspace_bytes(number of selected heads, n_tok, n_frames) bytes of device memory, contents irrelevant. */
+#define OASR_ALIGN_MAX_LAYERS 32
+typedef struct oasr_align_args {
+  const float* qk[OASR_ALIGN_MAX_LAYERS];
+  uint32_t head_mask[OASR_ALIGN_MAX_LAYERS];
+  int32_t n_layers, H, n_tok, Tk, n_frames, medfilt_width;
+  float qk_scale;
+  int32_t reserved;
+  float* out;
+  int64_t ldo;
+} oasr_align_args;
+size_t oasr_sizeof_align_args(void);
+size_t oasr_alignment_workspace_bytes(int n_selected_heads, int n_tok, int n_frames);
+int oasr_alignment_matrix(const oasr_align_args*, void* workspace, size_t workspace_bytes, void* stream);
+/* oasr_dtw: the monotonic alignment of rows (tokens) to columns (frames) of cost f32 [N, M] (row stride ld, so a row slice of the matrix
+ * above is passed as it is; negate != 0: of -cost), bit-identical to timing.py::dtw / whisper.timing.dtw: fp32 cost table with +inf borders,
+ * each cell x + min-choice in ONE fp32 add; diagonal only when strictly cheapest, else down only when strictly cheapest, else right; the
+ * path runs from (0, 0) to (N-1, M-1).  1 <= N <= 448 (n_text_ctx), 1 <= M <= 1500 (n_audio_ctx).  text_indices / time_indices: device
+ * int32, N + M - 1 entries each, of which the first *path_len (device int32) are written; everything stays on the device.  One workgroup;
+ * workspace: oasr_dtw_workspace_bytes(N, M) bytes of device memory, contents irrelevant (0 for N, M outside the range). */
+size_t oasr_dtw_workspace_bytes(int N, int M);
+int oasr_dtw(const float* cost, int64_t ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
+             void* workspace, size_t workspace_bytes, void* stream);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 int oasr_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);

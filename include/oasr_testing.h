@@ -100,6 +100,13 @@ int oasr_test_logits_to_f32(const void* logits, int dtype, int64_t ld, int64_t r
 int oasr_test_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dres, void* dx,
                             float* dgamma, float* dbeta, float* dsum, int dtype, int64_t rows, int d, void* stream);
 
+/* tests (CPU, tests/test_alignment_cpu.py): oasr_dtw's algorithm run on the HOST.  Shared with the kernel through csrc/dtw_core.h: the cell
+ * update, the skewed trace index and the 64-cell backtrace step.  The forward loop over anti-diagonals (one "thread" per row, two cost rows) is
+ * re-stated in csrc/dtw_host.cpp; the kernel's register prefetch of the costs and its LDS double buffer are covered by the GPU suite only.
+ * All pointers are host memory; workspace: oasr_dtw_workspace_bytes(N, M) bytes.  Touches no device. */
+int oasr_test_dtw_host(const float* cost, int64_t ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
+                       void* workspace);
+
 #ifdef __cplusplus
 }
 #endif

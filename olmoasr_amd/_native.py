@@ -44,6 +44,15 @@ class AttnArgs(C.Structure):
                 ("q_rows", C.c_void_p), ("k_rows", C.c_void_p), ("q_span", C.c_void_p)]
 
 
+class AlignArgs(C.Structure):  # include/oasr.h: oasr_align_args
+    MAX_LAYERS = 32  # OASR_ALIGN_MAX_LAYERS
+    _fields_ = [("qk", C.c_void_p * 32), ("head_mask", C.c_uint32 * 32), ("n_layers", C.c_int32), ("H", C.c_int32), ("n_tok", C.c_int32),
+                ("Tk", C.c_int32), ("n_frames", C.c_int32), ("medfilt_width", C.c_int32), ("qk_scale", C.c_float), ("reserved", C.c_int32),
+                ("out", C.c_void_p), ("ldo", C.c_int64)]
+
+
+DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_audio_ctx
+# The word-timestamp operators (oasr_alignment_matrix, oasr_dtw, oasr_test_dtw_host) add entry points without a new ABI generation: a library built before them is refused by the oasr_sizeof_align_args check in lib().
 ABI_VERSION = 215  # include/oasr.h: OASR_ABI_VERSION (215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
@@ -127,6 +136,12 @@ def _declare(lib):
         "oasr_attention_fwd": (i32, [C.POINTER(AttnArgs), vp]),
         "oasr_attention_bwd": (i32, [C.POINTER(AttnArgs), vp]),
         "oasr_attention_scores": (i32, [C.POINTER(AttnArgs), i32, vp, vp]),
+        "oasr_sizeof_align_args": (sz, []),
+        "oasr_alignment_workspace_bytes": (sz, [i32, i32, i32]),
+        "oasr_alignment_matrix": (i32, [C.POINTER(AlignArgs), vp, sz, vp]),
+        "oasr_dtw_workspace_bytes": (sz, [i32, i32]),
+        "oasr_dtw": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+        "oasr_test_dtw_host": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
         "oasr_pick_tokens": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, vp]),
@@ -184,6 +199,9 @@ def lib():
             exports = _declare(handle)
         except AttributeError as e:
             raise NativeError(f"{LIB_PATH} (ABI {ver}) lacks an entry point this binding declares: {e} -- rebuild (__graft_entry__.build())") from e
+        if int(handle.oasr_sizeof_align_args()) != C.sizeof(AlignArgs):
+            raise NativeError(f"{LIB_PATH}: oasr_align_args of {int(handle.oasr_sizeof_align_args())} bytes, this binding passes "
+                              f"{C.sizeof(AlignArgs)} -- rebuild (__graft_entry__.build())")
         _lib, EXPORTS = handle, exports
     return _lib
 

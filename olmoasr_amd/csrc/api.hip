@@ -197,6 +197,15 @@ extern "C" int oasr_attention_scores(const oasr_attn_args* a, int dtype, float* 
   return launch_attention_scores(f, scores, (hipStream_t)stream);
 }
 
+extern "C" size_t oasr_sizeof_align_args(void) { return sizeof(oasr_align_args); }
+extern "C" int oasr_alignment_matrix(const oasr_align_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_alignment_matrix(a, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int oasr_dtw(const float* cost, int64_t ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_dtw(cost, (long)ld, N, M, negate, text_indices, time_indices, path_len, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                                      int64_t* targets_rows_out, int64_t* active_rows_out, void* stream) {
   OASR_REQUIRE(active_rows_out, "oasr_test_span_tables: null");

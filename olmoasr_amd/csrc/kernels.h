@@ -272,6 +272,14 @@ int launch_sample_tokens_ts(const float* logits, long ld, int V, long rows, cons
                             long hist_ld, int n_hist, int ts_begin, int eot, int no_ts, int max_initial_index, float temperature,
                             const float* u, int64_t* tok, float* logprob, hipStream_t s);
 
+// ---- word-timestamp alignment (align.hip; the argument block and the contracts: include/oasr.h) ---------------------------------
+// score planes of the selected heads, read in place -> fp32 [n_tok, n_frames]; workspace of oasr_alignment_workspace_bytes
+struct oasr_align_args;
+int launch_alignment_matrix(const oasr_align_args* a, void* workspace, size_t workspace_bytes, hipStream_t s);
+// timing.py::dtw bit for bit, one workgroup, path left on the device; workspace of oasr_dtw_workspace_bytes (dtw_core.h)
+int launch_dtw(const float* cost, long ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
+               void* workspace, size_t workspace_bytes, hipStream_t s);
+
 // ---- LoRA adapters in weight space (lora.hip) -----------------------------------------------------------------
 // out = W0 + scale * B . A  (W0 [rows][cols] fp32, A [r][cols], B [rows][r]; k sum in ascending order): exactly one of out32 (fp32, may be w0
 // itself) / out16 (bf16, the rounding of launch_cast_f32_bf16)

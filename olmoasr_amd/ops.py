@@ -232,6 +232,134 @@ def attention_bwd_rows(qc, kc, vc, oc, lse, doc, B, H, Tq, Tk, q_rows, k_rows=No
     return dq, dk, dv
 
 
+# ---- word-timestamp alignment (csrc/align.hip; timing.find_alignment(backend="native")) --------------------------------------------------
+_ws_cache = {}  # (operator, device index) -> uint8 workspace, grown on demand and reused by later calls on that device
+
+
+def _workspace(kind, device, need):
+    key = (kind, torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device())
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        _ws_cache[key] = None
+        ws = _ws_cache[key] = torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+MEDFILT_WIDTHS = (1, 3, 5, 7, 9, 11, 13, 15)  # 7 (whisper's), 1 and 3 are the required ones; the other odd widths run the generic network
+
+
+def alignment_matrix(qk_layers, heads_per_layer, n_frames, medfilt_width=7, qk_scale=1.0, out=None):
+    """The [tokens, frames] alignment matrix of ``timing.find_alignment`` from the cross-attention score planes, in one operator:
+
+        out[i, j] = mean over the selected heads h of  median_w( z_h[i, reflect(j - w/2 .. j + w/2)] )
+        z_h[i, j] = (p_h[i, j] - mean_i p_h[., j]) / std_i p_h[., j]       (population std over ALL rows)
+        p_h[i, .] = softmax over j < n_frames of qk_scale * qk_h[i, j]
+
+    ``qk_layers``: fp32 tensors [H, n_tok, Tk], contiguous, as ``timing.cross_attention_scores`` returns them (at most 32);
+    ``heads_per_layer``: for each of them the head indices that take part (each at most once; the order is irrelevant).  The planes are read in place -- no stacked copy; unselected
+    heads and frames >= n_frames are never read.  1 <= n_frames <= Tk; ``medfilt_width`` odd, 1 .. 15; no filter when
+    n_frames <= medfilt_width // 2 (``timing.median_filter``'s rule).  Returns fp32 [n_tok, n_frames] (``out``: a caller's tensor of that
+    shape with unit column stride).  Bad arguments raise ValueError before anything is launched.  A column whose variance over the tokens
+    is exactly zero is outside the contract, here as in ``timing.alignment_matrix_torch`` (which yields NaN there)."""
+    qk_layers, heads_per_layer = list(qk_layers), [[int(h) for h in hs] for hs in heads_per_layer]
+    if any(len(set(hs)) != len(hs) for hs in heads_per_layer):  # (a head named twice would count twice in the torch path's mean and once in a bit mask)
+        raise ValueError("alignment_matrix: a head index is repeated within a layer")
+    if not qk_layers or len(qk_layers) != len(heads_per_layer) or len(qk_layers) > N.AlignArgs.MAX_LAYERS:
+        raise ValueError(f"alignment_matrix: {len(qk_layers)} score tensors for {len(heads_per_layer)} head lists (1 .. {N.AlignArgs.MAX_LAYERS}, one list each)")
+    shape = tuple(qk_layers[0].shape)
+    for t in qk_layers:
+        if not (isinstance(t, torch.Tensor) and t.dim() == 3 and tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("alignment_matrix: every score tensor is a contiguous fp32 [H, n_tok, Tk] of the same shape")
+    H, n_tok, Tk = shape
+    if not (1 <= H <= 32 and 1 <= n_tok <= 65535 and Tk >= 1):
+        raise ValueError(f"alignment_matrix: H = {H} (1 .. 32), n_tok = {n_tok} (1 .. 65535), Tk = {Tk}")
+    if any(h < 0 or h >= H for hs in heads_per_layer for h in hs) or not any(heads_per_layer):
+        raise ValueError(f"alignment_matrix: head indices must lie in [0, {H}) and at least one head must be selected")
+    n_frames, medfilt_width = int(n_frames), int(medfilt_width)
+    if not 1 <= n_frames <= Tk:
+        raise ValueError(f"alignment_matrix: n_frames = {n_frames} outside [1, Tk = {Tk}]")
+    if medfilt_width not in MEDFILT_WIDTHS:
+        raise ValueError(f"alignment_matrix: medfilt_width = {medfilt_width}: an odd width from 1 to 15")
+    dev = qk_layers[0].device
+    for t in qk_layers:
+        N.require_gpu(t, "alignment_matrix: score tensor")
+        if t.device != dev:
+            raise ValueError("alignment_matrix: score tensors on different devices")
+    if out is None:
+        out = torch.empty(n_tok, n_frames, device=dev, dtype=torch.float32)
+    elif not (out.dtype == torch.float32 and tuple(out.shape) == (n_tok, n_frames) and out.device == dev and (out.stride(1) == 1 or n_frames == 1)
+              and out.stride(0) >= n_frames):
+        raise ValueError("alignment_matrix: out must be fp32 [n_tok, n_frames] on the scores' device with unit column stride")
+    a = N.AlignArgs()
+    for l, (t, hs) in enumerate(zip(qk_layers, heads_per_layer)):
+        a.qk[l] = t.data_ptr()
+        a.head_mask[l] = sum(1 << h for h in hs)
+    a.n_layers, a.H, a.n_tok, a.Tk, a.n_frames, a.medfilt_width, a.qk_scale = len(qk_layers), H, n_tok, Tk, n_frames, medfilt_width, float(qk_scale)
+    a.out, a.ldo = out.data_ptr(), out.stride(0)
+    nsel = sum(len(hs) for hs in heads_per_layer)
+    with torch.cuda.device(dev):
+        ws = _workspace("alignment_matrix", dev, N.lib().oasr_alignment_workspace_bytes(nsel, n_tok, n_frames))
+        N.check(N.lib().oasr_alignment_matrix(C.byref(a), N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "oasr_alignment_matrix")
+    return out
+
+
+def _dtw_check(cost):
+    if not (isinstance(cost, torch.Tensor) and cost.dim() == 2 and cost.dtype == torch.float32):
+        raise ValueError("dtw: cost must be an fp32 [N, M] tensor")
+    n, m = cost.shape
+    if not (1 <= n <= N.DTW_MAX_N and 1 <= m <= N.DTW_MAX_M):
+        raise ValueError(f"dtw: cost of {n} x {m}: 1 <= N <= {N.DTW_MAX_N} (n_text_ctx) and 1 <= M <= {N.DTW_MAX_M} (n_audio_ctx)")
+    if m > 1 and cost.stride(1) != 1:
+        raise ValueError("dtw: cost needs unit column stride (any row stride)")
+    if n > 1 and cost.stride(0) < m:
+        raise ValueError("dtw: cost rows overlap")
+    return int(n), int(m)
+
+
+def dtw_device(cost, negate=False, path=None, workspace=None):
+    """``dtw`` with everything left on the device: returns (path, workspace) -- ``path`` int32 [2 * (N + M - 1) + 1] holds the text indices, the
+    time indices (the first ``len`` of N + M - 1 entries each) and ``len`` in its last element.  ``path`` / ``workspace``: caller's buffers."""
+    n, m = _dtw_check(cost)
+    N.require_gpu(cost, "dtw: cost")
+    P = n + m - 1
+    need = N.lib().oasr_dtw_workspace_bytes(n, m)
+    with torch.cuda.device(cost.device):
+        if path is None:
+            path = torch.empty(2 * P + 1, device=cost.device, dtype=torch.int32)
+        if workspace is None:
+            workspace = _workspace("dtw", cost.device, need)
+        assert path.dtype == torch.int32 and path.numel() == 2 * P + 1 and path.is_contiguous() and workspace.dtype == torch.uint8
+        ld = cost.stride(0) if n > 1 else max(m, cost.stride(0))
+        N.check(N.lib().oasr_dtw(N.ptr(cost), ld, n, m, int(bool(negate)), N.ptr(path), N.ptr(path[P:]), N.ptr(path[2 * P:]), N.ptr(workspace),
+                                 workspace.numel(), N.stream_ptr(cost.device)), "oasr_dtw")
+    return path, workspace
+
+
+def dtw(cost, negate=False):
+    """``timing.dtw`` on the device, bit for bit: cost fp32 [N, M] (any row stride; ``negate``: the alignment of ``-cost``),
+    1 <= N <= 448, 1 <= M <= 1500 -> (text_indices, time_indices), int64 CPU tensors, after ONE device-to-host copy of the path.
+    Out-of-range shapes raise ValueError before anything is launched."""
+    n, m = _dtw_check(cost)
+    path, _ = dtw_device(cost, negate)
+    host = path.cpu()
+    P, ln = n + m - 1, int(host[-1])
+    return host[:ln].to(torch.int64), host[P:P + ln].to(torch.int64)
+
+
+def dtw_host(cost, negate=False):
+    """include/oasr_testing.h: oasr_test_dtw_host -- the kernel's wavefront, skewed trace and backtrace run on the CPU (``cost``: CPU fp32)."""
+    n, m = _dtw_check(cost)
+    assert not cost.is_cuda
+    P = n + m - 1
+    path = torch.full((2 * P + 1,), -1, dtype=torch.int32)
+    ws = torch.empty(N.lib().oasr_dtw_workspace_bytes(n, m), dtype=torch.uint8)
+    ld = cost.stride(0) if n > 1 else max(m, cost.stride(0))
+    N.check(N.lib().oasr_test_dtw_host(N.ptr(cost), ld, n, m, int(bool(negate)), N.ptr(path), N.ptr(path[P:]), N.ptr(path[2 * P:]), N.ptr(ws)),
+            "oasr_test_dtw_host")
+    ln = int(path[-1])
+    return path[:ln].to(torch.int64), path[P:P + ln].to(torch.int64)
+
+
 def cross_entropy_(logits, V, targets, ignore, gscale=1.0, write_grad=True):
     """In place on bf16 logits [rows, ld]: returns (mean loss over non-ignored rows, row_loss); logits become the gradient."""
     rows, ld = logits.shape

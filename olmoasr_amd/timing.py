@@ -17,6 +17,11 @@ With the REFERENCE's model class step 1 cannot work: its cross-attention runs th
 ``qk = None`` (olmoasr/model.py:313, 328-345), and the class has no ``alignment_heads`` -- ``word_timestamps=True`` fails there.  Here the
 score matrix is computed on request (``MultiHeadAttention.return_qk`` -> ``oasr_attention_scores``, csrc/scores.hip), so the option works.
 
+Steps 2 and 3 have two backends (``find_alignment(backend=...)``, ``transcribe(alignment_backend=...)``): "torch" (the default) runs them as
+torch ops (``alignment_matrix_torch``) and the numpy ``dtw`` below on the host; "native" runs ``ops.alignment_matrix`` and ``ops.dtw``
+(csrc/align.hip) on the GPU: the score planes are read in place, the median is a register network, the DTW and its backtrace are one launch, and
+only the path comes back.  ``ops.dtw`` is bit-identical to ``dtw``; the matrix agrees to fp32 rounding.
+
 The tokenizer is a plug with whisper's attribute names: ``sot_sequence``, ``no_timestamps``, ``eot``, ``split_to_word_tokens(tokens) ->
 (words, word_tokens)``.
 """
@@ -127,28 +132,56 @@ def cross_attention_scores(model, tokens: torch.Tensor, xa: torch.Tensor, layers
     return got
 
 
+def alignment_matrix_torch(qks, heads, n_frames: int, medfilt_width: int = 7, qk_scale: float = 1.0) -> torch.Tensor:
+    """Step 2 of the module docstring in torch ops: ``qks`` {layer: fp32 [H, tokens, n_audio_ctx]}, ``heads`` [(layer, head)] -> fp32
+    [tokens, n_frames], every token row included (the caller slices).  A column whose variance over the tokens is exactly zero gives NaN."""
+    weights = torch.stack([qks[l][h] for l, h in heads])            # heads x tokens x frames
+    weights = weights[:, :, : n_frames]
+    weights = (weights * qk_scale).softmax(dim=-1)
+    std, mean = torch.std_mean(weights, dim=-2, keepdim=True, unbiased=False)
+    weights = (weights - mean) / std
+    weights = median_filter(weights, medfilt_width)
+    return weights.mean(dim=0)
+
+
+BACKENDS = ("torch", "native")
+
+
 @torch.no_grad()
 def find_alignment(model, tokenizer, text_tokens: List[int], mel: torch.Tensor, num_frames: int, *, medfilt_width: int = 7,
-                   qk_scale: float = 1.0) -> List[WordTiming]:
+                   qk_scale: float = 1.0, backend: str = "torch", audio_features: torch.Tensor = None) -> List[WordTiming]:
+    """``backend``: "torch" -- steps 2 and 3 as torch ops and the host ``dtw``; "native" -- ``ops.alignment_matrix`` and ``ops.dtw``
+    (csrc/align.hip) on the model's GPU, everything after the path being the same code.  ``audio_features``: the window's encoder output
+    where the caller has it already (``mel`` is then not encoded again).  ``num_frames`` < 2 (no audio token) raises ValueError for either backend."""
+    if backend not in BACKENDS:
+        raise ValueError(f"find_alignment: backend {backend!r} (one of {BACKENDS})")
+    if backend == "native" and torch.device(model.device).type != "cuda":
+        raise ValueError("find_alignment: backend='native' runs on the GPU and the model is on " + str(model.device))
     if len(text_tokens) == 0:
         return []
+    if num_frames < 2:  # (less than one audio token: no column to align to, for either backend)
+        raise ValueError(f"find_alignment: num_frames = {num_frames} mel frames hold no audio token (2 mel frames each)")
     n_sot = len(tokenizer.sot_sequence)
     tokens = torch.tensor([*tokenizer.sot_sequence, tokenizer.no_timestamps, *text_tokens, tokenizer.eot], device=model.device)
-    xa = model.embed_audio(mel[None] if mel.dim() == 2 else mel)
+    if audio_features is not None:
+        xa = audio_features[None] if audio_features.dim() == 2 else audio_features
+    else:
+        xa = model.embed_audio(mel[None] if mel.dim() == 2 else mel)
     logits = model.logits(tokens[None], xa)[0]
     probs = logits[n_sot:, : tokenizer.eot].float().softmax(dim=-1)
     text_token_probs = probs[torch.arange(len(text_tokens)), torch.tensor(text_tokens, device=probs.device)].tolist()
 
     heads = alignment_heads(model)
     qks = cross_attention_scores(model, tokens, xa, sorted({l for l, _ in heads}))
-    weights = torch.stack([qks[l][h] for l, h in heads])            # heads x tokens x frames
-    weights = weights[:, :, : num_frames // 2]
-    weights = (weights * qk_scale).softmax(dim=-1)
-    std, mean = torch.std_mean(weights, dim=-2, keepdim=True, unbiased=False)
-    weights = (weights - mean) / std
-    weights = median_filter(weights, medfilt_width)
-    matrix = weights.mean(dim=0)[n_sot:-1]                           # text tokens (+ <notimestamps>) x frames
-    text_indices, time_indices = dtw(-matrix.double().cpu().numpy())
+    if backend == "native":
+        from . import ops
+        layers = sorted(qks)
+        matrix = ops.alignment_matrix([qks[l] for l in layers], [[h for ll, h in heads if ll == l] for l in layers], num_frames // 2,
+                                      medfilt_width, qk_scale)
+        text_indices, time_indices = (t.numpy() for t in ops.dtw(matrix[n_sot:-1], negate=True))
+    else:
+        matrix = alignment_matrix_torch(qks, heads, num_frames // 2, medfilt_width, qk_scale)[n_sot:-1]  # text tokens (+ <notimestamps>) x frames
+        text_indices, time_indices = dtw(-matrix.double().cpu().numpy())
 
     words, word_tokens = tokenizer.split_to_word_tokens(text_tokens + [tokenizer.eot])
     if len(word_tokens) <= 1:  # only the eot "word": nothing to time

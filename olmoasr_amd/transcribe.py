@@ -35,6 +35,7 @@ import torch
 
 from .audio import FRAMES_PER_SECOND, HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE, log_mel_spectrogram, pad_or_trim
 from .decoding import EOT, TIMESTAMP_BEGIN, DecodingOptions, DecodingResult, decode, resolve_tokenizer
+from .timing import BACKENDS as ALIGNMENT_BACKENDS
 from .timing import add_word_timestamps
 
 PUNCTUATION = "\"'“¿([{-\"'.。,，!！?？:：”)]}、"  # (:188)
@@ -81,7 +82,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None,
                initial_prompt: Optional[str] = None, carry_initial_prompt: bool = False, word_timestamps: bool = False,
                prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
                clip_timestamps: Union[str, Sequence[float]] = "0",
-               hallucination_silence_threshold: Optional[float] = None, batch_windows: int = 16, tokenizer=None, **decode_options):
+               hallucination_silence_threshold: Optional[float] = None, batch_windows: int = 16, tokenizer=None,
+               alignment_backend: str = "torch", **decode_options):
     if isinstance(audio, str):
         from .audio import load_audio
         audio = load_audio(audio)
@@ -109,6 +111,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None,
     if word_timestamps and tokenizer is None:
         raise ValueError("word_timestamps=True needs a tokenizer (tokenizer=...): words are a property of the decoded text "
                          "(tokenizer.split_to_word_tokens); whisper's own is used where the package is installed")
+    if alignment_backend not in ALIGNMENT_BACKENDS:  # (olmoasr_amd/timing.py: "torch" ops + host DTW, or the operators of csrc/align.hip)
+        raise ValueError(f"alignment_backend {alignment_backend!r} (one of {ALIGNMENT_BACKENDS})")
     if word_timestamps and decode_options.get("task", "transcribe") == "translate":  # (:174-175)
         warnings.warn("Word-level timestamps on translations may not be reliable.")
     initial_prompt_tokens: List[int] = []
@@ -229,7 +233,9 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None,
         if word_timestamps:  # (:409-486)
             add_word_timestamps(segments=current_segments, model=model, tokenizer=tokenizer, mel=window(previous_seek, seek_clip_end)[0],
                                 num_frames=segment_size, prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
-                                last_speech_timestamp=last_speech_timestamp)
+                                last_speech_timestamp=last_speech_timestamp, backend=alignment_backend,
+                                # (the native backend aligns on the encoder output the decode call produced instead of encoding the window again)
+                                **({"audio_features": result.audio_features} if alignment_backend == "native" else {}))
             if not single_timestamp_ending:  # resume right after the last word instead of at the last closed timestamp
                 last_word_end = get_end(current_segments)
                 if last_word_end is not None and last_word_end > time_offset:
