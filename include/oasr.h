@@ -327,6 +327,32 @@ int oasr_alignment_matrix(const oasr_align_args*, void* workspace, size_t worksp
 size_t oasr_dtw_workspace_bytes(int N, int M);
 int oasr_dtw(const float* cost, int64_t ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
              void* workspace, size_t workspace_bytes, void* stream);
+/* SpecAugment (Park et al. 2019, without time warping) on the FINALIZED log-mel tensor, before the engine sees it (csrc/specaug.hip; the
+ * rule itself: csrc/specaug_core.h).  Both entries add entry points only: OASR_ABI_VERSION is unchanged, and a binding checks
+ * oasr_sizeof_specaug like oasr_sizeof_align_args.
+ *
+ * A clip's masks are a pure integer function of (seed, clip stream id, policy, shape), in unsigned 64-bit arithmetic with wrap-around:
+ *     mix(z):  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *              return z ^ (z >> 31)
+ *     h = mix(mix(seed) ^ clip)                                    clip = first_clip + row index in the batch
+ *     for (kind, n, W, L) in ((1, freq_masks, freq_width, n_mels), (2, time_masks, time_width, T)), mask i < n, W = min(W, L):
+ *         width = mix(h ^ ((kind << 16) | (i << 1)    )) % (W + 1)
+ *         start = mix(h ^ ((kind << 16) | (i << 1) | 1)) % (L - width + 1)
+ * and the cells [start, start + width) along that axis, over the whole other axis, are set to `fill`.  Masks may overlap and may have
+ * width 0.  time_width is taken as given: a cap relative to the clip length is the caller's (integer) business.
+ *
+ * oasr_spec_augment: mel f32 [B, n_mels, T], contiguous, in place, one launch on `stream`.  Masked cells are stored to; no other cell is
+ * written and mel is never read.  B, n_mels, T >= 1; 0 <= counts <= OASR_SPECAUG_MAX_MASKS; widths >= 0; else OASR_EINVAL.
+ * oasr_spec_augment_plan: HOST function (no GPU call, host pointers): the same intervals for ONE clip as (start, width) pairs,
+ * freq_iv int32 [freq_masks][2], time_iv int32 [time_masks][2]; both lists must be non-null. */
+#define OASR_SPECAUG_MAX_MASKS 8
+typedef struct oasr_specaug {
+  int32_t freq_masks, freq_width, time_masks, time_width;
+  float fill;
+} oasr_specaug;
+size_t oasr_sizeof_specaug(void);
+int oasr_spec_augment(float* mel, int B, int n_mels, int T, const oasr_specaug* policy, uint64_t seed, uint64_t first_clip, void* stream);
+int oasr_spec_augment_plan(const oasr_specaug* policy, uint64_t seed, uint64_t clip, int n_mels, int T, int32_t* freq_iv, int32_t* time_iv);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 int oasr_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);

@@ -51,8 +51,14 @@ class AlignArgs(C.Structure):  # include/oasr.h: oasr_align_args
                 ("out", C.c_void_p), ("ldo", C.c_int64)]
 
 
+class SpecAug(C.Structure):  # include/oasr.h: oasr_specaug
+    MAX_MASKS = 8  # OASR_SPECAUG_MAX_MASKS
+    _fields_ = [("freq_masks", C.c_int32), ("freq_width", C.c_int32), ("time_masks", C.c_int32), ("time_width", C.c_int32), ("fill", C.c_float)]
+
+
 DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_audio_ctx
 # The word-timestamp operators (oasr_alignment_matrix, oasr_dtw, oasr_test_dtw_host) add entry points without a new ABI generation: a library built before them is refused by the oasr_sizeof_align_args check in lib().
+# SpecAugment (oasr_spec_augment, oasr_spec_augment_plan) came the same way: entry points only, a stale library refused by the oasr_sizeof_specaug check in lib().
 ABI_VERSION = 215  # include/oasr.h: OASR_ABI_VERSION (215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
@@ -142,6 +148,9 @@ def _declare(lib):
         "oasr_dtw_workspace_bytes": (sz, [i32, i32]),
         "oasr_dtw": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
         "oasr_test_dtw_host": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+        "oasr_sizeof_specaug": (sz, []),
+        "oasr_spec_augment": (i32, [vp, i32, i32, i32, C.POINTER(SpecAug), C.c_uint64, C.c_uint64, vp]),
+        "oasr_spec_augment_plan": (i32, [C.POINTER(SpecAug), C.c_uint64, C.c_uint64, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
         "oasr_pick_tokens": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, vp]),
@@ -202,6 +211,9 @@ def lib():
         if int(handle.oasr_sizeof_align_args()) != C.sizeof(AlignArgs):
             raise NativeError(f"{LIB_PATH}: oasr_align_args of {int(handle.oasr_sizeof_align_args())} bytes, this binding passes "
                               f"{C.sizeof(AlignArgs)} -- rebuild (__graft_entry__.build())")
+        if int(handle.oasr_sizeof_specaug()) != C.sizeof(SpecAug):
+            raise NativeError(f"{LIB_PATH}: oasr_specaug of {int(handle.oasr_sizeof_specaug())} bytes, this binding passes "
+                              f"{C.sizeof(SpecAug)} -- rebuild (__graft_entry__.build())")
         _lib, EXPORTS = handle, exports
     return _lib
 

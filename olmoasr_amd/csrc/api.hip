@@ -206,6 +206,12 @@ extern "C" int oasr_dtw(const float* cost, int64_t ld, int N, int M, int negate,
   return launch_dtw(cost, (long)ld, N, M, negate, text_indices, time_indices, path_len, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+extern "C" size_t oasr_sizeof_specaug(void) { return sizeof(oasr_specaug); }
+extern "C" int oasr_spec_augment(float* mel, int B, int n_mels, int T, const oasr_specaug* policy, uint64_t seed, uint64_t first_clip,
+                                 void* stream) {
+  return launch_spec_augment(mel, B, n_mels, T, policy, seed, first_clip, (hipStream_t)stream);
+}
+
 extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                                      int64_t* targets_rows_out, int64_t* active_rows_out, void* stream) {
   OASR_REQUIRE(active_rows_out, "oasr_test_span_tables: null");

@@ -280,6 +280,11 @@ int launch_alignment_matrix(const oasr_align_args* a, void* workspace, size_t wo
 int launch_dtw(const float* cost, long ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
                void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// ---- SpecAugment (specaug.hip; the policy block and the rule: include/oasr.h, specaug_core.h) ------------------------------------
+// mel fp32 [B, n_mels, T] in place: the seeded masks of clips first_clip .. first_clip + B - 1 set to policy->fill, nothing else written
+struct oasr_specaug;
+int launch_spec_augment(float* mel, int B, int n_mels, int T, const oasr_specaug* policy, uint64_t seed, uint64_t first_clip, hipStream_t s);
+
 // ---- LoRA adapters in weight space (lora.hip) -----------------------------------------------------------------
 // out = W0 + scale * B . A  (W0 [rows][cols] fp32, A [r][cols], B [rows][r]; k sum in ascending order): exactly one of out32 (fp32, may be w0
 // itself) / out16 (bf16, the rounding of launch_cast_f32_bf16)

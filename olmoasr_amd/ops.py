@@ -399,6 +399,62 @@ def log_mel(pcm, finalize: bool = True):
     return mel
 
 
+_U64 = (1 << 64) - 1
+
+
+def specaug_policy(freq_masks, freq_width, time_masks, time_width, fill=0.0):
+    """The ``oasr_specaug`` block of a policy, refused here (ValueError) for what the library would refuse (OASR_EINVAL)."""
+    for name, v in (("freq_masks", freq_masks), ("freq_width", freq_width), ("time_masks", time_masks), ("time_width", time_width)):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < 2 ** 31:
+            raise ValueError(f"spec_augment: {name} must be an integer in [0, 2^31), got {v!r}")
+    if freq_masks > N.SpecAug.MAX_MASKS or time_masks > N.SpecAug.MAX_MASKS:
+        raise ValueError(f"spec_augment: at most {N.SpecAug.MAX_MASKS} masks of each kind, got {freq_masks} frequency / {time_masks} time masks")
+    return N.SpecAug(freq_masks, freq_width, time_masks, time_width, float(fill))
+
+
+def _u64(name, v):
+    if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= _U64:
+        raise ValueError(f"spec_augment: {name} must be an integer in [0, 2^64), got {v!r}")
+    return v
+
+
+def spec_augment_(mel, *, freq_masks, freq_width, time_masks, time_width, fill=0.0, seed=0, first_clip=0):
+    """SpecAugment in place on finalized log-mel (include/oasr.h: oasr_spec_augment): mel fp32 [B, n_mels, T] or [n_mels, T], contiguous, on
+    the GPU.  Row ``b`` takes the masks of stream id ``first_clip + b`` (mod 2^64) under ``seed``: ``freq_masks`` bands of width <=
+    ``freq_width`` over all frames and ``time_masks`` spans of width <= ``time_width`` over all bins are set to ``fill``; no other cell is
+    written.  ``time_width`` is taken as given (``augment.SpecAugment`` applies the cap relative to T).  One launch on the current stream;
+    returns ``mel``."""
+    N.require_gpu(mel, "spec_augment: mel")
+    if mel.dtype != torch.float32:
+        raise N.NativeError(f"spec_augment: unsupported dtype {mel.dtype} (float32 log-mel only)")
+    if mel.dim() not in (2, 3):
+        raise ValueError(f"spec_augment: mel must be [B, n_mels, T] or [n_mels, T], got {tuple(mel.shape)}")
+    if not mel.is_contiguous():
+        raise ValueError("spec_augment: mel must be contiguous (it is modified in place; a copy would take the masks with it)")
+    pol = specaug_policy(freq_masks, freq_width, time_masks, time_width, fill)
+    seed, first_clip = _u64("seed", seed), _u64("first_clip", first_clip)
+    B = mel.shape[0] if mel.dim() == 3 else 1
+    n_mels, T = mel.shape[-2:]
+    if B == 0:
+        return mel
+    if n_mels < 1 or T < 1:
+        raise ValueError(f"spec_augment: n_mels = {n_mels} and T = {T} must be >= 1")
+    with torch.cuda.device(mel.device):
+        N.check(N.lib().oasr_spec_augment(N.ptr(mel), B, n_mels, T, C.byref(pol), seed, first_clip, N.stream_ptr(mel.device)), "oasr_spec_augment")
+    return mel
+
+
+def spec_augment_plan(*, freq_masks, freq_width, time_masks, time_width, seed=0, clip=0, n_mels=80, T=3000):
+    """The masks ``spec_augment_`` gives stream id ``clip``, from the library's host twin (oasr_spec_augment_plan; no GPU):
+    (frequency masks, time masks), each a list of (start, width)."""
+    pol = specaug_policy(freq_masks, freq_width, time_masks, time_width)
+    if not (isinstance(n_mels, int) and isinstance(T, int) and 1 <= n_mels < 2 ** 31 and 1 <= T < 2 ** 31):
+        raise ValueError(f"spec_augment: n_mels = {n_mels!r} and T = {T!r} must be integers in [1, 2^31)")
+    f_iv, t_iv = (C.c_int32 * (2 * max(1, freq_masks)))(), (C.c_int32 * (2 * max(1, time_masks)))()
+    N.check(N.lib().oasr_spec_augment_plan(C.byref(pol), _u64("seed", seed), _u64("clip", clip), n_mels, T, f_iv, t_iv), "oasr_spec_augment_plan")
+    return ([(f_iv[2 * i], f_iv[2 * i + 1]) for i in range(freq_masks)], [(t_iv[2 * i], t_iv[2 * i + 1]) for i in range(time_masks)])
+
+
 def pick_tokens(logits, mask=None, mask2=None, want_logprob=True):
     """logits fp32 [rows, V] (row stride free) -> (argmax ids int64 [rows], log_softmax at the argmax fp32 [rows] | None);
     ``mask`` / ``mask2``: additive fp32 [V] (0 / -inf)."""

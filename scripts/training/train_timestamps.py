@@ -59,7 +59,13 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     freeze_encoder=False,  # fine-tuning: encoder.* get requires_grad=False (no gradient, no update; the backward skips the encoder)
     # LoRA fine-tuning (olmoasr_amd/lora.py): rank-r adapters with scale alpha / r on the modules --lora_targets selects (comma-separated
     # fnmatch patterns), every base parameter frozen; 0 = off.  With --freeze_encoder the encoder's adapters stay frozen as well.
-    lora_rank=0, lora_alpha=32, lora_targets="*.attn.query,*.attn.value")
+    lora_rank=0, lora_alpha=32, lora_targets="*.attn.query,*.attn.value",
+    # SpecAugment on the finalized log-mel of every TRAINING micro-batch (olmoasr_amd/augment.py, csrc/specaug.hip): off | LD (2 + 2 masks) |
+    # LB (1 + 1); the --spec_* overrides replace single fields of the preset.  Masks are seeded by --seed and the step counter (spec_offset).
+    spec_augment="off", spec_freq_masks=None, spec_freq_width=None, spec_time_masks=None, spec_time_width=None, spec_time_ratio=None,
+    spec_fill=None)
+SPEC_OVERRIDES = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_time_ratio", "spec_fill")
+SPEC_PRESETS = ("off", "LD", "LB")
 
 
 class Args(dict):
@@ -74,6 +80,36 @@ def _literal(v):
         return ast.literal_eval(v)
     except (ValueError, SyntaxError):
         return v
+
+
+def spec_policy(args):
+    """--spec_augment and its overrides -> augment.SpecAugment, or None for "off"."""
+    given = [f for f in SPEC_OVERRIDES if args[f] is not None]
+    if args.spec_augment not in SPEC_PRESETS:
+        raise SystemExit(f"--spec_augment must be one of {' | '.join(SPEC_PRESETS)}, got {args.spec_augment!r}")
+    if args.spec_augment == "off":
+        if given:
+            raise SystemExit(f"--{' --'.join(given)} given with --spec_augment=off: name a policy ({' | '.join(SPEC_PRESETS[1:])}) to override")
+        return None
+    from olmoasr_amd import augment
+    over = {f[len("spec_"):]: args[f] for f in given}
+    for k in ("time_ratio", "fill"):
+        if k in over:
+            try:
+                over[k] = float(over[k])  # ("nan" / "inf" are not Python literals)
+            except (TypeError, ValueError):
+                raise SystemExit(f"--spec_{k} must be a number, got {over[k]!r}")
+    try:
+        return augment.SpecAugment.preset(args.spec_augment, **over)
+    except ValueError as e:
+        raise SystemExit(f"--spec_augment={args.spec_augment}: {e}")
+
+
+def spec_offset(global_step, micro, accum, world_size, rank, train_batch_size):
+    """Stream id of row 0 of micro-batch ``micro`` of the step that follows ``global_step`` completed ones, on ``rank``; row b is + b.  A
+    function of the step counter, not of process lifetime: a resumed run draws the masks the uninterrupted run would have drawn, and the
+    id ranges of different (step, micro, rank) never overlap."""
+    return ((global_step * accum + micro) * world_size + rank) * train_batch_size
 
 
 def parse_args(argv=None):
@@ -117,6 +153,7 @@ def parse_args(argv=None):
     if isinstance(args.lora_targets, str):
         args.lora_targets = tuple(t.strip() for t in args.lora_targets.split(",") if t.strip())
     args.lora_targets = tuple(args.lora_targets)
+    args.spec_policy = spec_policy(args)
     return args
 
 
@@ -337,7 +374,7 @@ def host_cores():
 
 def main(argv=None):
     args = parse_args(argv)
-    from olmoasr_amd import ddp, ops
+    from olmoasr_amd import augment, ddp, ops
     from olmoasr_amd.config.model_dims import VARIANT_TO_DIMS
     from olmoasr_amd.model import OLMoASR
     from olmoasr_amd.synth import SynthLoader
@@ -420,12 +457,18 @@ def main(argv=None):
     else:
         per_rank = len(mine)
         loader = SynthLoader(batch_order(cursor), dev, workers=workers, depth=max(1, int(args.prefetch_factor)), timestamps=bool(args.timestamps))
-    held_out = [args.n_synthetic + i for i in range(8)]  # evaluate(): clips outside every rank's training shard
+    held_out = [args.n_synthetic + i for i in range(8)]  # evaluate(): clips outside every rank's training shard (never masked)
+    policy, spec_seed = args.spec_policy, int(args.seed) & ((1 << 64) - 1)
+    if policy is not None and rank == 0:
+        print(json.dumps({"event": "spec_augment", "policy": args.spec_augment, "freq_masks": policy.freq_masks, "freq_width": policy.freq_width,
+                          "time_masks": policy.time_masks, "time_width": policy.time_width, "time_ratio": policy.time_ratio,
+                          "fill": policy.fill if math.isfinite(policy.fill) else str(policy.fill), "seed": spec_seed}), flush=True)
     while global_step < args.train_steps:
         start_step = time.time()
         net.zero_grad()
         log_now = ((global_step + 1) % args.train_log_freq) == 0  # gen_pred condition of the reference (:1480)
         preds, tgts = [], []
+        spec_cells = 0  # cells masked on this rank in this step: from the host plan, no device read-back
         for i in range(accum):
             pcm, ti, ty, tl = next(loader)
             cursor += args.train_batch_size  # (position in this rank's epoch order; a short last batch also ends the epoch)
@@ -435,7 +478,13 @@ def main(argv=None):
             # (a logging step wants the logits back: it takes the plain step; every other step limits the decoder's backward to the span
             # and lets the encoder's transpose apply the log-mel floor / scale instead of a second pass over the tensor)
             use_span = bool(args.span_backward) and not log_now
-            mel, clip_max = ops.log_mel(pcm, finalize=False) if use_span else (ops.log_mel(pcm), None)
+            if policy is not None:  # masks go on the FINALIZED log-mel, so the span step takes it finalized as well (mel_clip_max=None)
+                mel, clip_max = ops.log_mel(pcm), None
+                first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
+                policy.apply_(mel, spec_seed, first)
+                spec_cells += augment.masked_cells(policy, spec_seed, first, *mel.shape)
+            else:
+                mel, clip_max = ops.log_mel(pcm, finalize=False) if use_span else (ops.log_mel(pcm), None)
             _, logits = net.loss_and_backward(mel, ti, ty, tl, loss_scale=scaler.scale, accumulation_steps=accum, loss_out=loss_buf,
                                               accumulate_loss=i > 0, return_logits=log_now,
                                               segment_events=reducer.segment_events() if (reducer and last) else None,
@@ -472,7 +521,8 @@ def main(argv=None):
             if rank == 0:
                 rec = {"global_step": global_step, "train_loss": float(t) / world_size, "lr": lr, "loss_scale": scaler.scale,
                        "time_per_step": round(time_per_step, 4), "audio_min_per_GPU_second": round(throughput, 3),
-                       "audio_sec_per_sec_node": round(throughput * 60 * world_size, 1), "found_inf": found_inf}
+                       "audio_sec_per_sec_node": round(throughput * 60 * world_size, 1), "found_inf": found_inf,
+                       "spec_masked_cells": spec_cells}
                 if preds:
                     rec["train_token_error_rate"] = round(token_error_rate(preds, tgts), 4)
                 log.append(rec)
