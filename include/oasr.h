@@ -170,7 +170,7 @@ int oasr_train_fwd_bwd_s(oasr_ctx*, const float* mel, const int64_t* tokens, con
  * every target of sample b at a position >= span_host[b] is ignore_index, and span_host[b] >= text_len[b].  Gradient rows past the
  * span are exactly zero in the reference's computation, so the decoder's token rows are stored in 64-position chunks with the
  * chunks that can carry gradient first and the decoder's backward GEMMs / LayerNorms / attention run over those rows only
- * (olmoasr_amd/csrc/engine.hip).  Loss and gradients equal oasr_train_fwd_bwd's up to fp32 summation order.  Falls back to the
+ * (olmoasr_amd/csrc/engine_step.hip).  Loss and gradients equal oasr_train_fwd_bwd's up to fp32 summation order.  Falls back to the
  * plain step when n_text_ctx is not a multiple of 64 or B > 512. */
 #define OASR_SPAN_FORWARD_ALL 0    /* the reference's shape: the decoder's forward covers all n_text_ctx positions */
 #define OASR_SPAN_FORWARD_ACTIVE 1 /* opt-in: the forward leaves the positions past the span out too -- their logits exist in the reference

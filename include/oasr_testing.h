@@ -25,7 +25,7 @@ int oasr_gemm_set_variant(int v);
  * XCD (B <= 4), 3 / 4 = that team as 32 / 64 workgroups spread over the chip, 5 = the chip-wide engine (one sequence; more: as 2).
  * 0-4 are bit-identical; 5 agrees with them to the fp32 rounding of differently ordered K sums (tests/test_gpu_decode_step.py). */
 int oasr_decode_set_ln_fold(int mode);
-/* tests / A-B: side streams of the supervised-span step (oasr_train_fwd_bwd_span; csrc/engine.hip: Runner::side_mode).  Bit 0: the decoder
+/* tests / A-B: side streams of the supervised-span step (oasr_train_fwd_bwd_span; csrc/engine_run.h: Runner::side_mode).  Bit 0: the decoder
  * backward's weight gradients over the R active rows, bit 2: the cross-attention key|value weight gradient and d(xa) -- run on lowest-priority
  * streams beside the data-gradient chain; bit 1: the key|value projections of the decoder forward likewise; bit 3: without segment events leave
  * the key|value gradients in flight across blocks.  -1 = the library default.  Gradients differ by fp32 atomic order only

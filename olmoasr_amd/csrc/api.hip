@@ -76,21 +76,7 @@ extern "C" int oasr_test_gemm(const oasr_gemm_args* a, float* colsum_scratch, in
   return launch_gemm(g, (hipStream_t)stream);
 }
 
-// The setters below change process-wide kernel-selection state (A/B experiments, forcing a kernel path in a parity test).  They live in
-// the same library as the product ABI, so they are inert unless the process opts in: OASR_TESTING_HOOKS=1 in the environment
-// (tests/conftest.py and the scripts/ that use them set it); without it they fail and change nothing.
-static int hooks_enabled(const char* what) {
-  const char* e = getenv("OASR_TESTING_HOOKS");
-  if (e && e[0] == '1') return OASR_OK;
-  oasr_set_error("%s: testing hook called without OASR_TESTING_HOOKS=1 (include/oasr_testing.h)", what);
-  return OASR_ESTATE;
-}
-#define OASR_HOOK_GATE(name)          \
-  do {                                \
-    const int g_ = hooks_enabled(name); \
-    if (g_) return g_;                \
-  } while (0)
-
+// The setters below change process-wide kernel-selection state: testing hooks, inert without the opt-in (common.h: OASR_HOOK_GATE).
 extern "C" int oasr_profile_gemm(int enable) {
   gemm_profile_enable(enable);
   return OASR_OK;

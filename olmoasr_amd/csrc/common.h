@@ -51,6 +51,21 @@ static inline const char* oasr_experiment_env(const char* name) {
   return (h && h[0] == '1') ? getenv(name) : nullptr;
 }
 
+// The setters of include/oasr_testing.h change process-wide kernel-selection state (A/B experiments, forcing a kernel path in a parity test).  They
+// live in the same library as the product ABI, so they are inert unless the process opts in: OASR_TESTING_HOOKS=1 in the environment
+// (tests/conftest.py and the scripts/ that use them set it); without it they fail and change nothing.
+static inline int hooks_enabled(const char* what) {
+  const char* e = getenv("OASR_TESTING_HOOKS");
+  if (e && e[0] == '1') return OASR_OK;
+  oasr_set_error("%s: testing hook called without OASR_TESTING_HOOKS=1 (include/oasr_testing.h)", what);
+  return OASR_ESTATE;
+}
+#define OASR_HOOK_GATE(name)            \
+  do {                                  \
+    const int g_ = hooks_enabled(name); \
+    if (g_) return g_;                  \
+  } while (0)
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel: a process that touches a second GPU must set
 // it there too.  One of these per launch site (a function-local static); setting it again is harmless, so two host threads racing on
 // a slot only repeat the call.

@@ -3,7 +3,7 @@
 // -- TextDecoder.forward for one new token per sequence, olmoasr/model.py:786-817 with the kv_cache hooks of :925-964
 // (inference twin: olmoasr/inf_model.py:150-196, 320-362).
 //
-// Why: the multi-launch step (engine.hip::oasr_decode_step_impl) is ~8 dependent launches per layer, each a 4.7 us dispatch floor plus a
+// Why: the multi-launch step (engine_decode.hip::oasr_decode_step_impl) is ~8 dependent launches per layer, each a 4.7 us dispatch floor plus a
 // chain of dependent memory round trips (weights that must first miss to HBM, a reduction, a store): 2.4 ms per token at medium = 0.05
 // of the HBM roof (profiles/r02_decode_step.txt, r03_decode_xcd.txt).  What those measurements asked for is built here:
 //   * ONE persistent launch; the `team` workgroups (one per CU, by default the 32 CUs of ONE XCD: blockIdx % 8 == 0) walk the 8 phases

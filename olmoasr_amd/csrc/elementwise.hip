@@ -297,7 +297,7 @@ int launch_embedding_bwd(const int64_t* tok, const bf16_t* dx, float* dE, float*
   return OASR_OK;
 }
 
-// ---- supervised-span tables (engine.hip) ------------------------------------------------------------------------------------
+// ---- supervised-span tables (engine_step.hip) -----------------------------------------------------------------------------------
 namespace {
 struct SpanArg {
   uint16_t span[512];

@@ -1,0 +1,333 @@
+// Entry points of the inference forward and of every training step (plain, supervised-span, cut at the logits, staged at xa): argument checks,
+// one Step<T> (engine_run.h) per call, and the order in which the Runner's halves are issued.
+#include "engine_run.h"
+
+// Runner::side_mode of the span step.  7 = the decoder backward's R-row weight gradients, the cross-attention key|value gradients AND the
+// forward's key|value projections on the lowest-priority side streams: -1.4..-1.55 % of the step against no side streams, -0.7 % against mode 5
+// (same-box A/Bs, profiles/r05_side_streams.txt; round 6 re-measured: profiles/r06_side_streams.txt).  The 48 forward projections share the
+// dominant forward kernel's symbol; as filler their begin-to-end spans are queueing times, so the GEMM launch statistics carry the lane a
+// launch ran on (gemm_profile_lane, set by Runner::OnStream) and bench.py's `roofline` / scripts/rocprof_summary.py price main-stream launches only.
+constexpr int SIDE_STREAMS_DEFAULT = 7;
+
+template <typename T>
+static size_t plan_bytes(const oasr_ctx* c, int B, int S, bool train, int stage) {
+  return Step<T>(c, nullptr, 0, nullptr, B, S, nullptr, train, stage).A.cur;
+}
+extern "C" size_t oasr_workspace_bytes(const oasr_ctx* c, int B, int S, int mode) {
+  if (!c || B <= 0 || S <= 0 || mode < OASR_MODE_INFER || mode > OASR_MODE_TRAIN_DEC) return 0;
+  const bool train = mode != OASR_MODE_INFER;
+  const int stage = mode == OASR_MODE_TRAIN_ENC ? STAGE_ENC : mode == OASR_MODE_TRAIN_DEC ? STAGE_DEC : STAGE_ALL;
+  return OASR_BY_DTYPE(c, plan_bytes, c, B, S, train, stage) + 4096;
+}
+
+template <typename T>
+static int oasr_forward_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int32_t* text_len, int B, int S,
+                            float* logits_out, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, false));
+  OASR_REQUIRE(mel && tokens && workspace && B > 0 && S > 0 && S <= c->S_max, "oasr_forward: bad args (B=%d S=%d)", B, S);
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_INFER), "oasr_forward: workspace too small");
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, false);
+  RC(s.r.encoder_fwd(s.p, mel));
+  RC(s.r.decoder_fwd(s.p, tokens));
+  if (xa_out) RC(copy_xa<T>(c, xa_out, s.p.xa, B, s.r.st));
+  if (logits_out) RC(launch_logits_to_f32(s.p.logits, c->Vp, (long)B * S, c->V, logits_out, s.r.st));
+  return OASR_OK;
+}
+extern "C" int oasr_forward(oasr_ctx* c, const float* mel, const int64_t* tokens, const int32_t* text_len, int B, int S,
+                            float* logits_out, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  OASR_REQUIRE(c, "oasr_forward: null context");
+  return OASR_BY_DTYPE(c, oasr_forward_impl, c, mel, tokens, text_len, B, S, logits_out, xa_out, workspace, workspace_bytes, stream);
+}
+
+// AudioEncoder.forward (olmoasr/model.py:571-623): mel -> xa bf16 [B, n_audio_ctx, d]
+template <typename T>
+static int oasr_encode_impl(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, false));
+  OASR_REQUIRE(mel && xa_out && workspace && B > 0, "oasr_encode: bad args");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, 1, OASR_MODE_INFER), "oasr_encode: workspace too small");
+  Step<T> s(c, workspace, workspace_bytes, stream, B, 1, nullptr, false);
+  RC(s.r.encoder_fwd(s.p, mel));
+  return copy_xa<T>(c, xa_out, s.p.xa, B, s.r.st);
+}
+extern "C" int oasr_encode(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  OASR_REQUIRE(c, "oasr_encode: null context");
+  return OASR_BY_DTYPE(c, oasr_encode_impl, c, mel, B, xa_out, workspace, workspace_bytes, stream);
+}
+
+// TextDecoder.forward without kv_cache (olmoasr/model.py:688-775) on given audio features: OLMoASR.logits(tokens, xa).
+// last_only != 0: logits_out is f32 [B, rows] for position S-1 only (greedy decode step); else f32 [B, S, rows].
+template <typename T>
+static int oasr_decode_logits_impl(oasr_ctx* c, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S,
+                                  int last_only, float* logits_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, false));
+  OASR_REQUIRE(tokens && xa && logits_out && workspace && B > 0 && S > 0 && S <= c->S_max, "oasr_decode_logits: bad args");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_INFER), "oasr_decode_logits: workspace too small");
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, false);
+  RC(copy_xa<T>(c, s.p.xa, xa, B, s.r.st));
+  RC(s.r.decoder_fwd(s.p, tokens, last_only != 0));
+  return launch_logits_to_f32(s.p.logits, c->Vp, last_only ? (long)B : (long)B * S, c->V, logits_out, s.r.st);
+}
+extern "C" int oasr_decode_logits(oasr_ctx* c, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S,
+                                  int last_only, float* logits_out, void* workspace, size_t workspace_bytes, void* stream) {
+  OASR_REQUIRE(c, "oasr_decode_logits: null context");
+  return OASR_BY_DTYPE(c, oasr_decode_logits_impl, c, tokens, xa, text_len, B, S, last_only, logits_out, workspace, workspace_bytes, stream);
+}
+
+// Side streams of the supervised-span step (Runner::side_mode): the setter is a testing hook, OASR_SIDE_STREAMS an experiment switch
+static int g_side_streams = -1;
+static int span_side_streams() {
+  if (g_side_streams >= 0) return g_side_streams;
+  static const int env = [] {
+    const char* e = oasr_experiment_env("OASR_SIDE_STREAMS");
+    return e ? atoi(e) : -1;
+  }();
+  return env >= 0 ? (env & 15) : SIDE_STREAMS_DEFAULT;
+}
+extern "C" int oasr_span_side_streams(void) { return span_side_streams(); }
+extern "C" int oasr_span_set_side_streams(int mode) {
+  OASR_HOOK_GATE("oasr_span_set_side_streams");
+  g_side_streams = mode < 0 ? -1 : (mode & 15);
+  return OASR_OK;
+}
+
+// Same step over a decoder context of S <= n_text_ctx positions (tokens / targets are [B, S]).  With S >= max(text_len)
+// rounded up, the loss, every gradient and therefore the optimizer step are those of the full padded context: positions
+// past the last real token only ever see ignore_index targets, and no real query attends to them (causal mask), so
+// the reference spends their share of the decoder on exact zeros (train_timestamps.py:318-329 pads every sample to 448).
+// xa_in (oasr_train_dec_fwd_bwd): the decoder alone, on the caller's encoder output.
+template <typename T>
+static int oasr_train_fwd_bwd_s_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets,
+                                    const int32_t* text_len, int B, int S, float loss_scale, float inv_accum, float* loss_out,
+                                    int accumulate_loss, float* logits_out, void** ev, void* workspace, size_t workspace_bytes,
+                                    void* stream, const float* mel_clip_max = nullptr, const void* xa_in = nullptr) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_fwd_bwd: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
+  OASR_REQUIRE((mel || xa_in) && tokens && targets && text_len && loss_out && workspace && B > 0, "oasr_train_fwd_bwd: bad args");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, xa_in ? OASR_MODE_TRAIN_DEC : OASR_MODE_TRAIN), "oasr_train_fwd_bwd: workspace too small");
+  const long Md = (long)B * S;
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, xa_in ? STAGE_DEC : STAGE_ALL);
+  auto& p = s.p;
+  auto& r = s.r;
+  r.mel_clip_max = mel_clip_max;  // un-finalized log-mel (oasr_log_mel_raw): the floor / scale lines ride in the encoder's transpose
+  hipStream_t st = r.st;
+  // ---------------- forward ----------------
+  if (xa_in) RC(copy_xa<T>(c, p.xa, xa_in, B, st));
+  else RC(r.encoder_fwd(p, mel));
+  RC(r.decoder_fwd(p, tokens));
+  if (logits_out) RC(launch_logits_to_f32(p.logits, c->Vp, Md, c->V, logits_out, st));
+  RC(launch_count_valid(targets, Md, PAD_ID, c->V, p.n_valid, st));
+  RC(launch_cross_entropy(p.logits, c->Vp, c->V, targets, Md, PAD_ID, loss_scale * inv_accum, p.n_valid, p.row_loss, 1, st));
+  RC(launch_loss_reduce(p.row_loss, Md, p.n_valid, inv_accum, loss_out, accumulate_loss, st));
+  return train_backward<T>(c, r, p, tokens, B, S, ev);
+}
+extern "C" int oasr_train_fwd_bwd_s(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets,
+                                    const int32_t* text_len, int B, int S, float loss_scale, float inv_accum, float* loss_out,
+                                    int accumulate_loss, float* logits_out, void** ev, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  OASR_REQUIRE(c, "oasr_train_fwd_bwd_s: null context");
+  return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, mel, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss,
+                       logits_out, ev, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_fwd_bwd(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                  int B, float loss_scale, float inv_accum, float* loss_out, int accumulate_loss, float* logits_out,
+                                  void** ev, void* workspace, size_t workspace_bytes, void* stream) {
+  return oasr_train_fwd_bwd_s(c, mel, tokens, targets, text_len, B, c ? c->S_max : 0, loss_scale, inv_accum, loss_out, accumulate_loss,
+                              logits_out, ev, workspace, workspace_bytes, stream);
+}
+
+// ---- the supervised-span micro-step ---------------------------------------------------------------------------------------------
+// Same forward (all n_text_ctx positions, as the reference pads them: train_timestamps.py:318-329), same loss, same gradients; what
+// changes is WHERE the decoder's token rows live and how much of the backward is executed.  span_host[b] (host memory, known to the
+// data loader: train_timestamps.py:238-343 builds the token sequences on the host) bounds the positions of sample b that can carry
+// gradient: every target at or past it is ignore_index (train_timestamps.py:1444) and it is >= text_len[b], the first masked key
+// column (:314-315).  Rows of every decoder-side gradient past the span are exactly zero in the reference's computation -- the loss
+// ignores them, no supervised query attends to them -- so:
+//   * the decoder's activations are laid out in 64-position CHUNKS, every chunk with a position < span first (kernels.h:
+//     AttnArgs.q_rows; only the embedding, the attention kernels and the target gather know about the permutation -- LayerNorm, the
+//     GEMMs and their epilogues are row-wise and see plain matrices);
+//   * the backward of the decoder (dgrad / wgrad GEMMs, LayerNorm, attention, cross-entropy gradient, embedding scatter) runs on the
+//     leading R = sum_b ceil64(span[b]) rows only -- on the synthetic lengths 1/3 of the 448 * B.
+// The results differ from oasr_train_fwd_bwd's only by fp32 summation order (weight gradients sum over fewer, re-ordered token rows).
+// A shape the row table cannot chunk takes the plain step (same results).
+static bool span_chunkable(const oasr_ctx* c, int B) { return (c->S_max % 64) == 0 && c->S_max <= 64 * OASR_ROWTAB && B <= 512; }
+
+template <typename T>
+static int oasr_train_fwd_bwd_span_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                       const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
+                                       float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
+                                       size_t workspace_bytes, void* stream, const void* xa_in = nullptr) {
+  const int S = c->S_max;
+  const long Md = (long)B * S;
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, xa_in ? STAGE_DEC : STAGE_ALL);  // (s.r.lane: the lane tag is put back on every path)
+  auto& p = s.p;
+  auto& r = s.r;
+  hipStream_t st = r.st;
+  long R = 0;
+  RC(launch_build_span_tables(span_host, B, S, targets, PAD_ID, p.rows, p.span_dev, p.targets_phys, &R, st));
+  OASR_REQUIRE(R > 0, "oasr_train_fwd_bwd_span: no position of the micro-batch carries gradient (every span is 0)");
+  r.dec_rows = p.rows;
+  r.dec_span = p.span_dev;
+  r.dec_rows_bwd = R;
+  r.dec_rows_fwd = forward_rows == OASR_SPAN_FORWARD_ACTIVE ? R : 0;
+  r.mel_clip_max = mel_clip_max;
+  if (const int mode = span_side_streams()) RC(r.side_begin(mode));
+  // ---------------- forward (every position, unless the caller opted out of the padded ones) ----------------
+  if (xa_in) RC(copy_xa<T>(c, p.xa, xa_in, B, st));
+  else RC(r.encoder_fwd(p, mel));
+  RC(r.decoder_fwd(p, tokens));
+  // loss over the active rows (the other rows' targets are ignore_index: they add nothing to the sum and nothing to the count)
+  RC(launch_count_valid(targets, Md, PAD_ID, c->V, p.n_valid, st));
+  RC(launch_cross_entropy(p.logits, c->Vp, c->V, p.targets_phys, R, PAD_ID, loss_scale * inv_accum, p.n_valid, p.row_loss, 1, st));
+  RC(launch_loss_reduce(p.row_loss, R, p.n_valid, inv_accum, loss_out, accumulate_loss, st));
+  return train_backward<T>(c, r, p, tokens, B, S, ev);
+}
+extern "C" int oasr_train_fwd_bwd_span(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                       const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
+                                       float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(mel && tokens && targets && text_len && span_host && loss_out && workspace && B > 0, "oasr_train_fwd_bwd_span: bad args");
+  OASR_REQUIRE(forward_rows == OASR_SPAN_FORWARD_ALL || forward_rows == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_fwd_bwd_span: forward_rows");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, c->S_max, OASR_MODE_TRAIN), "oasr_train_fwd_bwd_span: workspace too small");
+  if (!span_chunkable(c, B))
+    return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, mel, tokens, targets, text_len, B, c->S_max, loss_scale, inv_accum, loss_out,
+                         accumulate_loss, nullptr, ev, workspace, workspace_bytes, stream, mel_clip_max);
+  return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_span_impl, c, mel, tokens, targets, text_len, span_host, forward_rows, mel_clip_max, B, loss_scale,
+                       inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream);
+}
+
+// ---- the same micro-step cut at the logits, for torch.autograd (OLMoASR.forward in training mode, olmoasr/model.py:856-887 followed
+// by the caller's own loss, train_timestamps.py:1440-1454): oasr_train_fwd returns fp32 logits [B, S, rows] and leaves every saved
+// activation in the workspace; oasr_train_bwd takes d(loss)/d(logits) (fp32, same shape; rounded to the engine's activation type
+// exactly where autocast's backward would round it) and accumulates the parameter gradients into the bound arena.  The workspace
+// must not be used for anything else in between; B, S, tokens and text_len must be the forward's.
+template <typename T>
+static int oasr_train_fwd_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int32_t* text_len, int B, int S,
+                               float* logits_out, void* workspace, size_t workspace_bytes, void* stream) {
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true);
+  RC(s.r.encoder_fwd(s.p, mel));
+  RC(s.r.decoder_fwd(s.p, tokens));
+  return launch_logits_to_f32(s.p.logits, c->Vp, (long)B * S, c->V, logits_out, s.r.st);
+}
+template <typename T>
+static int oasr_train_bwd_impl(oasr_ctx* c, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void** ev,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true);
+  RC(launch_dlogits_from_f32(dlogits, c->V, (long)B * S, c->Vp, s.p.logits, s.r.st));
+  return train_backward<T>(c, s.r, s.p, tokens, B, S, ev);
+}
+extern "C" int oasr_train_fwd(oasr_ctx* c, const float* mel, const int64_t* tokens, const int32_t* text_len, int B, int S, float* logits_out,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_fwd: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
+  OASR_REQUIRE(mel && tokens && text_len && logits_out && workspace && B > 0, "oasr_train_fwd: bad args");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN), "oasr_train_fwd: workspace too small");
+  return OASR_BY_DTYPE(c, oasr_train_fwd_impl, c, mel, tokens, text_len, B, S, logits_out, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_bwd(oasr_ctx* c, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void** ev,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_bwd: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
+  OASR_REQUIRE(tokens && text_len && dlogits && workspace && B > 0, "oasr_train_bwd: bad args");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN), "oasr_train_bwd: workspace too small");
+  return OASR_BY_DTYPE(c, oasr_train_bwd_impl, c, tokens, text_len, dlogits, B, S, ev, workspace, workspace_bytes, stream);
+}
+
+// ---- the training step in two stages, for torch.autograd through model.encoder / model.decoder -------------------
+// Each stage has a workspace plan of its own (OASR_MODE_TRAIN_ENC / _DEC) that holds one forward's saved activations until its backward.
+// The forwards are the fused training forward's (train = true: the MLP epilogue saves GELU'(u)), cut at xa: encode then decode runs the
+// kernels of oasr_train_fwd on the same inputs, plus one copy of xa into the decoder's plan.  The backwards are the two halves of
+// train_backward, started from the caller's d(logits) / d(xa); a requested input gradient (d(xa), d(mel)) is computed even where the mask
+// would prune it, and an all-frozen mask is accepted when one is requested.
+template <typename T>
+static int oasr_train_encode_impl(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  Step<T> s(c, workspace, workspace_bytes, stream, B, 1, nullptr, true, STAGE_ENC);
+  RC(s.r.encoder_fwd(s.p, mel));
+  return copy_xa<T>(c, xa_out, s.p.xa, B, s.r.st);
+}
+template <typename T>
+static int oasr_train_encode_bwd_impl(oasr_ctx* c, const void* dxa, int B, float* dmel_out, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  RC(backward_check(c, dmel_out != nullptr));
+  Step<T> s(c, workspace, workspace_bytes, stream, B, 1, nullptr, true, STAGE_ENC);
+  RC(backward_begin<T>(c, s.r, s.p));
+  int seg = 0;
+  RC(backward_encoder<T>(c, s.r, s.p, (const T*)dxa, B, nullptr, seg, dmel_out));
+  return backward_finish<T>(c, s.r, s.p, nullptr, seg, STAGE_ENC);
+}
+template <typename T>
+static int oasr_train_decode_impl(oasr_ctx* c, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S, float* logits_out,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, STAGE_DEC);
+  RC(copy_xa<T>(c, s.p.xa, xa, B, s.r.st));
+  RC(s.r.decoder_fwd(s.p, tokens));
+  return launch_logits_to_f32(s.p.logits, c->Vp, (long)B * S, c->V, logits_out, s.r.st);
+}
+template <typename T>
+static int oasr_train_decode_bwd_impl(oasr_ctx* c, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S,
+                                      void* dxa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(backward_check(c, dxa_out != nullptr));
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, STAGE_DEC);
+  RC(launch_dlogits_from_f32(dlogits, c->V, (long)B * S, c->Vp, s.p.logits, s.r.st));
+  RC(backward_begin<T>(c, s.r, s.p));
+  int seg = 0;
+  RC(backward_decoder<T>(c, s.r, s.p, tokens, B, S, nullptr, seg, dxa_out != nullptr));
+  // d(xa) in the compute dtype, summed over the decoder layers in block_bwd's order (top layer first)
+  if (dxa_out) RC(copy_xa<T>(c, dxa_out, s.p.gxa, B, s.r.st));
+  return backward_finish<T>(c, s.r, s.p, nullptr, seg, STAGE_DEC);
+}
+extern "C" int oasr_train_encode(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(mel && xa_out && workspace && B > 0, "oasr_train_encode: bad args (mel, xa_out and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, 1, OASR_MODE_TRAIN_ENC), "oasr_train_encode: workspace too small");
+  return OASR_BY_DTYPE(c, oasr_train_encode_impl, c, mel, B, xa_out, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_encode_bwd(oasr_ctx* c, const void* dxa, int B, float* dmel_out, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(dxa && workspace && B > 0, "oasr_train_encode_bwd: bad args (dxa and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, 1, OASR_MODE_TRAIN_ENC), "oasr_train_encode_bwd: workspace too small");
+  return OASR_BY_DTYPE(c, oasr_train_encode_bwd_impl, c, dxa, B, dmel_out, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_decode(oasr_ctx* c, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S, float* logits_out,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_decode: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
+  OASR_REQUIRE(tokens && xa && text_len && logits_out && workspace && B > 0,
+               "oasr_train_decode: bad args (tokens, xa, text_len, logits_out and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_decode: workspace too small");
+  return OASR_BY_DTYPE(c, oasr_train_decode_impl, c, tokens, xa, text_len, B, S, logits_out, workspace, workspace_bytes, stream);
+}
+extern "C" int oasr_train_decode_bwd(oasr_ctx* c, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void* dxa_out,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_decode_bwd: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
+  OASR_REQUIRE(tokens && text_len && dlogits && workspace && B > 0,
+               "oasr_train_decode_bwd: bad args (tokens, text_len, dlogits and workspace are required, B > 0)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_decode_bwd: workspace too small");
+  return OASR_BY_DTYPE(c, oasr_train_decode_bwd_impl, c, tokens, text_len, dlogits, B, S, dxa_out, workspace, workspace_bytes, stream);
+}
+// The fused loss step of the decoder alone, from the caller's encoder output (a frozen encoder whose xa is computed once and reused):
+// oasr_train_fwd_bwd_s / _span with the encoder forward replaced by a copy of xa.  Every segment event is recorded; the encoder's at once,
+// as the frozen-encoder step records them.
+extern "C" int oasr_train_dec_fwd_bwd(oasr_ctx* c, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                      const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
+                                      int accumulate_loss, void** ev, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(xa && tokens && targets && text_len && loss_out && workspace && B > 0 && S > 0 && S <= c->S_max,
+               "oasr_train_dec_fwd_bwd: bad args (xa, tokens, targets, text_len, loss_out and workspace are required, 0 < S <= n_text_ctx)");
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_dec_fwd_bwd: workspace too small");
+  if (c->pr.enc_any) {
+    oasr_set_error("oasr_train_dec_fwd_bwd: an encoder tensor is trainable -- the step from a given xa has no encoder backward (freeze the "
+                   "encoder, or use oasr_train_fwd_bwd*)");
+    return OASR_ESTATE;
+  }
+  if (span_host && span_chunkable(c, B)) {
+    OASR_REQUIRE(S == c->S_max, "oasr_train_dec_fwd_bwd: a span step covers the whole context (S = %d, n_text_ctx = %d)", S, c->S_max);
+    OASR_REQUIRE(span_forward == OASR_SPAN_FORWARD_ALL || span_forward == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_dec_fwd_bwd: span_forward");
+    return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_span_impl, c, nullptr, tokens, targets, text_len, span_host, span_forward, nullptr, B, loss_scale,
+                         inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, xa);
+  }
+  // (no span, or no chunking for this shape: the plain step, same results)
+  return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, nullptr, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss,
+                       nullptr, ev, workspace, workspace_bytes, stream, nullptr, xa);
+}

@@ -128,7 +128,7 @@ struct AttnArgsT {
   // dK/dV kernel stops at the last such tile (decoder side of a padded batch: the loss ignores the padded positions, their d_o rows
   // are exactly zero and contribute exactly nothing -- three quarters of the 448 positions on average).  Results are bit-identical.
   int32_t* qtile_flags;
-  // ---- chunked token rows (the decoder side of a span-limited training step, engine.hip "supervised span") -----------------
+  // ---- chunked token rows (the decoder side of a span-limited training step, engine_step.hip "supervised span") -----------------
   // q_rows / k_rows: optional int32 [B][OASR_ROWTAB]: entry c = first token row (relative to the tensor base pointers, batch
   // strides unused) of the 64-position chunk c of sample b; q_rows addresses q / o / o_lo / d_o / dq, k_rows k / v / dk / dv.
   // lse / delta / qtile_flags keep their logical [B, H, Tq] indexing.  Needs Tq (Tk) % 64 == 0 and <= 64 * OASR_ROWTAB.
@@ -209,7 +209,7 @@ int launch_embedding_fwd(const int64_t* tok, const float* E, const float* pos, b
 // dE[tok] += dx (skipping pad_id), dpos[s] += sum_b dx;  span (optional, with rows): positions s >= span[b] hold no gradient and are skipped
 int launch_embedding_bwd(const int64_t* tok, const bf16_t* dx, float* dE, float* dpos, int B, int S, int d, long pad_id, long n_embed,
                          hipStream_t s, const int32_t* rows = nullptr, const int32_t* span = nullptr);
-// Supervised-span tables of one decoder micro-batch (engine.hip): span_host[b] (host, <= S) -> on the device
+// Supervised-span tables of one decoder micro-batch (engine_step.hip): span_host[b] (host, <= S) -> on the device
 //   rows [B][OASR_ROWTAB]: the chunk-row table -- the active chunks (64*c < span[b]) of all samples first, position-block-major,
 //                          then the inactive ones; span_dev [B] = span rounded up to 64; targets_phys [B*S]: targets in row order
 // Returns the number of active token rows through *active_rows (host).  S % 64 == 0, S <= 64 * OASR_ROWTAB, B <= 512.
