@@ -610,7 +610,7 @@ static int ensure_tables(int device, MelTables** t_out) {
         for (int sl = 0; sl < QMEL_NSLOT[m]; ++sl)
           for (int l = 0; l < 4; ++l) {
             const int k = K1[l] + 4 * (QMEL_K2LO[m] + sl);
-            qt[(size_t)QTAB_MEL + 4 * (QMEL_OFF[m] + sl) + l] = k <= 199 ? 0.25f * fb[m * NFREQ + k] : 0.f;  // (P holds 4 |X|^2)
+            qt[(size_t)QTAB_MEL + 4 * (QMEL_OFF[m] + sl) + l] = k <= 199 ? (float)(1 << QLOG_SHIFT) * 0.25f * fb[m * NFREQ + k] : 0.f;  // (P holds 4 |X|^2; 2^QLOG_SHIFT: logmel_quad.h)
           }
       }
       OASR_CHECK_HIP(hipMalloc((void**)&t.quad_tab, sizeof(float) * QTAB));

@@ -22,6 +22,7 @@
 #include "logmel_quad_tables.h"
 
 constexpr int QT = 64;                              // frames per workgroup
+constexpr int QLOG_SHIFT = 16;                      // the mel weights carry 2^16: see the logarithm at the end of the mel phase
 constexpr int QNS = QT * HOP + (NFFT - HOP);        // samples of 64 frames: 10480
 constexpr int QTAB_WIN = 0, QTAB_TW200 = 400, QTAB_TW400 = 800, QTAB_MEL = 1200, QTAB = 1200 + 4 * QMEL_SLOTS;  // floats
 
@@ -311,9 +312,15 @@ __global__ __launch_bounds__(256, QUAD_WAVES) void logmel_quad(const PCM* __rest
         s4[decltype(ic)::value] = a;
       });
       const float mine = (QUAD_ABLATE & 8) ? (s4[0] + s4[1]) + (s4[2] + s4[3]) : bsel(m_hi, bsel(m_odd, s4[3], s4[2]), bsel(m_odd, s4[1], s4[0]));
-      // log10 = log2 * log10(2) on the hardware log2 (v_log_f32, ~1 ulp; the argument is a normal number >= 1e-10): libm's log10f spends a dozen
-      // VALU on denormal scaling and a correction step this kernel has no use for (20 values per lane)
-      val[j] = __builtin_amdgcn_logf(fmaxf(mine, 1e-10f)) * 0.30102999566398120f;
+      // log10 = log2 * log10(2) on the hardware log2 (v_log_f32, ~1 ulp OF ITS RESULT): libm's log10f spends a dozen VALU on denormal scaling
+      // and a correction step this kernel has no use for (20 values per lane).  The mel weights carry a factor 2^QLOG_SHIFT (exact), taken out
+      // again inside the fma (-16 fl(log10 2) is exact; the product with log10(2) is not rounded on its own).  The hardware result then lies
+      // in [-17.3, 30] instead of [-33.3, 14]: one ulp of it is 1.9e-6 instead of 3.8e-6 for powers below 2.3e-10, the cells next to the clamp,
+      // where 3.8e-6 is a relative 2.6e-6 of the power -- most of the 2^-18 the tests allow beside the transform's error.  The loud side pays:
+      // powers of 1 and above see 1.9e-6 where they saw at most 9.5e-7, a relative 1.3e-6 of the power (0.35 of that allowance).
+      // whisper's clamp at 1e-10 is applied to the LOGARITHM, so that a silent cell is exactly -10 and finalises to exactly -1.5 (the product
+      // fl(log2(1e-10f)) * fl(log10 2) is one ulp below -10); max(log10 p, -10) is the same function, log2(0) = -inf included
+      val[j] = fmaxf(fmaf(__builtin_amdgcn_logf(mine), 0.30102999566398120f, -(float)QLOG_SHIFT * 0.30102999566398120f), -10.0f);
       if constexpr (j % 4 == 3) __builtin_amdgcn_sched_barrier(0);
     });
     if (live) {
