@@ -221,6 +221,25 @@ int oasr_train_decode_bwd(oasr_ctx*, const int64_t* tokens, const int32_t* text_
 int oasr_train_dec_fwd_bwd(oasr_ctx*, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
                            const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
                            int accumulate_loss, void** seg_events, void* workspace, size_t workspace_bytes, void* stream);
+/* The two span steps with the teacher-forced predictions on request (the reference's gen_pred argmax, train_timestamps.py:1077, without
+ * leaving the span step and without an fp32 logits tensor).  pred_out: NULL (then these ARE oasr_train_fwd_bwd_span / oasr_train_dec_fwd_bwd,
+ * launch for launch), or device int32 [B, n_text_ctx]:
+ *     pred_out[b, s] = argmax over c < n_vocab + 1 of logits[b, s, c]   for s < span_host[b] rounded up to 64 -- the rows every forward
+ *                      mode computes; the lowest index wins among equal maxima, the padded columns of the tied head are never candidates
+ *     pred_out[b, s] = -1                                               elsewhere
+ * One extra kernel between the decoder forward and the cross-entropy (which overwrites the logits with their gradient): each active row is
+ * read once in the compute dtype, 4 bytes are written; it addresses rows through the chunk-row table, so the output is in logical order.
+ * Loss and gradients are those of the entry without pred_out.  With pred_out the dec entry needs span_host, and a shape the row table
+ * cannot chunk (n_text_ctx not a multiple of 64, or B > 512) is refused (OASR_EINVAL) before any launch instead of taking the plain step.
+ * Entry points only: OASR_ABI_VERSION is unchanged, a library without them is refused by the oasr_sizeof_edit_args check below. */
+int oasr_train_fwd_bwd_span_pred(oasr_ctx*, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                 const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
+                                 float inv_accum, float* loss_out, int accumulate_loss, void** seg_events, void* workspace,
+                                 size_t workspace_bytes, int32_t* pred_out, void* stream);
+int oasr_train_dec_fwd_bwd_pred(oasr_ctx*, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
+                                int accumulate_loss, void** seg_events, void* workspace, size_t workspace_bytes, int32_t* pred_out,
+                                void* stream);
 
 /* Frozen parameters (torch's requires_grad == False): mask holds one byte per tensor in oasr_param_info order, nonzero = trainable;
  * the default is all ones.  From then on the backward entries (oasr_train_fwd_bwd, _s, _span, oasr_train_bwd) neither launch nor
@@ -353,6 +372,38 @@ typedef struct oasr_specaug {
 size_t oasr_sizeof_specaug(void);
 int oasr_spec_augment(float* mel, int B, int n_mels, int T, const oasr_specaug* policy, uint64_t seed, uint64_t first_clip, void* stream);
 int oasr_spec_augment_plan(const oasr_specaug* policy, uint64_t seed, uint64_t clip, int n_mels, int T, int32_t* freq_iv, int32_t* time_iv);
+/* Token error counts (csrc/editdist.hip; the rule itself: csrc/editdist_core.h): the batched edit distance between hypothesis and reference
+ * token rows with its split into substitutions, deletions, insertions and hits -- what calc_pred_wer (train_timestamps.py:1125) reports at
+ * word level.  Both entries add entry points only: OASR_ABI_VERSION is unchanged, and a binding checks oasr_sizeof_edit_args like
+ * oasr_sizeof_specaug.
+ *
+ * hyp int32 [B, Lh] (row stride ld_hyp), ref int32 [B, Lr] (row stride ld_ref), unit column stride; hyp_len / ref_len int32 [B] with
+ * 0 <= length <= min(OASR_EDIT_MAX_LEN, row width); tokens past a length are never read.  out int32 [B, 4], contiguous = (S, D, I, H).
+ * Cell (i, j) covers hyp prefix i and ref prefix j and carries (S, D, I); its cost is S + D + I.
+ *     borders    (0, j) = (0, j, 0)      (i, 0) = (0, 0, i)
+ *     interior   cd = cost(i-1, j-1) + (hyp[i-1] != ref[j-1]),   cl = cost(i, j-1) + 1 (deletion: the ref token is missing from hyp),
+ *                cu = cost(i-1, j) + 1 (insertion); the minimum wins, on a tie the diagonal, then the deletion, then the insertion; the
+ *                cell inherits the chosen predecessor's counts and adds its own step
+ * The answer is cell (hyp_len, ref_len) and H = ref_len - S - D.  S + D + I is the Levenshtein distance, which is unique; its split depends
+ * on the tie rule, which is this library's own (a backtracing aligner such as jiwer's may split a tie differently).  Known answers:
+ *     [] -> [1,2,3]: (0,3,0,0)   [1,2,3] -> []: (0,0,3,0)   [1,9,3] -> [1,2,3]: (1,0,0,2)   [1,3] -> [1,2,3]: (0,1,0,2)
+ *     [1,2,2,3] -> [1,2,3]: (0,0,1,3)   [2,1] -> [1,2]: (2,0,0,0)   [1,1,2] -> [1,2]: (0,0,1,2)   [0,1,0,1] -> [1,0,1,0]: (0,1,1,3)
+ *
+ * oasr_edit_counts: device pointers, one launch on `stream`, one workgroup per pair; nothing but out[b, 0:4] is written.  The lengths live
+ * on the device, so the host cannot refuse them: a pair whose length is outside the contract gets out[b] = (-1, -1, -1, -1) and none of its
+ * tokens is read.  Everything else (null pointers, B < 1, a row stride below the row width) is OASR_EINVAL before the launch.
+ * oasr_edit_counts_host: HOST function (no GPU call, host pointers), the same rule from the same text; a length outside the contract is
+ * OASR_EINVAL before anything is written. */
+#define OASR_EDIT_MAX_LEN 1023
+typedef struct oasr_edit_args {
+  const int32_t *hyp, *ref, *hyp_len, *ref_len;
+  int32_t* out;
+  int64_t ld_hyp, ld_ref;
+  int32_t B, Lh, Lr, reserved;
+} oasr_edit_args;
+size_t oasr_sizeof_edit_args(void);
+int oasr_edit_counts(const oasr_edit_args*, void* stream);
+int oasr_edit_counts_host(const oasr_edit_args*);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 int oasr_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);

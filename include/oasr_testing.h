@@ -107,6 +107,14 @@ int oasr_test_layernorm_bwd(const void* dy, const void* x, const float* gamma, c
 int oasr_test_dtw_host(const float* cost, int64_t ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
                        void* workspace);
 
+/* tests (tests/test_gpu_train_pred.py): the prediction kernel of oasr_train_fwd_bwd_span_pred on a caller's matrix and tables, like the glue
+ * operators above (no process state, no opt-in).  logits: [n_rows][ld] in `dtype`, ld >= V (16-byte aligned rows that hold V rounded up to a 16-byte piece are read in such pieces, others column by column);
+ * rows: device int32 [B][OASR_ROWTAB] chunk-row table; span: device int32 [B], multiples of 64, <= S; pred_out: device int32 [B][S]:
+ *     pred_out[b, s] = argmax over c < V of logits[rows[b][s >> 6] + (s & 63)][c] for s < span[b] (lowest index among equal maxima), else -1;
+ * a table entry that points outside [0, n_rows) also gives -1 (the row is not read). */
+int oasr_test_argmax_rows(const void* logits, int dtype, int64_t ld, int V, int64_t n_rows, const int32_t* rows, const int32_t* span, int B, int S,
+                          int32_t* pred_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,9 +56,16 @@ class SpecAug(C.Structure):  # include/oasr.h: oasr_specaug
     _fields_ = [("freq_masks", C.c_int32), ("freq_width", C.c_int32), ("time_masks", C.c_int32), ("time_width", C.c_int32), ("fill", C.c_float)]
 
 
+class EditArgs(C.Structure):  # include/oasr.h: oasr_edit_args
+    MAX_LEN = 1023  # OASR_EDIT_MAX_LEN
+    _fields_ = [("hyp", C.c_void_p), ("ref", C.c_void_p), ("hyp_len", C.c_void_p), ("ref_len", C.c_void_p), ("out", C.c_void_p),
+                ("ld_hyp", C.c_int64), ("ld_ref", C.c_int64), ("B", C.c_int32), ("Lh", C.c_int32), ("Lr", C.c_int32), ("reserved", C.c_int32)]
+
+
 DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_audio_ctx
 # The word-timestamp operators (oasr_alignment_matrix, oasr_dtw, oasr_test_dtw_host) add entry points without a new ABI generation: a library built before them is refused by the oasr_sizeof_align_args check in lib().
 # SpecAugment (oasr_spec_augment, oasr_spec_augment_plan) came the same way: entry points only, a stale library refused by the oasr_sizeof_specaug check in lib().
+# Token error counts (oasr_edit_counts, oasr_edit_counts_host) and the span steps with predictions (oasr_train_fwd_bwd_span_pred, oasr_train_dec_fwd_bwd_pred, oasr_test_argmax_rows) likewise: a stale library is refused by the oasr_sizeof_edit_args check in lib().
 ABI_VERSION = 215  # include/oasr.h: OASR_ABI_VERSION (215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
@@ -106,6 +113,7 @@ def _declare(lib):
         "oasr_train_fwd_bwd": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, vp, i32, vp, vp, vp, sz, vp]),
         "oasr_train_fwd_bwd_s": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, i32, vp, vp, vp, sz, vp]),
         "oasr_train_fwd_bwd_span": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, vp, i32, vp, vp, sz, vp]),
+        "oasr_train_fwd_bwd_span_pred": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, vp, i32, vp, vp, sz, vp, vp]),
         "oasr_log_mel_raw": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
         "oasr_sizeof_attn_args": (sz, []),
         "oasr_test_span_tables": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp]),
@@ -130,6 +138,7 @@ def _declare(lib):
         "oasr_train_decode": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_train_decode_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_train_dec_fwd_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, vp, vp, sz, vp]),
+        "oasr_train_dec_fwd_bwd_pred": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, vp, vp, sz, vp, vp]),
         "oasr_set_trainable": (i32, [vp, vp, i32]),
         "oasr_optim_step": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, i64, vp, vp, vp]),
         "oasr_grad_sumsq_range": (i32, [vp, i64, i64, vp, vp, vp]),
@@ -151,6 +160,10 @@ def _declare(lib):
         "oasr_sizeof_specaug": (sz, []),
         "oasr_spec_augment": (i32, [vp, i32, i32, i32, C.POINTER(SpecAug), C.c_uint64, C.c_uint64, vp]),
         "oasr_spec_augment_plan": (i32, [C.POINTER(SpecAug), C.c_uint64, C.c_uint64, i32, i32, vp, vp]),
+        "oasr_sizeof_edit_args": (sz, []),
+        "oasr_edit_counts": (i32, [C.POINTER(EditArgs), vp]),
+        "oasr_edit_counts_host": (i32, [C.POINTER(EditArgs)]),
+        "oasr_test_argmax_rows": (i32, [vp, i32, i64, i32, i64, vp, vp, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
         "oasr_pick_tokens": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, vp]),
@@ -214,6 +227,9 @@ def lib():
         if int(handle.oasr_sizeof_specaug()) != C.sizeof(SpecAug):
             raise NativeError(f"{LIB_PATH}: oasr_specaug of {int(handle.oasr_sizeof_specaug())} bytes, this binding passes "
                               f"{C.sizeof(SpecAug)} -- rebuild (__graft_entry__.build())")
+        if int(handle.oasr_sizeof_edit_args()) != C.sizeof(EditArgs):
+            raise NativeError(f"{LIB_PATH}: oasr_edit_args of {int(handle.oasr_sizeof_edit_args())} bytes, this binding passes "
+                              f"{C.sizeof(EditArgs)} -- rebuild (__graft_entry__.build())")
         _lib, EXPORTS = handle, exports
     return _lib
 

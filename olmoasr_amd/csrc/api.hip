@@ -198,6 +198,8 @@ extern "C" int oasr_spec_augment(float* mel, int B, int n_mels, int T, const oas
   return launch_spec_augment(mel, B, n_mels, T, policy, seed, first_clip, (hipStream_t)stream);
 }
 
+extern "C" int oasr_edit_counts(const oasr_edit_args* a, void* stream) { return launch_edit_counts(a, (hipStream_t)stream); }
+
 extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                                      int64_t* targets_rows_out, int64_t* active_rows_out, void* stream) {
   OASR_REQUIRE(active_rows_out, "oasr_test_span_tables: null");
@@ -288,6 +290,14 @@ extern "C" int oasr_test_layernorm_bwd(const void* dy, const void* x, const floa
                                 (long)rows, d, (hipStream_t)stream);
   return launch_layernorm_bwd((const float*)dy, (const float*)x, gamma, mean, rstd, (const float*)dres, (float*)dx, dgamma, dbeta, dsum, (long)rows, d,
                               (hipStream_t)stream);
+}
+
+extern "C" int oasr_test_argmax_rows(const void* logits, int dtype, int64_t ld, int V, int64_t n_rows, const int32_t* rows, const int32_t* span, int B,
+                                     int S, int32_t* pred_out, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_argmax_rows");
+  if (dtype == OASR_DTYPE_BF16)
+    return launch_argmax_rows((const bf16_t*)logits, (long)ld, V, (long)n_rows, rows, span, B, S, pred_out, (hipStream_t)stream);
+  return launch_argmax_rows((const float*)logits, (long)ld, V, (long)n_rows, rows, span, B, S, pred_out, (hipStream_t)stream);
 }
 
 extern "C" int oasr_cross_entropy(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,

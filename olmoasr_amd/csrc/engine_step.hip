@@ -155,7 +155,7 @@ template <typename T>
 static int oasr_train_fwd_bwd_span_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
                                        const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
                                        float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
-                                       size_t workspace_bytes, void* stream, const void* xa_in = nullptr) {
+                                       size_t workspace_bytes, void* stream, const void* xa_in = nullptr, int32_t* pred_out = nullptr) {
   const int S = c->S_max;
   const long Md = (long)B * S;
   Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, xa_in ? STAGE_DEC : STAGE_ALL);  // (s.r.lane: the lane tag is put back on every path)
@@ -175,25 +175,40 @@ static int oasr_train_fwd_bwd_span_impl(oasr_ctx* c, const float* mel, const int
   if (xa_in) RC(copy_xa<T>(c, p.xa, xa_in, B, st));
   else RC(r.encoder_fwd(p, mel));
   RC(r.decoder_fwd(p, tokens));
+  // predictions on request, while the logits are still logits (the cross-entropy below overwrites them with their gradient)
+  if (pred_out) RC(launch_argmax_rows(p.logits, c->Vp, c->V, Md, p.rows, p.span_dev, B, S, pred_out, st));
   // loss over the active rows (the other rows' targets are ignore_index: they add nothing to the sum and nothing to the count)
   RC(launch_count_valid(targets, Md, PAD_ID, c->V, p.n_valid, st));
   RC(launch_cross_entropy(p.logits, c->Vp, c->V, p.targets_phys, R, PAD_ID, loss_scale * inv_accum, p.n_valid, p.row_loss, 1, st));
   RC(launch_loss_reduce(p.row_loss, R, p.n_valid, inv_accum, loss_out, accumulate_loss, st));
   return train_backward<T>(c, r, p, tokens, B, S, ev);
 }
-extern "C" int oasr_train_fwd_bwd_span(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                       const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
-                                       float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
+static int span_pred_refuse(const oasr_ctx* c, int B) {  // pred_out is indexed through the row table: no plain-step fall-back with it
+  OASR_REQUIRE(span_chunkable(c, B), "pred_out needs the chunk-row table: n_text_ctx = %d must be a multiple of 64 (<= %d) and B = %d <= 512",
+               c->S_max, 64 * OASR_ROWTAB, B);
+  return OASR_OK;
+}
+extern "C" int oasr_train_fwd_bwd_span_pred(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                            const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
+                                            float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
+                                            size_t workspace_bytes, int32_t* pred_out, void* stream) {
   RC(check_bound(c, true));
   OASR_REQUIRE(mel && tokens && targets && text_len && span_host && loss_out && workspace && B > 0, "oasr_train_fwd_bwd_span: bad args");
   OASR_REQUIRE(forward_rows == OASR_SPAN_FORWARD_ALL || forward_rows == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_fwd_bwd_span: forward_rows");
   OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, c->S_max, OASR_MODE_TRAIN), "oasr_train_fwd_bwd_span: workspace too small");
+  if (pred_out) RC(span_pred_refuse(c, B));
   if (!span_chunkable(c, B))
     return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, mel, tokens, targets, text_len, B, c->S_max, loss_scale, inv_accum, loss_out,
                          accumulate_loss, nullptr, ev, workspace, workspace_bytes, stream, mel_clip_max);
   return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_span_impl, c, mel, tokens, targets, text_len, span_host, forward_rows, mel_clip_max, B, loss_scale,
-                       inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream);
+                       inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, nullptr, pred_out);
+}
+extern "C" int oasr_train_fwd_bwd_span(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                       const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
+                                       float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  return oasr_train_fwd_bwd_span_pred(c, mel, tokens, targets, text_len, span_host, forward_rows, mel_clip_max, B, loss_scale, inv_accum, loss_out,
+                                      accumulate_loss, ev, workspace, workspace_bytes, nullptr, stream);
 }
 
 // ---- the same micro-step cut at the logits, for torch.autograd (OLMoASR.forward in training mode, olmoasr/model.py:856-887 followed
@@ -309,9 +324,10 @@ extern "C" int oasr_train_decode_bwd(oasr_ctx* c, const int64_t* tokens, const i
 // The fused loss step of the decoder alone, from the caller's encoder output (a frozen encoder whose xa is computed once and reused):
 // oasr_train_fwd_bwd_s / _span with the encoder forward replaced by a copy of xa.  Every segment event is recorded; the encoder's at once,
 // as the frozen-encoder step records them.
-extern "C" int oasr_train_dec_fwd_bwd(oasr_ctx* c, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                      const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
-                                      int accumulate_loss, void** ev, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int oasr_train_dec_fwd_bwd_pred(oasr_ctx* c, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                           const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum,
+                                           float* loss_out, int accumulate_loss, void** ev, void* workspace, size_t workspace_bytes,
+                                           int32_t* pred_out, void* stream) {
   RC(check_bound(c, true));
   OASR_REQUIRE(xa && tokens && targets && text_len && loss_out && workspace && B > 0 && S > 0 && S <= c->S_max,
                "oasr_train_dec_fwd_bwd: bad args (xa, tokens, targets, text_len, loss_out and workspace are required, 0 < S <= n_text_ctx)");
@@ -321,13 +337,23 @@ extern "C" int oasr_train_dec_fwd_bwd(oasr_ctx* c, const void* xa, const int64_t
                    "encoder, or use oasr_train_fwd_bwd*)");
     return OASR_ESTATE;
   }
+  if (pred_out) {
+    OASR_REQUIRE(span_host, "oasr_train_dec_fwd_bwd_pred: pred_out comes with span_host (the predictions cover the span's rows)");
+    RC(span_pred_refuse(c, B));
+  }
   if (span_host && span_chunkable(c, B)) {
     OASR_REQUIRE(S == c->S_max, "oasr_train_dec_fwd_bwd: a span step covers the whole context (S = %d, n_text_ctx = %d)", S, c->S_max);
     OASR_REQUIRE(span_forward == OASR_SPAN_FORWARD_ALL || span_forward == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_dec_fwd_bwd: span_forward");
     return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_span_impl, c, nullptr, tokens, targets, text_len, span_host, span_forward, nullptr, B, loss_scale,
-                         inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, xa);
+                         inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, xa, pred_out);
   }
   // (no span, or no chunking for this shape: the plain step, same results)
   return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, nullptr, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss,
                        nullptr, ev, workspace, workspace_bytes, stream, nullptr, xa);
+}
+extern "C" int oasr_train_dec_fwd_bwd(oasr_ctx* c, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
+                                      const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
+                                      int accumulate_loss, void** ev, void* workspace, size_t workspace_bytes, void* stream) {
+  return oasr_train_dec_fwd_bwd_pred(c, xa, tokens, targets, text_len, span_host, span_forward, B, S, loss_scale, inv_accum, loss_out,
+                                     accumulate_loss, ev, workspace, workspace_bytes, nullptr, stream);
 }

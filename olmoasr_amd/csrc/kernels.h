@@ -280,6 +280,18 @@ int launch_alignment_matrix(const oasr_align_args* a, void* workspace, size_t wo
 int launch_dtw(const float* cost, long ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
                void* workspace, size_t workspace_bytes, hipStream_t s);
 
+// ---- token error counts (editdist.hip; the contract: include/oasr.h at oasr_edit_counts, the rule: editdist_core.h) ---------------------
+struct oasr_edit_args;
+int launch_edit_counts(const oasr_edit_args* a, hipStream_t s);
+
+// ---- teacher-forced predictions of the span step (argmax.hip) --------------------------------------------------------------------------
+// pred[b, s] = argmax_c<V logits[rows[b][s >> 6] + (s & 63)][c] (lowest index among equal maxima) for s < span[b], else -1; logits
+// [n_rows][ld], rows int32 [B][OASR_ROWTAB], span int32 [B] (multiples of 64), pred int32 [B][S].  Reads each active row once.
+int launch_argmax_rows(const bf16_t* logits, long ld, int V, long n_rows, const int32_t* rows, const int32_t* span, int B, int S, int32_t* pred,
+                       hipStream_t s);
+int launch_argmax_rows(const float* logits, long ld, int V, long n_rows, const int32_t* rows, const int32_t* span, int B, int S, int32_t* pred,
+                       hipStream_t s);
+
 // ---- SpecAugment (specaug.hip; the policy block and the rule: include/oasr.h, specaug_core.h) ------------------------------------
 // mel fp32 [B, n_mels, T] in place: the seeded masks of clips first_clip .. first_clip + B - 1 set to policy->fill, nothing else written
 struct oasr_specaug;

@@ -1041,7 +1041,7 @@ class OLMoASR(nn.Module):
                           accumulation_steps: int = 1, loss_out: Optional[Tensor] = None, accumulate_loss: bool = False,
                           return_logits: bool = False, segment_events=None, text_ctx: Optional[int] = None, span=None,
                           span_forward: Optional[bool] = None, mel_clip_max: Optional[Tensor] = None,
-                          audio_features: Optional[Tensor] = None):
+                          audio_features: Optional[Tensor] = None, pred_out: Optional[Tensor] = None):
         """forward + F.cross_entropy(ignore_index=51864)/accumulation_steps + backward of (loss * loss_scale)
         (train_timestamps.py:1440-1454).  Gradients accumulate into ``flat_grads``.  Returns (loss tensor [1], logits|None).
 
@@ -1065,7 +1065,21 @@ class OLMoASR(nn.Module):
         (``oasr_train_dec_fwd_bwd``): the decoder's forward, loss and backward only -- for features computed once (``embed_audio``, or
         ``model.encoder(mel)`` in training mode for the bits the fused step computes) and reused every epoch.  ``span``, ``span_forward``,
         ``segment_events``, ``loss_scale`` and ``accumulation_steps`` work as above; an encoder parameter that requires grad, ``mel_clip_max``,
-        ``text_ctx`` and ``return_logits`` raise ``ValueError``."""
+        ``text_ctx`` and ``return_logits`` raise ``ValueError``.
+
+        ``pred_out`` (with ``span``; ``mel`` or ``audio_features``): a contiguous int32 [B, n_text_ctx] device tensor that receives the
+        teacher-forced predictions (``oasr_train_fwd_bwd_span_pred``): ``argmax_c logits[b, s, c]`` over the n_vocab + 1 columns (lowest index
+        among equal maxima) at every position ``s`` below ``span[b]`` rounded up to 64 -- the rows every forward mode computes -- and -1
+        elsewhere.  One kernel between the decoder forward and the loss; no fp32 logits exist.  Loss and gradients are unchanged.  Without
+        ``span``, or with ``return_logits`` / ``text_ctx``, it raises ``ValueError``."""
+        if pred_out is not None:
+            if span is None or span is False or return_logits or text_ctx is not None:
+                raise ValueError("loss_and_backward(pred_out=...): the predictions come from the span step -- pass span=, and neither "
+                                 "return_logits nor text_ctx")
+            N.require_gpu(pred_out, "pred_out")
+            if not (pred_out.dtype == torch.int32 and tuple(pred_out.shape) == tuple(tokens.shape) and pred_out.is_contiguous()
+                    and tokens.shape[1] == self.dims.n_text_ctx):
+                raise ValueError("loss_and_backward(pred_out=...): pred_out must be a contiguous int32 [B, n_text_ctx] tensor")
         if audio_features is not None:
             if mel is not None:
                 raise ValueError("loss_and_backward: pass mel=None with audio_features (the step starts from the encoder output)")
@@ -1115,6 +1129,13 @@ class OLMoASR(nn.Module):
                 span_h = span_h.to(torch.int32).contiguous()
                 assert span_h.numel() == B and not span_h.is_cuda
             with torch.cuda.device(dev):
+                if pred_out is not None:
+                    N.check(N.lib().oasr_train_dec_fwd_bwd_pred(self._ctx, N.ptr(xa), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
+                                                                C.c_void_p(span_h.data_ptr()), int(span_forward is None or bool(span_forward)), B, S,
+                                                                float(loss_scale), 1.0 / accumulation_steps, N.ptr(loss_out), int(accumulate_loss),
+                                                                ev, N.ptr(ws), ws.numel(), N.ptr(pred_out), N.stream_ptr()),
+                            "oasr_train_dec_fwd_bwd_pred")
+                    return loss_out, None
                 N.check(N.lib().oasr_train_dec_fwd_bwd(self._ctx, N.ptr(xa), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
                                                        None if span_h is None else C.c_void_p(span_h.data_ptr()),
                                                        int(span_forward is None or bool(span_forward)), B, S, float(loss_scale),
@@ -1132,6 +1153,13 @@ class OLMoASR(nn.Module):
                 mel_clip_max = mel_clip_max.float().contiguous()
                 assert mel_clip_max.numel() == B
             with torch.cuda.device(mel.device):
+                if pred_out is not None:
+                    N.check(N.lib().oasr_train_fwd_bwd_span_pred(self._ctx, N.ptr(mel), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
+                                                                 C.c_void_p(span_h.data_ptr()), int(span_forward is None or bool(span_forward)),
+                                                                 N.ptr(mel_clip_max), B, float(loss_scale), 1.0 / accumulation_steps,
+                                                                 N.ptr(loss_out), int(accumulate_loss), ev, N.ptr(ws), ws.numel(), N.ptr(pred_out),
+                                                                 N.stream_ptr()), "oasr_train_fwd_bwd_span_pred")
+                    return loss_out, None
                 N.check(N.lib().oasr_train_fwd_bwd_span(self._ctx, N.ptr(mel), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
                                                         C.c_void_p(span_h.data_ptr()), int(span_forward is None or bool(span_forward)), N.ptr(mel_clip_max), B,
                                                         float(loss_scale),

@@ -360,6 +360,66 @@ def dtw_host(cost, negate=False):
     return path[:ln].to(torch.int64), path[P:P + ln].to(torch.int64)
 
 
+def _edit_args(hyp, hyp_len, ref, ref_len, cuda):
+    """Checks and converts the operands of ``edit_counts`` / ``edit_counts_host``: (EditArgs, out, keep-alive tuple)."""
+    what = "edit_counts" if cuda else "edit_counts_host"
+    for t, nm in ((hyp, "hyp"), (ref, "ref"), (hyp_len, "hyp_len"), (ref_len, "ref_len")):
+        if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64)):
+            raise ValueError(f"{what}: {nm} must be an int32 / int64 tensor")
+        if t.is_cuda != cuda:
+            raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor")
+        if t.device != hyp.device:
+            raise ValueError(f"{what}: operands on different devices")
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp_len.dim() != 1 or ref_len.dim() != 1:
+        raise ValueError(f"{what}: hyp [B, Lh], ref [B, Lr], hyp_len [B], ref_len [B]")
+    B, Lh = hyp.shape
+    Lr = ref.shape[1]
+    if B < 1 or ref.shape[0] != B or hyp_len.numel() != B or ref_len.numel() != B:
+        raise ValueError(f"{what}: B mismatch (hyp {tuple(hyp.shape)}, ref {tuple(ref.shape)}, hyp_len {hyp_len.numel()}, ref_len {ref_len.numel()}; B >= 1)")
+
+    def rows(t):  # int32, unit column stride, rows that do not overlap (any row stride beyond that: a view is passed as it is)
+        t = t.to(torch.int32)
+        ok = (t.shape[1] <= 1 or t.stride(1) == 1) and (B == 1 or t.stride(0) >= t.shape[1])
+        return t if ok else t.contiguous()
+    hyp, ref = rows(hyp), rows(ref)
+    hyp_len, ref_len = hyp_len.to(torch.int32).contiguous(), ref_len.to(torch.int32).contiguous()
+    out = torch.empty(B, 4, dtype=torch.int32, device=hyp.device)
+    a = N.EditArgs()
+    a.hyp, a.ref, a.hyp_len, a.ref_len, a.out = hyp.data_ptr(), ref.data_ptr(), hyp_len.data_ptr(), ref_len.data_ptr(), out.data_ptr()
+    a.ld_hyp, a.ld_ref = (hyp.stride(0) if B > 1 else Lh), (ref.stride(0) if B > 1 else Lr)
+    a.B, a.Lh, a.Lr = B, Lh, Lr
+    return a, out, (hyp, ref, hyp_len, ref_len)
+
+
+def edit_counts(hyp, hyp_len, ref, ref_len, out=None):
+    """Batched token edit distance with its split (include/oasr.h: oasr_edit_counts; the rule: csrc/editdist_core.h): ``hyp`` [B, Lh] and
+    ``ref`` [B, Lr] token ids, ``hyp_len`` / ``ref_len`` [B] with 0 <= length <= min(1023, row width), all on the GPU (int32; int64 is
+    converted) -> int32 [B, 4] = (substitutions, deletions, insertions, hits) per pair, H = ref_len - S - D.  Ties prefer the diagonal, then
+    the deletion, then the insertion.  One launch on the current stream and no host read: the lengths stay on the device, so a pair whose
+    length is outside the contract yields (-1, -1, -1, -1) instead of an exception.  Wrong shapes / dtypes / devices raise ValueError
+    before anything is launched.  ``out``: a caller's contiguous int32 [B, 4]."""
+    a, res, keep = _edit_args(hyp, hyp_len, ref, ref_len, True)
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.int32 and tuple(out.shape) == (a.B, 4) and out.is_contiguous()
+                and out.device == keep[0].device):
+            raise ValueError("edit_counts: out must be a contiguous int32 [B, 4] on the operands' device")
+        res, a.out = out, out.data_ptr()
+    with torch.cuda.device(res.device):
+        N.check(N.lib().oasr_edit_counts(C.byref(a), N.stream_ptr(res.device)), "oasr_edit_counts")
+    return res
+
+
+def edit_counts_host(hyp, hyp_len, ref, ref_len):
+    """``edit_counts`` on CPU tensors through the library's host twin (oasr_edit_counts_host: the same rule from the same text, no GPU).
+    Here the lengths are readable, so one outside [0, min(1023, row width)] raises ValueError."""
+    a, out, keep = _edit_args(hyp, hyp_len, ref, ref_len, False)
+    for nm, ln, w in (("hyp_len", keep[2], a.Lh), ("ref_len", keep[3], a.Lr)):
+        if int(ln.min()) < 0 or int(ln.max()) > min(N.EditArgs.MAX_LEN, w):
+            raise ValueError(f"edit_counts_host: {nm} outside [0, min({N.EditArgs.MAX_LEN}, row width {w})]")
+    N.check(N.lib().oasr_edit_counts_host(C.byref(a)), "oasr_edit_counts_host")
+    return out
+
+
 def cross_entropy_(logits, V, targets, ignore, gscale=1.0, write_grad=True):
     """In place on bf16 logits [rows, ld]: returns (mean loss over non-ignored rows, row_loss); logits become the gradient."""
     rows, ld = logits.shape
@@ -602,3 +662,12 @@ def layernorm_bwd_(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum):
     rows, d = x.shape
     N.check(N.lib().oasr_test_layernorm_bwd(N.ptr(dy), N.ptr(x), N.ptr(gamma), N.ptr(mean), N.ptr(rstd), N.ptr(dres), N.ptr(dx), N.ptr(dgamma),
                                             N.ptr(dbeta), N.ptr(dsum), _dt(x), rows, d, N.stream_ptr()), "oasr_test_layernorm_bwd")
+
+
+def argmax_rows_(logits, V, rows, span, pred_out):
+    """include/oasr_testing.h: oasr_test_argmax_rows -- the prediction kernel of ``loss_and_backward(pred_out=...)`` on a caller's matrix:
+    ``logits`` bf16 / fp32 [n_rows, ld], ``rows`` int32 [B, 16] chunk-row table, ``span`` int32 [B] (multiples of 64), ``pred_out`` int32 [B, S]."""
+    B, S = pred_out.shape
+    N.check(N.lib().oasr_test_argmax_rows(N.ptr(logits), _dt(logits), logits.stride(0), V, logits.shape[0], N.ptr(rows), N.ptr(span), B, S,
+                                          N.ptr(pred_out), N.stream_ptr()), "oasr_test_argmax_rows")
+    return pred_out

@@ -63,7 +63,16 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     # SpecAugment on the finalized log-mel of every TRAINING micro-batch (olmoasr_amd/augment.py, csrc/specaug.hip): off | LD (2 + 2 masks) |
     # LB (1 + 1); the --spec_* overrides replace single fields of the preset.  Masks are seeded by --seed and the step counter (spec_offset).
     spec_augment="off", spec_freq_masks=None, spec_freq_width=None, spec_time_masks=None, spec_time_width=None, spec_time_ratio=None,
-    spec_fill=None)
+    spec_fill=None,
+    # Token error counts of a logging step (train_token_error_rate).  "host": the plain step returns fp32 logits, gen_pred + token_error_rate
+    # score them in Python.  "device": the logging step stays on the span step (needs --span_backward; the un-finalized log-mel shortcut stays
+    # in use), which hands back the argmax ids (loss_and_backward(pred_out=...)); olmoasr_amd.metrics scores them with the edit-distance
+    # kernel (ops.edit_counts), the counts are read where the loss is read and all-reduced with it, and the record gains train_subs /
+    # train_dels / train_ins; evaluate() scores with the same kernel.  ONE difference: a prediction without <|endoftext|> inside the computed
+    # prefix ends at span[b] rounded up to 64 instead of at position 448 -- the host path also scores the argmax of padded positions, which
+    # the loss ignores (and which the span step's forward does not compute).
+    train_error_counts="host")
+ERROR_COUNTS = ("host", "device")
 SPEC_OVERRIDES = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_time_ratio", "spec_fill")
 SPEC_PRESETS = ("off", "LD", "LB")
 
@@ -154,6 +163,10 @@ def parse_args(argv=None):
         args.lora_targets = tuple(t.strip() for t in args.lora_targets.split(",") if t.strip())
     args.lora_targets = tuple(args.lora_targets)
     args.spec_policy = spec_policy(args)
+    if args.train_error_counts not in ERROR_COUNTS:
+        raise SystemExit(f"--train_error_counts must be one of {' | '.join(ERROR_COUNTS)}, got {args.train_error_counts!r}")
+    if args.train_error_counts == "device" and not args.span_backward:
+        raise SystemExit("--train_error_counts=device takes the predictions from the span step: it needs --span_backward=True")
     return args
 
 
@@ -330,8 +343,8 @@ def gen_pred(logits, text_y):
     return preds, tgts
 
 
-def token_error_rate(preds, tgts):
-    """Token-level analogue of calc_pred_wer (:1125-1180): (substitutions + deletions + insertions) / reference tokens."""
+def token_error_counts(preds, tgts):
+    """(edit distance summed over the pairs, reference tokens): numerator and denominator of ``token_error_rate``."""
     errs = n = 0
     for p, t in zip(preds, tgts):
         prev = list(range(len(t) + 1))
@@ -342,13 +355,19 @@ def token_error_rate(preds, tgts):
             prev = cur
         errs += prev[-1]
         n += len(t)
+    return errs, n
+
+
+def token_error_rate(preds, tgts):
+    """Token-level analogue of calc_pred_wer (:1125-1180): (substitutions + deletions + insertions) / reference tokens."""
+    errs, n = token_error_counts(preds, tgts)
     return errs / max(1, n)
 
 
-def evaluate(net, indices, dev, timestamps=False, sample_len=32, batch=8):
+def evaluate(net, indices, dev, timestamps=False, sample_len=32, batch=8, error_counts="host"):
     """evaluate() of the reference (train_timestamps.py:1835-1919) on held-out SYNTHETIC clips (the eval sets themselves are
     out of scope): greedy ``model.decode(audio_input, DecodingOptions(language="en", without_timestamps=True))`` (:1916-1919),
-    scored as token error rate against the transcript ids."""
+    scored as token error rate against the transcript ids (``error_counts="device"``: by ops.edit_counts instead of the Python loop)."""
     from olmoasr_amd import ops
     from olmoasr_amd.decoding import DecodingOptions
     from olmoasr_amd.synth import synth_samples
@@ -358,6 +377,11 @@ def evaluate(net, indices, dev, timestamps=False, sample_len=32, batch=8):
         res = net.decode(ops.log_mel(pcm), DecodingOptions(language="en", without_timestamps=True, sample_len=sample_len))
         preds += [r.tokens for r in res]
         tgts += [[t for t in row[1:n] if t < 50257][:sample_len] for row, n in zip(ti.cpu().tolist(), tl.cpu().tolist())]
+    if error_counts == "device":
+        from olmoasr_amd import metrics
+        counter = metrics.ErrorCounter(dev)
+        counter.add_sequences(*metrics.pad_sequences(preds, dev), *metrics.pad_sequences(tgts, dev))
+        return counter.rate()
     return token_error_rate(preds, tgts)
 
 
@@ -463,6 +487,11 @@ def main(argv=None):
         print(json.dumps({"event": "spec_augment", "policy": args.spec_augment, "freq_masks": policy.freq_masks, "freq_width": policy.freq_width,
                           "time_masks": policy.time_masks, "time_width": policy.time_width, "time_ratio": policy.time_ratio,
                           "fill": policy.fill if math.isfinite(policy.fill) else str(policy.fill), "seed": spec_seed}), flush=True)
+    device_counts = args.train_error_counts == "device"
+    if device_counts:
+        from olmoasr_amd import metrics
+        counter = metrics.ErrorCounter(dev)
+        pred_buf = torch.empty(args.train_batch_size, dims.n_text_ctx, dtype=torch.int32, device=dev)
     while global_step < args.train_steps:
         start_step = time.time()
         net.zero_grad()
@@ -475,9 +504,10 @@ def main(argv=None):
             if cursor >= per_rank:
                 cursor, epoch = 0, epoch + 1
             last = i == accum - 1
-            # (a logging step wants the logits back: it takes the plain step; every other step limits the decoder's backward to the span
-            # and lets the encoder's transpose apply the log-mel floor / scale instead of a second pass over the tensor)
-            use_span = bool(args.span_backward) and not log_now
+            # (a logging step with --train_error_counts=host wants the logits back: it takes the plain step; every other step limits the decoder's
+            # backward to the span and lets the encoder's transpose apply the log-mel floor / scale instead of a second pass over the tensor)
+            use_span = bool(args.span_backward) and (device_counts or not log_now)
+            want_pred = device_counts and log_now
             if policy is not None:  # masks go on the FINALIZED log-mel, so the span step takes it finalized as well (mel_clip_max=None)
                 mel, clip_max = ops.log_mel(pcm), None
                 first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
@@ -486,11 +516,16 @@ def main(argv=None):
             else:
                 mel, clip_max = ops.log_mel(pcm, finalize=False) if use_span else (ops.log_mel(pcm), None)
             _, logits = net.loss_and_backward(mel, ti, ty, tl, loss_scale=scaler.scale, accumulation_steps=accum, loss_out=loss_buf,
-                                              accumulate_loss=i > 0, return_logits=log_now,
+                                              accumulate_loss=i > 0, return_logits=log_now and not device_counts,
                                               segment_events=reducer.segment_events() if (reducer and last) else None,
                                               span=loader.last_span if use_span else None, mel_clip_max=clip_max,
-                                              span_forward=use_span and bool(args.span_forward))
-            if log_now:
+                                              span_forward=use_span and bool(args.span_forward),
+                                              **({"pred_out": pred_buf[:ti.shape[0]]} if want_pred else {}))
+            if want_pred:
+                if i == 0:
+                    counter.reset()
+                counter.add(pred_buf[:ti.shape[0]], ty)
+            elif log_now:
                 p_, t_ = gen_pred(logits, ty)
                 preds += p_
                 tgts += t_
@@ -515,9 +550,16 @@ def main(argv=None):
         time_per_step = time.time() - start_step
         throughput = ((args.train_batch_size * accum * 30) / 60) / time_per_step  # audio_min_per_GPU_second (:1525-1527)
         if global_step % args.train_log_freq == 0 or global_step == 1:
-            t = loss_buf.clone()
+            scored = device_counts and global_step % args.train_log_freq == 0  # (global_step was advanced: this is log_now of the step just run)
+            if scored:  # the counts ride with the loss: one all-reduce, one read (float64 holds both exactly enough: counts < 2^53)
+                t = torch.cat([loss_buf.double(), counter.total.double()])
+            else:
+                t = loss_buf.clone()
             if world_size > 1:
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            if scored:
+                t, *sdih = t.cpu().tolist()  # the step's one read of the device: loss and counts together
+                sdih = [int(v) for v in sdih]
             if rank == 0:
                 rec = {"global_step": global_step, "train_loss": float(t) / world_size, "lr": lr, "loss_scale": scaler.scale,
                        "time_per_step": round(time_per_step, 4), "audio_min_per_GPU_second": round(throughput, 3),
@@ -525,11 +567,14 @@ def main(argv=None):
                        "spec_masked_cells": spec_cells}
                 if preds:
                     rec["train_token_error_rate"] = round(token_error_rate(preds, tgts), 4)
+                if scored:
+                    errs, n_ref = metrics.ErrorCounter.fraction(sdih)
+                    rec.update(train_token_error_rate=round(errs / max(1, n_ref), 4), train_subs=sdih[0], train_dels=sdih[1], train_ins=sdih[2])
                 log.append(rec)
                 print(json.dumps(rec), flush=True)
         if args.run_eval and args.eval_freq and global_step % int(args.eval_freq) == 0 and rank == 0:
             print(json.dumps({"event": "eval", "global_step": global_step,
-                              "token_error_rate": round(evaluate(net, held_out, dev, bool(args.timestamps)), 4)}), flush=True)
+                              "token_error_rate": round(evaluate(net, held_out, dev, bool(args.timestamps), error_counts=args.train_error_counts), 4)}), flush=True)
         if args.ckpt_freq and global_step % args.ckpt_freq == 0:
             save_ckpt(net, scaler, global_step, local_step, epoch, args, dims, rank, run_id, cursor, optimizer_steps, sharded=sharded)
     loader.close()
