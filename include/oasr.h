@@ -35,7 +35,7 @@ typedef struct oasr_dims {
 const char* oasr_last_error(void);
 /* ABI version: 100 * major + minor.  Structs passed by pointer (oasr_attn_args, oasr_gemm_args) only grow at the end and only with a
  * major bump; olmoasr_amd/_native.py refuses to drive a library whose version differs from OASR_ABI_VERSION. */
-#define OASR_ABI_VERSION 215
+#define OASR_ABI_VERSION 216
 int oasr_version(void);
 
 /* ---- log-mel front end: whisper.audio.log_mel_spectrogram as called at train_timestamps.py:196,214 and
@@ -46,7 +46,7 @@ size_t oasr_log_mel_workspace_bytes(int B);
 int oasr_log_mel(const void* pcm, int pcm_dtype, int B, int n_samples, float* mel, void* workspace, void* stream);
 /* The same front end without its last pass over the tensor: mel_raw = log10(max(mel power, 1e-10)), clip_max f32 [B] = each clip's maximum
  * of it.  whisper.audio's last two lines -- max(x, x.max() - 8), (x + 4) / 4 -- are then applied by the consumer while it reads the
- * tensor anyway (oasr_train_fwd_bwd_span's mel_clip_max): half the HBM traffic of this front end, bit-identical encoder input. */
+ * tensor anyway (oasr_train_step's mel_clip_max): half the HBM traffic of this front end, bit-identical encoder input. */
 int oasr_log_mel_raw(const void* pcm, int pcm_dtype, int B, int n_samples, float* mel_raw, float* clip_max, void* workspace, void* stream);
 /* HOST helper: the slaney 80 x 201 filterbank (whisper assets/mel_filters.npz) into a host buffer. */
 int oasr_mel_filterbank(float* out_host);
@@ -109,7 +109,7 @@ int oasr_refresh_shadow(oasr_ctx*, void* stream); /* after params changed outsid
 #define OASR_MODE_INFER 0
 #define OASR_MODE_TRAIN 1
 #define OASR_MODE_TRAIN_ENC 2 /* ABI 214: the workspace of the staged encoder entries (oasr_train_encode / _encode_bwd; S is not used) */
-#define OASR_MODE_TRAIN_DEC 3 /* ABI 214: the workspace of the staged decoder entries (oasr_train_decode / _decode_bwd / oasr_train_dec_fwd_bwd) */
+#define OASR_MODE_TRAIN_DEC 3 /* ABI 214: the workspace of the staged decoder entries (oasr_train_decode / _decode_bwd, and of oasr_train_step from a given xa) */
 size_t oasr_workspace_bytes(const oasr_ctx*, int B, int S, int mode); /* 0 for an unknown mode */
 
 /* OLMoASR.forward(mel, tokens, padding_mask) (olmoasr/model.py:856-887).  mel f32 [B,80,2*n_audio_ctx]; tokens i64 [B,S];
@@ -149,40 +149,62 @@ int oasr_decode_step(oasr_ctx*, const int64_t* tokens_last, int B, int pos, void
  * tokens back.  OASR_OK, or OASR_ERETRY (see above: enqueue the window's begin / steps again; at most once per context). */
 int oasr_decode_check(oasr_ctx*, int B, void* kv_cache, void* stream);
 
-/* One micro-step of train() (train_timestamps.py:1440-1454): forward, CE(ignore_index=pad)/accum, backward.
- * Gradients of the loss scaled by loss_scale are ACCUMULATED into the bound grad arena (zero it with oasr_zero_grad
- * at the start of an accumulation window).  loss_out (device f32): unscaled loss/accum, overwritten or accumulated.
- * seg_events: NULL or oasr_segment_count() hipEvent_t handles; event i is recorded when segment i's gradient is final.
- * logits_out: NULL, or f32 [B,S,n_vocab+1] (parity mode; costs an extra pass). */
-int oasr_train_fwd_bwd(oasr_ctx*, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len, int B,
-                       float loss_scale, float inv_accum, float* loss_out, int accumulate_loss, float* logits_out,
-                       void** seg_events, void* workspace, size_t workspace_bytes, void* stream);
-/* The same step over the first S <= n_text_ctx decoder positions (tokens/targets [B,S]; logits_out [B,S,n_vocab+1]).
- * For S >= max(text_len) the loss and all gradients equal the full-context ones (the trimmed positions are pure
- * padding: ignore_index targets, never attended to by a real query) -- an opt-in the reference does not have. */
-int oasr_train_fwd_bwd_s(oasr_ctx*, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len, int B,
-                         int S, float loss_scale, float inv_accum, float* loss_out, int accumulate_loss, float* logits_out,
-                         void** seg_events, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The same micro-step with the decoder's BACKWARD limited to the supervised span -- exact, and the forward still covers all
- * n_text_ctx positions like the reference's (train_timestamps.py:318-329 pads every sample to 448; :1444 then ignores the padding).
- * span_host: HOST int32 [B] (the data loader builds the token sequences on the host, train_timestamps.py:238-343):
- * every target of sample b at a position >= span_host[b] is ignore_index, and span_host[b] >= text_len[b].  Gradient rows past the
- * span are exactly zero in the reference's computation, so the decoder's token rows are stored in 64-position chunks with the
- * chunks that can carry gradient first and the decoder's backward GEMMs / LayerNorms / attention run over those rows only
- * (olmoasr_amd/csrc/engine_step.hip).  Loss and gradients equal oasr_train_fwd_bwd's up to fp32 summation order.  Falls back to the
- * plain step when n_text_ctx is not a multiple of 64 or B > 512. */
+/* ABI 216: one micro-step of train() (train_timestamps.py:1440-1454): forward, CE(ignore_index=pad)/accum, backward -- ONE entry for every
+ * form of the fused step; the options are fields of oasr_train_step_args, NULL / 0 where not used, and a binding checks
+ * oasr_sizeof_train_step_args like oasr_sizeof_attn_args.  Gradients of the loss scaled by loss_scale are ACCUMULATED into the bound grad
+ * arena (zero it with oasr_zero_grad at the start of an accumulation window).  Every combination the fields' comments exclude is refused
+ * (OASR_EINVAL; OASR_ESTATE for the context's state) before anything is launched or dereferenced.
+ * Streams: asynchronous on `stream` like everything else.  With span_host, part of the decoder's backward (weight-gradient GEMMs) runs on two
+ * lowest-priority streams the context owns (created on the first call, destroyed by oasr_destroy), forked from and joined back into `stream`
+ * with events inside the call: when the call returns, everything it enqueued is ordered before whatever the caller enqueues on `stream`
+ * next, and each seg_events[i] still means "every gradient of segment i is complete". */
 #define OASR_SPAN_FORWARD_ALL 0    /* the reference's shape: the decoder's forward covers all n_text_ctx positions */
 #define OASR_SPAN_FORWARD_ACTIVE 1 /* opt-in: the forward leaves the positions past the span out too -- their logits exist in the reference
                                     * (model.py:768-770 over the padded context) but nothing reads them: loss and gradients unchanged */
-/* mel_clip_max: NULL (mel is finished log-mel, as everywhere else), or device f32 [B] with mel = oasr_log_mel_raw's output.
- * Streams: asynchronous on `stream` like everything else.  Part of the decoder's backward (weight-gradient GEMMs) runs on two lowest-priority
- * streams the context owns (created on the first call, destroyed by oasr_destroy), forked from and joined back into `stream` with events inside
- * the call: when the call returns, everything it enqueued is ordered before whatever the caller enqueues on `stream` next, and each
- * seg_events[i] still means "every gradient of segment i is complete". */
-int oasr_train_fwd_bwd_span(oasr_ctx*, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                            const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale, float inv_accum,
-                            float* loss_out, int accumulate_loss, void** seg_events, void* workspace, size_t workspace_bytes, void* stream);
+typedef struct oasr_train_step_args {
+  /* Exactly one of mel and xa. */
+  const float* mel; /* f32 [B, n_mels, 2*n_audio_ctx]: the whole step.  Workspace: OASR_MODE_TRAIN bytes. */
+  /* compute dtype [B, n_audio_ctx, d]: the decoder alone, from a given encoder output -- a frozen encoder's features computed once and
+   * reused.  Loss, events and gradients as from mel; every segment event is recorded, the encoder's at once.  OASR_ESTATE if an encoder
+   * tensor (or an encoder adapter) is trainable.  Not with mel_clip_max or logits_out.  Workspace: OASR_MODE_TRAIN_DEC bytes. */
+  const void* xa;
+  const int64_t* tokens;   /* [B, S] */
+  const int64_t* targets;  /* [B, S] */
+  const int32_t* text_len; /* [B] */
+  /* NULL: the plain step.  Or HOST int32 [B] (the data loader builds the token sequences on the host, train_timestamps.py:238-343): the
+   * same micro-step with the decoder's BACKWARD limited to the supervised span -- exact, and the forward still covers all n_text_ctx
+   * positions like the reference's (train_timestamps.py:318-329 pads every sample to 448; :1444 then ignores the padding).  Every target of
+   * sample b at a position >= span_host[b] is ignore_index, and span_host[b] >= text_len[b].  Gradient rows past the span are exactly zero
+   * in the reference's computation, so the decoder's token rows are stored in 64-position chunks with the chunks that can carry gradient
+   * first and the decoder's backward GEMMs / LayerNorms / attention run over those rows only (olmoasr_amd/csrc/engine_step.hip).  Loss and
+   * gradients equal the plain step's up to fp32 summation order.  Needs S = n_text_ctx and span_forward = OASR_SPAN_FORWARD_*; not with
+   * logits_out.  Falls back to the plain step when n_text_ctx is not a multiple of 64 or B > 512. */
+  const int32_t* span_host;
+  /* NULL (mel is finished log-mel, as everywhere else), or device f32 [B] with mel = oasr_log_mel_raw's output.  With span_host and mel only. */
+  const float* mel_clip_max;
+  float* loss_out;   /* device f32: unscaled loss/accum, overwritten or (accumulate_loss != 0) accumulated */
+  float* logits_out; /* NULL, or f32 [B, S, n_vocab+1] (parity mode; costs an extra pass).  Plain step from mel only. */
+  /* The teacher-forced predictions on request (the reference's gen_pred argmax, train_timestamps.py:1077, without leaving the span step and
+   * without an fp32 logits tensor).  NULL (then the step is the one without them, launch for launch), or device int32 [B, n_text_ctx]:
+   *     pred_out[b, s] = argmax over c < n_vocab + 1 of logits[b, s, c]   for s < span_host[b] rounded up to 64 -- the rows every forward
+   *                      mode computes; the lowest index wins among equal maxima, the padded columns of the tied head are never candidates
+   *     pred_out[b, s] = -1                                               elsewhere
+   * One extra kernel between the decoder forward and the cross-entropy (which overwrites the logits with their gradient): each active row is
+   * read once in the compute dtype, 4 bytes are written; it addresses rows through the chunk-row table, so the output is in logical order.
+   * Loss and gradients are unchanged.  With span_host only, and a shape the row table cannot chunk (n_text_ctx not a multiple of 64, or
+   * B > 512) is then refused (OASR_EINVAL) before any launch instead of taking the plain step. */
+  int32_t* pred_out;
+  void** seg_events; /* NULL or oasr_segment_count() hipEvent_t handles; event i is recorded when segment i's gradient is final */
+  int32_t B;
+  /* decoder positions, 0 < S <= n_text_ctx.  For S >= max(text_len) the loss and all gradients equal the full-context ones (the trimmed
+   * positions are pure padding: ignore_index targets, never attended to by a real query) -- an opt-in the reference does not have. */
+  int32_t S;
+  int32_t span_forward; /* OASR_SPAN_FORWARD_*; read with span_host only */
+  int32_t accumulate_loss;
+  float loss_scale, inv_accum; /* inv_accum = 1 / accumulation steps */
+} oasr_train_step_args;
+size_t oasr_sizeof_train_step_args(void);
+int oasr_train_step(oasr_ctx*, const oasr_train_step_args*, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same micro-step cut at the logits, for torch.autograd: OLMoASR.forward in training mode (olmoasr/model.py:856-887) followed by
  * the CALLER's loss and .backward() (train_timestamps.py:1440-1454 unchanged).  train_fwd: fp32 logits [B, S, rows], every saved
@@ -214,35 +236,9 @@ int oasr_train_decode(oasr_ctx*, const int64_t* tokens, const void* xa, const in
                       void* workspace, size_t workspace_bytes, void* stream);
 int oasr_train_decode_bwd(oasr_ctx*, const int64_t* tokens, const int32_t* text_len, const float* dlogits, int B, int S, void* dxa_out,
                           void* workspace, size_t workspace_bytes, void* stream);
-/* ABI 214: the fused micro-step of the decoder alone, from a given encoder output xa (compute dtype) -- a frozen encoder's features
- * computed once and reused.  span_host: NULL (= oasr_train_fwd_bwd_s over S positions) or the host [B] array of oasr_train_fwd_bwd_span
- * (then S = n_text_ctx and span_forward = OASR_SPAN_FORWARD_*).  Loss, events and gradients as those entries; every segment event is
- * recorded, the encoder's at once.  OASR_ESTATE if an encoder tensor (or an encoder adapter) is trainable.  Workspace: OASR_MODE_TRAIN_DEC. */
-int oasr_train_dec_fwd_bwd(oasr_ctx*, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                           const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
-                           int accumulate_loss, void** seg_events, void* workspace, size_t workspace_bytes, void* stream);
-/* The two span steps with the teacher-forced predictions on request (the reference's gen_pred argmax, train_timestamps.py:1077, without
- * leaving the span step and without an fp32 logits tensor).  pred_out: NULL (then these ARE oasr_train_fwd_bwd_span / oasr_train_dec_fwd_bwd,
- * launch for launch), or device int32 [B, n_text_ctx]:
- *     pred_out[b, s] = argmax over c < n_vocab + 1 of logits[b, s, c]   for s < span_host[b] rounded up to 64 -- the rows every forward
- *                      mode computes; the lowest index wins among equal maxima, the padded columns of the tied head are never candidates
- *     pred_out[b, s] = -1                                               elsewhere
- * One extra kernel between the decoder forward and the cross-entropy (which overwrites the logits with their gradient): each active row is
- * read once in the compute dtype, 4 bytes are written; it addresses rows through the chunk-row table, so the output is in logical order.
- * Loss and gradients are those of the entry without pred_out.  With pred_out the dec entry needs span_host, and a shape the row table
- * cannot chunk (n_text_ctx not a multiple of 64, or B > 512) is refused (OASR_EINVAL) before any launch instead of taking the plain step.
- * Entry points only: OASR_ABI_VERSION is unchanged, a library without them is refused by the oasr_sizeof_edit_args check below. */
-int oasr_train_fwd_bwd_span_pred(oasr_ctx*, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                 const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
-                                 float inv_accum, float* loss_out, int accumulate_loss, void** seg_events, void* workspace,
-                                 size_t workspace_bytes, int32_t* pred_out, void* stream);
-int oasr_train_dec_fwd_bwd_pred(oasr_ctx*, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
-                                int accumulate_loss, void** seg_events, void* workspace, size_t workspace_bytes, int32_t* pred_out,
-                                void* stream);
 
 /* Frozen parameters (torch's requires_grad == False): mask holds one byte per tensor in oasr_param_info order, nonzero = trainable;
- * the default is all ones.  From then on the backward entries (oasr_train_fwd_bwd, _s, _span, oasr_train_bwd) neither launch nor
+ * the default is all ones.  From then on the backward entries (oasr_train_step, oasr_train_bwd) neither launch nor
  * write anything whose only purpose is a frozen tensor's gradient: frozen ranges of the gradient arena are left as they are.
  * oasr_optim_step updates, decays and clips over the trainable tensors only (frozen moments stay as they are).  With no trainable
  * tensor the backward entries return OASR_ESTATE.  The call is synchronous (it uploads the optimizer's table of trainable runs).
@@ -292,7 +288,7 @@ typedef struct oasr_attn_args {
   float* colsum_scratch;        /* with either of them: B * (ceil(Tq/128) + ceil(Tk/128)) * H*64 floats of scratch */
   int32_t* qtile_flags;         /* optional [B, H, ceil(Tq/64)] workspace (backward): 64-query tiles of d_o that are all zero -- the padded
                                  * positions of a decoder batch -- are recorded by the dQ kernel and skipped by both; bit-identical */
-  /* ABI 200: chunked token rows (the decoder of oasr_train_fwd_bwd_span).  q_rows / k_rows: optional int32 [B][OASR_ROWTAB]: first
+  /* ABI 200: chunked token rows (the decoder of oasr_train_step with span_host).  q_rows / k_rows: optional int32 [B][OASR_ROWTAB]: first
    * token row -- relative to the base pointers, batch strides unused -- of every 64-position chunk of sample b (q_rows: q, o, o_lo,
    * d_o, dq; k_rows: k, v, dk, dv); q_span: optional int32 [B], multiples of 64 (backward): d_o is zero at query positions >=
    * q_span[b]; those rows are not read and their dq (self-attention: dk / dv too) not written. */

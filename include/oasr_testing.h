@@ -25,7 +25,7 @@ int oasr_gemm_set_variant(int v);
  * XCD (B <= 4), 3 / 4 = that team as 32 / 64 workgroups spread over the chip, 5 = the chip-wide engine (one sequence; more: as 2).
  * 0-4 are bit-identical; 5 agrees with them to the fp32 rounding of differently ordered K sums (tests/test_gpu_decode_step.py). */
 int oasr_decode_set_ln_fold(int mode);
-/* tests / A-B: side streams of the supervised-span step (oasr_train_fwd_bwd_span; csrc/engine_run.h: Runner::side_mode).  Bit 0: the decoder
+/* tests / A-B: side streams of the supervised-span step (oasr_train_step with span_host; csrc/engine_run.h: Runner::side_mode).  Bit 0: the decoder
  * backward's weight gradients over the R active rows, bit 2: the cross-attention key|value weight gradient and d(xa) -- run on lowest-priority
  * streams beside the data-gradient chain; bit 1: the key|value projections of the decoder forward likewise; bit 3: without segment events leave
  * the key|value gradients in flight across blocks.  -1 = the library default.  Gradients differ by fp32 atomic order only
@@ -61,7 +61,7 @@ int oasr_profile_gemm_records(char* buf, int cap);
 int oasr_profile_gemm_collect(double* ms4, double* flops4, int64_t* count4, char* by_symbol /* "symbol\tlaunches\tms\tflops\n"... or NULL */, int cap);
 int oasr_probe_lds_oob(const void* src_u16 /*[512]*/, void* dst_u16 /*[512]*/, void* stream);
 int oasr_probe_tr16(const void* src_bf16 /*[16][64]*/, void* dst_bf16 /*[64 lanes][4]*/, void* stream);
-/* tests: the tables oasr_train_fwd_bwd_span builds for one micro-batch -- span_host: HOST int32 [B]; rows_out: device int32
+/* tests: the tables oasr_train_step builds from span_host for one micro-batch -- span_host: HOST int32 [B]; rows_out: device int32
  * [B][OASR_ROWTAB] chunk-row table; span_out: device int32 [B] spans rounded up to 64; targets_rows_out: device int64 [B*S] targets in
  * row order (active rows only); active_rows_out: HOST int64, the number of leading rows the decoder's backward runs over. */
 int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
@@ -107,7 +107,7 @@ int oasr_test_layernorm_bwd(const void* dy, const void* x, const float* gamma, c
 int oasr_test_dtw_host(const float* cost, int64_t ld, int N, int M, int negate, int32_t* text_indices, int32_t* time_indices, int32_t* path_len,
                        void* workspace);
 
-/* tests (tests/test_gpu_train_pred.py): the prediction kernel of oasr_train_fwd_bwd_span_pred on a caller's matrix and tables, like the glue
+/* tests (tests/test_gpu_train_pred.py): the prediction kernel of oasr_train_step's pred_out on a caller's matrix and tables, like the glue
  * operators above (no process state, no opt-in).  logits: [n_rows][ld] in `dtype`, ld >= V (16-byte aligned rows that hold V rounded up to a 16-byte piece are read in such pieces, others column by column);
  * rows: device int32 [B][OASR_ROWTAB] chunk-row table; span: device int32 [B], multiples of 64, <= S; pred_out: device int32 [B][S]:
  *     pred_out[b, s] = argmax over c < V of logits[rows[b][s >> 6] + (s & 63)][c] for s < span[b] (lowest index among equal maxima), else -1;

@@ -62,11 +62,17 @@ class EditArgs(C.Structure):  # include/oasr.h: oasr_edit_args
                 ("ld_hyp", C.c_int64), ("ld_ref", C.c_int64), ("B", C.c_int32), ("Lh", C.c_int32), ("Lr", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
+    _fields_ = [(n, C.c_void_p) for n in ("mel", "xa", "tokens", "targets", "text_len", "span_host", "mel_clip_max", "loss_out", "logits_out",
+                                          "pred_out", "seg_events")] + \
+               [(n, C.c_int32) for n in ("B", "S", "span_forward", "accumulate_loss")] + [("loss_scale", C.c_float), ("inv_accum", C.c_float)]
+
+
 DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_audio_ctx
 # The word-timestamp operators (oasr_alignment_matrix, oasr_dtw, oasr_test_dtw_host) add entry points without a new ABI generation: a library built before them is refused by the oasr_sizeof_align_args check in lib().
 # SpecAugment (oasr_spec_augment, oasr_spec_augment_plan) came the same way: entry points only, a stale library refused by the oasr_sizeof_specaug check in lib().
-# Token error counts (oasr_edit_counts, oasr_edit_counts_host) and the span steps with predictions (oasr_train_fwd_bwd_span_pred, oasr_train_dec_fwd_bwd_pred, oasr_test_argmax_rows) likewise: a stale library is refused by the oasr_sizeof_edit_args check in lib().
-ABI_VERSION = 215  # include/oasr.h: OASR_ABI_VERSION (215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
+# Token error counts (oasr_edit_counts, oasr_edit_counts_host) and the prediction kernel's hook (oasr_test_argmax_rows) likewise: a stale library is refused by the oasr_sizeof_edit_args check in lib().
+ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
 ROWTAB = 16        # include/oasr.h: OASR_ROWTAB (entries per sample of a chunk-row table)
@@ -110,10 +116,8 @@ def _declare(lib):
         "oasr_refresh_shadow": (i32, [vp, vp]),
         "oasr_workspace_bytes": (sz, [vp, i32, i32, i32]),
         "oasr_forward": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
-        "oasr_train_fwd_bwd": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, vp, i32, vp, vp, vp, sz, vp]),
-        "oasr_train_fwd_bwd_s": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, i32, vp, vp, vp, sz, vp]),
-        "oasr_train_fwd_bwd_span": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, vp, i32, vp, vp, sz, vp]),
-        "oasr_train_fwd_bwd_span_pred": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, vp, i32, vp, vp, sz, vp, vp]),
+        "oasr_sizeof_train_step_args": (sz, []),
+        "oasr_train_step": (i32, [vp, C.POINTER(TrainStepArgs), vp, sz, vp]),
         "oasr_log_mel_raw": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
         "oasr_sizeof_attn_args": (sz, []),
         "oasr_test_span_tables": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp]),
@@ -137,8 +141,6 @@ def _declare(lib):
         "oasr_train_encode_bwd": (i32, [vp, vp, i32, vp, vp, sz, vp]),
         "oasr_train_decode": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
         "oasr_train_decode_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
-        "oasr_train_dec_fwd_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, vp, vp, sz, vp]),
-        "oasr_train_dec_fwd_bwd_pred": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, vp, vp, sz, vp, vp]),
         "oasr_set_trainable": (i32, [vp, vp, i32]),
         "oasr_optim_step": (i32, [vp, f32, f32, f32, f32, f32, f32, f32, i64, vp, vp, vp]),
         "oasr_grad_sumsq_range": (i32, [vp, i64, i64, vp, vp, vp]),
@@ -230,6 +232,9 @@ def lib():
         if int(handle.oasr_sizeof_edit_args()) != C.sizeof(EditArgs):
             raise NativeError(f"{LIB_PATH}: oasr_edit_args of {int(handle.oasr_sizeof_edit_args())} bytes, this binding passes "
                               f"{C.sizeof(EditArgs)} -- rebuild (__graft_entry__.build())")
+        if int(handle.oasr_sizeof_train_step_args()) != C.sizeof(TrainStepArgs):
+            raise NativeError(f"{LIB_PATH}: oasr_train_step_args of {int(handle.oasr_sizeof_train_step_args())} bytes, this binding passes "
+                              f"{C.sizeof(TrainStepArgs)} -- rebuild (__graft_entry__.build())")
         _lib, EXPORTS = handle, exports
     return _lib
 

@@ -1,4 +1,4 @@
-// Teacher-forced predictions of the span step (include/oasr.h at oasr_train_fwd_bwd_span_pred): pred[b, s] = argmax_c logits[row(b, s)][c]
+// Teacher-forced predictions of the span step (include/oasr.h at oasr_train_step_args.pred_out): pred[b, s] = argmax_c logits[row(b, s)][c]
 // over c < V, the lowest index among equal maxima -- gen_pred's argmax (train_timestamps.py:1077) taken from the logits in the compute dtype
 // before the cross-entropy overwrites them with their gradient.
 //

@@ -51,7 +51,7 @@ struct Plan {
   T *ga, *gb, *gc, *gln, *gqkv, *go, *gu, *gxa, *gkv, *gq, *gA2;
   float *delta, *tmp_w1p, *tmp_w2p, *cs_scratch, *gemm_cs_scratch;
   int32_t* qtile_flags;  // attention backward of the decoder: which 64-position tiles of d_o are non-zero
-  // supervised-span step (oasr_train_fwd_bwd_span): chunk-row table of the decoder's token rows, spans, targets in row order
+  // supervised-span step (oasr_train_step with span_host): chunk-row table of the decoder's token rows, spans, targets in row order
   int32_t *rows, *span_dev;
   int64_t* targets_phys;
   float *lora_dw, *lora_part;  // adapter contexts: the adapted weights' gradients (oasr_ctx::Lora::dw) and lora_grad's partial sums
@@ -744,7 +744,7 @@ static void other_two(typename Engine<T>::Plan& p, const T* cur, T** a, T** b) {
 }
 
 // The backward half of a training micro-step: p.logits holds d(loss)/d(logits) (bf16 engine: bf16 [Md, Vp]) on entry -- written in
-// place by the fused cross-entropy (oasr_train_fwd_bwd*) or converted from the caller's fp32 tensor (oasr_train_bwd, the
+// place by the fused cross-entropy (oasr_train_step) or converted from the caller's fp32 tensor (oasr_train_bwd, the
 // torch.autograd path) -- and every saved activation of the forward is still in the workspace.  It runs in two halves (train_backward
 // below calls both).  backward_decoder starts from p.logits and ends at the token / positional embeddings; with `xa_grad` it
 // leaves d(xa) in p.gxa.  backward_encoder starts from d(xa) = `gxa` and ends at the conv stem; with `dmel` it also writes d(mel) (fp32

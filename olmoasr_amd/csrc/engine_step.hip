@@ -90,53 +90,11 @@ extern "C" int oasr_span_set_side_streams(int mode) {
   return OASR_OK;
 }
 
-// Same step over a decoder context of S <= n_text_ctx positions (tokens / targets are [B, S]).  With S >= max(text_len)
-// rounded up, the loss, every gradient and therefore the optimizer step are those of the full padded context: positions
-// past the last real token only ever see ignore_index targets, and no real query attends to them (causal mask), so
-// the reference spends their share of the decoder on exact zeros (train_timestamps.py:318-329 pads every sample to 448).
-// xa_in (oasr_train_dec_fwd_bwd): the decoder alone, on the caller's encoder output.
-template <typename T>
-static int oasr_train_fwd_bwd_s_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets,
-                                    const int32_t* text_len, int B, int S, float loss_scale, float inv_accum, float* loss_out,
-                                    int accumulate_loss, float* logits_out, void** ev, void* workspace, size_t workspace_bytes,
-                                    void* stream, const float* mel_clip_max = nullptr, const void* xa_in = nullptr) {
-  RC(check_bound(c, true));
-  OASR_REQUIRE(S > 0 && S <= c->S_max, "oasr_train_fwd_bwd: S=%d outside (0, n_text_ctx=%d]", S, c->S_max);
-  OASR_REQUIRE((mel || xa_in) && tokens && targets && text_len && loss_out && workspace && B > 0, "oasr_train_fwd_bwd: bad args");
-  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, xa_in ? OASR_MODE_TRAIN_DEC : OASR_MODE_TRAIN), "oasr_train_fwd_bwd: workspace too small");
-  const long Md = (long)B * S;
-  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, xa_in ? STAGE_DEC : STAGE_ALL);
-  auto& p = s.p;
-  auto& r = s.r;
-  r.mel_clip_max = mel_clip_max;  // un-finalized log-mel (oasr_log_mel_raw): the floor / scale lines ride in the encoder's transpose
-  hipStream_t st = r.st;
-  // ---------------- forward ----------------
-  if (xa_in) RC(copy_xa<T>(c, p.xa, xa_in, B, st));
-  else RC(r.encoder_fwd(p, mel));
-  RC(r.decoder_fwd(p, tokens));
-  if (logits_out) RC(launch_logits_to_f32(p.logits, c->Vp, Md, c->V, logits_out, st));
-  RC(launch_count_valid(targets, Md, PAD_ID, c->V, p.n_valid, st));
-  RC(launch_cross_entropy(p.logits, c->Vp, c->V, targets, Md, PAD_ID, loss_scale * inv_accum, p.n_valid, p.row_loss, 1, st));
-  RC(launch_loss_reduce(p.row_loss, Md, p.n_valid, inv_accum, loss_out, accumulate_loss, st));
-  return train_backward<T>(c, r, p, tokens, B, S, ev);
-}
-extern "C" int oasr_train_fwd_bwd_s(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets,
-                                    const int32_t* text_len, int B, int S, float loss_scale, float inv_accum, float* loss_out,
-                                    int accumulate_loss, float* logits_out, void** ev, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-  OASR_REQUIRE(c, "oasr_train_fwd_bwd_s: null context");
-  return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, mel, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss,
-                       logits_out, ev, workspace, workspace_bytes, stream);
-}
-extern "C" int oasr_train_fwd_bwd(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                  int B, float loss_scale, float inv_accum, float* loss_out, int accumulate_loss, float* logits_out,
-                                  void** ev, void* workspace, size_t workspace_bytes, void* stream) {
-  return oasr_train_fwd_bwd_s(c, mel, tokens, targets, text_len, B, c ? c->S_max : 0, loss_scale, inv_accum, loss_out, accumulate_loss,
-                              logits_out, ev, workspace, workspace_bytes, stream);
-}
-
-// ---- the supervised-span micro-step ---------------------------------------------------------------------------------------------
-// Same forward (all n_text_ctx positions, as the reference pads them: train_timestamps.py:318-329), same loss, same gradients; what
+// ---- the fused micro-step (oasr_train_step; the contract of every field: include/oasr.h at oasr_train_step_args) -----------------------
+// S < n_text_ctx (text_ctx): with S >= max(text_len) rounded up, the loss, every gradient and therefore the optimizer step are those of
+// the full padded context: positions past the last real token only ever see ignore_index targets, and no real query attends to them
+// (causal mask), so the reference spends their share of the decoder on exact zeros (train_timestamps.py:318-329 pads every sample to 448).
+// span_host, the supervised-span step: same forward (all n_text_ctx positions, as the reference pads them), same loss, same gradients; what
 // changes is WHERE the decoder's token rows live and how much of the backward is executed.  span_host[b] (host memory, known to the
 // data loader: train_timestamps.py:238-343 builds the token sequences on the host) bounds the positions of sample b that can carry
 // gradient: every target at or past it is ignore_index (train_timestamps.py:1444) and it is >= text_len[b], the first masked key
@@ -147,68 +105,80 @@ extern "C" int oasr_train_fwd_bwd(oasr_ctx* c, const float* mel, const int64_t* 
 //     GEMMs and their epilogues are row-wise and see plain matrices);
 //   * the backward of the decoder (dgrad / wgrad GEMMs, LayerNorm, attention, cross-entropy gradient, embedding scatter) runs on the
 //     leading R = sum_b ceil64(span[b]) rows only -- on the synthetic lengths 1/3 of the 448 * B.
-// The results differ from oasr_train_fwd_bwd's only by fp32 summation order (weight gradients sum over fewer, re-ordered token rows).
+// The results differ from the plain step's only by fp32 summation order (weight gradients sum over fewer, re-ordered token rows).
 // A shape the row table cannot chunk takes the plain step (same results).
 static bool span_chunkable(const oasr_ctx* c, int B) { return (c->S_max % 64) == 0 && c->S_max <= 64 * OASR_ROWTAB && B <= 512; }
 
+// Every refusal of oasr_train_step, before anything is launched or dereferenced: the arguments, then the workspace size, then the context's state.
+static int train_step_check(const oasr_ctx* c, const oasr_train_step_args* a, const void* workspace, size_t workspace_bytes) {
+  RC(check_bound(c, true));
+  OASR_REQUIRE(a, "oasr_train_step: null args");
+  OASR_REQUIRE(!a->mel != !a->xa, "oasr_train_step: exactly one of mel and xa is required (mel: the whole step; xa: the decoder alone on given features)");
+  OASR_REQUIRE(a->tokens && a->targets && a->text_len && a->loss_out && workspace,
+               "oasr_train_step: bad args (tokens, targets, text_len, loss_out and workspace are required)");
+  OASR_REQUIRE(a->B > 0 && a->S > 0 && a->S <= c->S_max, "oasr_train_step: B=%d must be positive and S=%d inside (0, n_text_ctx=%d]", a->B, a->S, c->S_max);
+  if (a->span_host) {
+    OASR_REQUIRE(a->S == c->S_max, "oasr_train_step: a span step covers the whole context (S = %d, n_text_ctx = %d)", a->S, c->S_max);
+    OASR_REQUIRE(a->span_forward == OASR_SPAN_FORWARD_ALL || a->span_forward == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_step: span_forward");
+    OASR_REQUIRE(!a->logits_out, "oasr_train_step: logits_out belongs to the plain step (the span step keeps no fp32 logits)");
+  } else {
+    OASR_REQUIRE(!a->pred_out, "oasr_train_step: pred_out comes with span_host (the predictions cover the span's rows)");
+    OASR_REQUIRE(!a->mel_clip_max, "oasr_train_step: mel_clip_max comes with span_host (the un-finalized log-mel is consumed by the span step only)");
+  }
+  OASR_REQUIRE(!a->xa || (!a->mel_clip_max && !a->logits_out), "oasr_train_step: mel_clip_max / logits_out do not apply to the step from a given xa");
+  // pred_out is indexed through the row table: no plain-step fall-back with it
+  OASR_REQUIRE(!a->pred_out || span_chunkable(c, a->B),
+               "pred_out needs the chunk-row table: n_text_ctx = %d must be a multiple of 64 (<= %d) and B = %d <= 512", c->S_max, 64 * OASR_ROWTAB, a->B);
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, a->B, a->S, a->xa ? OASR_MODE_TRAIN_DEC : OASR_MODE_TRAIN), "oasr_train_step: workspace too small");
+  if (a->xa && c->pr.enc_any) {
+    oasr_set_error("oasr_train_step: an encoder tensor is trainable -- the step from a given xa has no encoder backward (freeze the "
+                   "encoder, or pass mel)");
+    return OASR_ESTATE;
+  }
+  return OASR_OK;
+}
+
+// chunked: the supervised-span step over the chunk-row table; else the plain step over B * S rows (an unchunkable span call included)
 template <typename T>
-static int oasr_train_fwd_bwd_span_impl(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                       const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
-                                       float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
-                                       size_t workspace_bytes, void* stream, const void* xa_in = nullptr, int32_t* pred_out = nullptr) {
-  const int S = c->S_max;
+static int train_step_impl(oasr_ctx* c, const oasr_train_step_args& a, bool chunked, void* workspace, size_t workspace_bytes, void* stream) {
+  const int B = a.B, S = a.S;
   const long Md = (long)B * S;
-  Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, xa_in ? STAGE_DEC : STAGE_ALL);  // (s.r.lane: the lane tag is put back on every path)
+  Step<T> s(c, workspace, workspace_bytes, stream, B, S, a.text_len, true, a.xa ? STAGE_DEC : STAGE_ALL);  // (s.r.lane: the lane tag is put back on every path)
   auto& p = s.p;
   auto& r = s.r;
   hipStream_t st = r.st;
-  long R = 0;
-  RC(launch_build_span_tables(span_host, B, S, targets, PAD_ID, p.rows, p.span_dev, p.targets_phys, &R, st));
-  OASR_REQUIRE(R > 0, "oasr_train_fwd_bwd_span: no position of the micro-batch carries gradient (every span is 0)");
-  r.dec_rows = p.rows;
-  r.dec_span = p.span_dev;
-  r.dec_rows_bwd = R;
-  r.dec_rows_fwd = forward_rows == OASR_SPAN_FORWARD_ACTIVE ? R : 0;
-  r.mel_clip_max = mel_clip_max;
-  if (const int mode = span_side_streams()) RC(r.side_begin(mode));
-  // ---------------- forward (every position, unless the caller opted out of the padded ones) ----------------
-  if (xa_in) RC(copy_xa<T>(c, p.xa, xa_in, B, st));
-  else RC(r.encoder_fwd(p, mel));
-  RC(r.decoder_fwd(p, tokens));
+  r.mel_clip_max = a.mel_clip_max;  // un-finalized log-mel (oasr_log_mel_raw): the floor / scale lines ride in the encoder's transpose
+  const int64_t* ce_targets = a.targets;  // cross-entropy over every row, or over the R active rows in row order
+  long ce_rows = Md;
+  if (chunked) {
+    long R = 0;
+    RC(launch_build_span_tables(a.span_host, B, S, a.targets, PAD_ID, p.rows, p.span_dev, p.targets_phys, &R, st));
+    OASR_REQUIRE(R > 0, "oasr_train_step: no position of the micro-batch carries gradient (every span is 0)");
+    r.dec_rows = p.rows;
+    r.dec_span = p.span_dev;
+    r.dec_rows_bwd = R;
+    r.dec_rows_fwd = a.span_forward == OASR_SPAN_FORWARD_ACTIVE ? R : 0;
+    if (const int mode = span_side_streams()) RC(r.side_begin(mode));
+    ce_targets = p.targets_phys;
+    ce_rows = R;
+  }
+  // ---------------- forward (every position, unless the caller of a span step opted out of the padded ones) ----------------
+  if (a.xa) RC(copy_xa<T>(c, p.xa, a.xa, B, st));
+  else RC(r.encoder_fwd(p, a.mel));
+  RC(r.decoder_fwd(p, a.tokens));
+  if (a.logits_out) RC(launch_logits_to_f32(p.logits, c->Vp, Md, c->V, a.logits_out, st));
   // predictions on request, while the logits are still logits (the cross-entropy below overwrites them with their gradient)
-  if (pred_out) RC(launch_argmax_rows(p.logits, c->Vp, c->V, Md, p.rows, p.span_dev, B, S, pred_out, st));
-  // loss over the active rows (the other rows' targets are ignore_index: they add nothing to the sum and nothing to the count)
-  RC(launch_count_valid(targets, Md, PAD_ID, c->V, p.n_valid, st));
-  RC(launch_cross_entropy(p.logits, c->Vp, c->V, p.targets_phys, R, PAD_ID, loss_scale * inv_accum, p.n_valid, p.row_loss, 1, st));
-  RC(launch_loss_reduce(p.row_loss, R, p.n_valid, inv_accum, loss_out, accumulate_loss, st));
-  return train_backward<T>(c, r, p, tokens, B, S, ev);
+  if (a.pred_out) RC(launch_argmax_rows(p.logits, c->Vp, c->V, Md, p.rows, p.span_dev, B, S, a.pred_out, st));
+  // loss (chunked: over the active rows; the other rows' targets are ignore_index: they add nothing to the sum and nothing to the count)
+  RC(launch_count_valid(a.targets, Md, PAD_ID, c->V, p.n_valid, st));
+  RC(launch_cross_entropy(p.logits, c->Vp, c->V, ce_targets, ce_rows, PAD_ID, a.loss_scale * a.inv_accum, p.n_valid, p.row_loss, 1, st));
+  RC(launch_loss_reduce(p.row_loss, ce_rows, p.n_valid, a.inv_accum, a.loss_out, a.accumulate_loss, st));
+  return train_backward<T>(c, r, p, a.tokens, B, S, a.seg_events);
 }
-static int span_pred_refuse(const oasr_ctx* c, int B) {  // pred_out is indexed through the row table: no plain-step fall-back with it
-  OASR_REQUIRE(span_chunkable(c, B), "pred_out needs the chunk-row table: n_text_ctx = %d must be a multiple of 64 (<= %d) and B = %d <= 512",
-               c->S_max, 64 * OASR_ROWTAB, B);
-  return OASR_OK;
-}
-extern "C" int oasr_train_fwd_bwd_span_pred(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                            const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
-                                            float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
-                                            size_t workspace_bytes, int32_t* pred_out, void* stream) {
-  RC(check_bound(c, true));
-  OASR_REQUIRE(mel && tokens && targets && text_len && span_host && loss_out && workspace && B > 0, "oasr_train_fwd_bwd_span: bad args");
-  OASR_REQUIRE(forward_rows == OASR_SPAN_FORWARD_ALL || forward_rows == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_fwd_bwd_span: forward_rows");
-  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, c->S_max, OASR_MODE_TRAIN), "oasr_train_fwd_bwd_span: workspace too small");
-  if (pred_out) RC(span_pred_refuse(c, B));
-  if (!span_chunkable(c, B))
-    return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, mel, tokens, targets, text_len, B, c->S_max, loss_scale, inv_accum, loss_out,
-                         accumulate_loss, nullptr, ev, workspace, workspace_bytes, stream, mel_clip_max);
-  return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_span_impl, c, mel, tokens, targets, text_len, span_host, forward_rows, mel_clip_max, B, loss_scale,
-                       inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, nullptr, pred_out);
-}
-extern "C" int oasr_train_fwd_bwd_span(oasr_ctx* c, const float* mel, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                       const int32_t* span_host, int forward_rows, const float* mel_clip_max, int B, float loss_scale,
-                                       float inv_accum, float* loss_out, int accumulate_loss, void** ev, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-  return oasr_train_fwd_bwd_span_pred(c, mel, tokens, targets, text_len, span_host, forward_rows, mel_clip_max, B, loss_scale, inv_accum, loss_out,
-                                      accumulate_loss, ev, workspace, workspace_bytes, nullptr, stream);
+extern "C" size_t oasr_sizeof_train_step_args(void) { return sizeof(oasr_train_step_args); }
+extern "C" int oasr_train_step(oasr_ctx* c, const oasr_train_step_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(train_step_check(c, a, workspace, workspace_bytes));
+  return OASR_BY_DTYPE(c, train_step_impl, c, *a, a->span_host && span_chunkable(c, a->B), workspace, workspace_bytes, stream);
 }
 
 // ---- the same micro-step cut at the logits, for torch.autograd (OLMoASR.forward in training mode, olmoasr/model.py:856-887 followed
@@ -320,40 +290,4 @@ extern "C" int oasr_train_decode_bwd(oasr_ctx* c, const int64_t* tokens, const i
                "oasr_train_decode_bwd: bad args (tokens, text_len, dlogits and workspace are required, B > 0)");
   OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_decode_bwd: workspace too small");
   return OASR_BY_DTYPE(c, oasr_train_decode_bwd_impl, c, tokens, text_len, dlogits, B, S, dxa_out, workspace, workspace_bytes, stream);
-}
-// The fused loss step of the decoder alone, from the caller's encoder output (a frozen encoder whose xa is computed once and reused):
-// oasr_train_fwd_bwd_s / _span with the encoder forward replaced by a copy of xa.  Every segment event is recorded; the encoder's at once,
-// as the frozen-encoder step records them.
-extern "C" int oasr_train_dec_fwd_bwd_pred(oasr_ctx* c, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                           const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum,
-                                           float* loss_out, int accumulate_loss, void** ev, void* workspace, size_t workspace_bytes,
-                                           int32_t* pred_out, void* stream) {
-  RC(check_bound(c, true));
-  OASR_REQUIRE(xa && tokens && targets && text_len && loss_out && workspace && B > 0 && S > 0 && S <= c->S_max,
-               "oasr_train_dec_fwd_bwd: bad args (xa, tokens, targets, text_len, loss_out and workspace are required, 0 < S <= n_text_ctx)");
-  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, B, S, OASR_MODE_TRAIN_DEC), "oasr_train_dec_fwd_bwd: workspace too small");
-  if (c->pr.enc_any) {
-    oasr_set_error("oasr_train_dec_fwd_bwd: an encoder tensor is trainable -- the step from a given xa has no encoder backward (freeze the "
-                   "encoder, or use oasr_train_fwd_bwd*)");
-    return OASR_ESTATE;
-  }
-  if (pred_out) {
-    OASR_REQUIRE(span_host, "oasr_train_dec_fwd_bwd_pred: pred_out comes with span_host (the predictions cover the span's rows)");
-    RC(span_pred_refuse(c, B));
-  }
-  if (span_host && span_chunkable(c, B)) {
-    OASR_REQUIRE(S == c->S_max, "oasr_train_dec_fwd_bwd: a span step covers the whole context (S = %d, n_text_ctx = %d)", S, c->S_max);
-    OASR_REQUIRE(span_forward == OASR_SPAN_FORWARD_ALL || span_forward == OASR_SPAN_FORWARD_ACTIVE, "oasr_train_dec_fwd_bwd: span_forward");
-    return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_span_impl, c, nullptr, tokens, targets, text_len, span_host, span_forward, nullptr, B, loss_scale,
-                         inv_accum, loss_out, accumulate_loss, ev, workspace, workspace_bytes, stream, xa, pred_out);
-  }
-  // (no span, or no chunking for this shape: the plain step, same results)
-  return OASR_BY_DTYPE(c, oasr_train_fwd_bwd_s_impl, c, nullptr, tokens, targets, text_len, B, S, loss_scale, inv_accum, loss_out, accumulate_loss,
-                       nullptr, ev, workspace, workspace_bytes, stream, nullptr, xa);
-}
-extern "C" int oasr_train_dec_fwd_bwd(oasr_ctx* c, const void* xa, const int64_t* tokens, const int64_t* targets, const int32_t* text_len,
-                                      const int32_t* span_host, int span_forward, int B, int S, float loss_scale, float inv_accum, float* loss_out,
-                                      int accumulate_loss, void** ev, void* workspace, size_t workspace_bytes, void* stream) {
-  return oasr_train_dec_fwd_bwd_pred(c, xa, tokens, targets, text_len, span_host, span_forward, B, S, loss_scale, inv_accum, loss_out,
-                                     accumulate_loss, ev, workspace, workspace_bytes, nullptr, stream);
 }

@@ -645,7 +645,7 @@ extern "C" int oasr_log_mel(const void* pcm, int pcm_dtype, int B, int n_samples
 // The same front end WITHOUT its last pass: mel_raw = log10(max(mel power, 1e-10)) and clip_max[b] = the clip's maximum of it (device
 // f32 [B]).  whisper's last two lines -- log_spec = max(log_spec, log_spec.max() - 8); (log_spec + 4) / 4 -- need the clip maximum, i.e.
 // a second pass over the tensor; a consumer that reads the tensor anyway applies them on the fly instead
-// (oasr_train_fwd_bwd_span's mel_clip_max: the encoder's time-major transpose), which halves this front end's HBM traffic.
+// (oasr_train_step's mel_clip_max: the encoder's time-major transpose), which halves this front end's HBM traffic.
 extern "C" int oasr_log_mel_raw(const void* pcm, int pcm_dtype, int B, int n_samples, float* mel_raw, float* clip_max, void* workspace,
                                 hipStream_t stream) {
   OASR_REQUIRE(clip_max, "oasr_log_mel_raw: null clip_max");

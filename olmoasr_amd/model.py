@@ -138,6 +138,11 @@ class _EngineKV:
         return _EngineKV(m, {"cache": cache, "ws": ws, "B": Bn, "pos": self.state["pos"]})
 
 
+def _text_len_or_full(text_len: Optional[Tensor], B: int, S: int, device) -> Tensor:
+    """int32 [B] for the training entries, which need one: no padding mask = every one of the S positions is a key."""
+    return torch.full((B,), S, dtype=torch.int32, device=device) if text_len is None else text_len.to(torch.int32).contiguous()
+
+
 class _TrainStep(torch.autograd.Function):
     """OLMoASR.forward with a grad_fn: oasr_train_fwd keeps the saved activations in the model's workspace, backward hands
     d(loss)/d(logits) to oasr_train_bwd, which accumulates into the flat gradient arena (= every ``p.grad``).  Gradients do not
@@ -154,7 +159,7 @@ class _TrainStep(torch.autograd.Function):
         model._sync_for_autograd()
         mel = mel.float().contiguous()
         tokens = tokens.to(torch.int64).contiguous()
-        text_len = (torch.full((B,), S, dtype=torch.int32, device=mel.device) if text_len is None else text_len.to(torch.int32).contiguous())
+        text_len = _text_len_or_full(text_len, B, S, mel.device)
         ws = model._ws(B, S, 1)
         logits = torch.empty(B, S, model._n_rows, device=mel.device, dtype=torch.float32)
         with torch.cuda.device(mel.device):
@@ -230,7 +235,7 @@ class _DecoderStage(torch.autograd.Function):
         B, S = tokens.shape
         xa_c = xa.detach().to(model._act_dtype).contiguous()
         tokens = tokens.to(torch.int64).contiguous()
-        text_len = (torch.full((B,), S, dtype=torch.int32, device=tokens.device) if text_len is None else text_len.to(torch.int32).contiguous())
+        text_len = _text_len_or_full(text_len, B, S, tokens.device)
         ws = model._stage_ws("dec", B, S)
         logits = torch.empty(B, S, model._n_rows, device=tokens.device, dtype=torch.float32)
         with torch.cuda.device(tokens.device):
@@ -463,10 +468,7 @@ class TextDecoder(_ParamModule):
                 N.require_gpu(x, "tokens")
                 N.require_gpu(xa, "xa")
                 assert xa.shape == (x.shape[0], m.dims.n_audio_ctx, m.dims.n_audio_state), "incorrect audio feature shape"
-                text_len = None
-                if padding_mask is not None:
-                    text_len = padding_mask.to(torch.int32) if padding_mask.dim() == 1 else m._text_len_from_mask(padding_mask)
-                    text_len = text_len.to(x.device).contiguous()
+                text_len = m._text_len_of(padding_mask, x.device)
                 m._stage_begin(xa.requires_grad)
                 return _DecoderStage.apply(m._autograd_anchor(), m, x, xa, text_len)
             return m.logits(x, xa, padding_mask)
@@ -778,6 +780,14 @@ class OLMoASR(nn.Module):
         Recover len[b] = number of finite columns in row 0."""
         return torch.isfinite(padding_mask[:, 0, :]).sum(-1).to(torch.int32)
 
+    @classmethod
+    def _text_len_of(cls, padding_mask: Optional[Tensor], device) -> Optional[Tensor]:
+        """``padding_mask`` as the entries take it: int32 [B] on ``device`` from the reference's [B,S,S] mask or from a [B] text_len tensor; None stays None."""
+        if padding_mask is None:
+            return None
+        text_len = padding_mask.to(torch.int32) if padding_mask.dim() == 1 else cls._text_len_from_mask(padding_mask)
+        return text_len.to(device).contiguous()
+
     def _forward_impl(self, mel, tokens, text_len, want_logits=True, want_xa=False):
         N.require_gpu(mel, "mel")
         N.require_gpu(tokens, "tokens")
@@ -801,10 +811,7 @@ class OLMoASR(nn.Module):
         the reference's do: the caller's own loss and ``.backward()`` (train_timestamps.py:1440-1454 unchanged, GradScaler
         included) run the engine's backward from d(loss)/d(logits) and ACCUMULATE into ``p.grad`` of every parameter (views of the
         flat gradient arena).  ``loss_and_backward`` is the fused form of the same step (cross-entropy inside, no fp32 logits)."""
-        text_len = None
-        if padding_mask is not None:
-            text_len = padding_mask.to(torch.int32) if padding_mask.dim() == 1 else self._text_len_from_mask(padding_mask)
-            text_len = text_len.to(mel.device).contiguous()
+        text_len = self._text_len_of(padding_mask, mel.device)
         if torch.is_grad_enabled() and self.training and not self.inference:
             return _TrainStep.apply(self._autograd_anchor(), self, mel, tokens, text_len)
         with torch.no_grad():
@@ -889,10 +896,7 @@ class OLMoASR(nn.Module):
         xa = audio_features.to(self._act_dtype).contiguous()
         assert xa.shape == (B, self.dims.n_audio_ctx, self.dims.n_audio_state)
         tokens = tokens.to(torch.int64).contiguous()
-        text_len = None
-        if padding_mask is not None:
-            text_len = padding_mask.to(torch.int32) if padding_mask.dim() == 1 else self._text_len_from_mask(padding_mask)
-            text_len = text_len.to(tokens.device).contiguous()
+        text_len = self._text_len_of(padding_mask, tokens.device)
         ws = self._ws(B, S, 0)
         shape = (B, self._n_rows) if last_only else (B, S, self._n_rows)
         out = torch.empty(*shape, device=tokens.device, dtype=torch.float32)
@@ -1045,7 +1049,7 @@ class OLMoASR(nn.Module):
         """forward + F.cross_entropy(ignore_index=51864)/accumulation_steps + backward of (loss * loss_scale)
         (train_timestamps.py:1440-1454).  Gradients accumulate into ``flat_grads``.  Returns (loss tensor [1], logits|None).
 
-        ``span``: limit the decoder's BACKWARD to the positions that can carry gradient (``oasr_train_fwd_bwd_span``; the forward
+        ``span``: limit the decoder's BACKWARD to the positions that can carry gradient (``oasr_train_step``'s ``span_host``; the forward
         still covers all 448 positions, loss and gradients are those of the plain step up to fp32 summation order).  ``True``:
         derive it here from ``targets`` / ``text_len`` (one small device->host copy); a HOST int sequence / CPU tensor [B]: the
         caller's own bound (the data loader knows the token counts: every target at or past ``span[b]`` must be the ignore
@@ -1062,13 +1066,13 @@ class OLMoASR(nn.Module):
         reference computes and then ignores); logits are returned for those positions only.
 
         ``audio_features`` (with ``mel=None``): the step of a frozen encoder from its given output xa [B, n_audio_ctx, n_audio_state]
-        (``oasr_train_dec_fwd_bwd``): the decoder's forward, loss and backward only -- for features computed once (``embed_audio``, or
+        (``oasr_train_step``'s ``xa``): the decoder's forward, loss and backward only -- for features computed once (``embed_audio``, or
         ``model.encoder(mel)`` in training mode for the bits the fused step computes) and reused every epoch.  ``span``, ``span_forward``,
         ``segment_events``, ``loss_scale`` and ``accumulation_steps`` work as above; an encoder parameter that requires grad, ``mel_clip_max``,
         ``text_ctx`` and ``return_logits`` raise ``ValueError``.
 
         ``pred_out`` (with ``span``; ``mel`` or ``audio_features``): a contiguous int32 [B, n_text_ctx] device tensor that receives the
-        teacher-forced predictions (``oasr_train_fwd_bwd_span_pred``): ``argmax_c logits[b, s, c]`` over the n_vocab + 1 columns (lowest index
+        teacher-forced predictions (``oasr_train_step``'s ``pred_out``): ``argmax_c logits[b, s, c]`` over the n_vocab + 1 columns (lowest index
         among equal maxima) at every position ``s`` below ``span[b]`` rounded up to 64 -- the rows every forward mode computes -- and -1
         elsewhere.  One kernel between the decoder forward and the loss; no fp32 logits exist.  Loss and gradients are unchanged.  Without
         ``span``, or with ``return_logits`` / ``text_ctx``, it raises ``ValueError``."""
@@ -1094,6 +1098,11 @@ class OLMoASR(nn.Module):
             N.require_gpu(mel, "mel")
         for t, nm in ((tokens, "tokens"), (targets, "targets"), (text_len, "text_len")):
             N.require_gpu(t, nm)
+        span_on = span is not None and span is not False
+        if span_on and (return_logits or text_ctx is not None):
+            raise ValueError("span= cannot be combined with return_logits / text_ctx")
+        if mel_clip_max is not None and not span_on:
+            raise ValueError("mel_clip_max needs span= (the un-finalized log-mel is consumed by the span step only)")
         self.enable_grad_arena()
         B, S = tokens.shape
         assert S == self.dims.n_text_ctx, "training feeds the full padded context (train_timestamps.py:318-329)"
@@ -1110,6 +1119,10 @@ class OLMoASR(nn.Module):
         tokens = tokens.to(torch.int64).contiguous()
         targets = targets.to(torch.int64).contiguous()
         text_len = text_len.to(torch.int32).contiguous()
+        if mel_clip_max is not None:
+            N.require_gpu(mel_clip_max, "mel_clip_max")
+            mel_clip_max = mel_clip_max.float().contiguous()
+            assert mel_clip_max.numel() == B
         ws = self._ws(B, S, N.MODE_TRAIN_DEC if xa is not None else N.MODE_TRAIN)
         if loss_out is None:
             loss_out = torch.zeros(1, device=dev, dtype=torch.float32)
@@ -1122,63 +1135,24 @@ class OLMoASR(nn.Module):
                 raise N.NativeError("segment_events must be recorded-once torch.cuda.Event objects (null HIP event handle)")
             ev = (C.c_void_p * len(segment_events))(*handles)
         self._sync_trainable()
-        if xa is not None:
-            span_h = None
-            if span is not None and span is not False:
-                span_h = self.supervised_span(targets, text_len) if span is True else torch.as_tensor(span, dtype=torch.int32, device="cpu")
-                span_h = span_h.to(torch.int32).contiguous()
-                assert span_h.numel() == B and not span_h.is_cuda
-            with torch.cuda.device(dev):
-                if pred_out is not None:
-                    N.check(N.lib().oasr_train_dec_fwd_bwd_pred(self._ctx, N.ptr(xa), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
-                                                                C.c_void_p(span_h.data_ptr()), int(span_forward is None or bool(span_forward)), B, S,
-                                                                float(loss_scale), 1.0 / accumulation_steps, N.ptr(loss_out), int(accumulate_loss),
-                                                                ev, N.ptr(ws), ws.numel(), N.ptr(pred_out), N.stream_ptr()),
-                            "oasr_train_dec_fwd_bwd_pred")
-                    return loss_out, None
-                N.check(N.lib().oasr_train_dec_fwd_bwd(self._ctx, N.ptr(xa), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
-                                                       None if span_h is None else C.c_void_p(span_h.data_ptr()),
-                                                       int(span_forward is None or bool(span_forward)), B, S, float(loss_scale),
-                                                       1.0 / accumulation_steps, N.ptr(loss_out), int(accumulate_loss), ev, N.ptr(ws),
-                                                       ws.numel(), N.stream_ptr()), "oasr_train_dec_fwd_bwd")
-            return loss_out, None
-        if span is not None and span is not False:
-            if return_logits or text_ctx is not None:
-                raise ValueError("span= cannot be combined with return_logits / text_ctx")
+        span_h = None
+        if span_on:
             span_h = self.supervised_span(targets, text_len) if span is True else torch.as_tensor(span, dtype=torch.int32, device="cpu")
             span_h = span_h.to(torch.int32).contiguous()
             assert span_h.numel() == B and not span_h.is_cuda
-            if mel_clip_max is not None:
-                N.require_gpu(mel_clip_max, "mel_clip_max")
-                mel_clip_max = mel_clip_max.float().contiguous()
-                assert mel_clip_max.numel() == B
-            with torch.cuda.device(mel.device):
-                if pred_out is not None:
-                    N.check(N.lib().oasr_train_fwd_bwd_span_pred(self._ctx, N.ptr(mel), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
-                                                                 C.c_void_p(span_h.data_ptr()), int(span_forward is None or bool(span_forward)),
-                                                                 N.ptr(mel_clip_max), B, float(loss_scale), 1.0 / accumulation_steps,
-                                                                 N.ptr(loss_out), int(accumulate_loss), ev, N.ptr(ws), ws.numel(), N.ptr(pred_out),
-                                                                 N.stream_ptr()), "oasr_train_fwd_bwd_span_pred")
-                    return loss_out, None
-                N.check(N.lib().oasr_train_fwd_bwd_span(self._ctx, N.ptr(mel), N.ptr(tokens), N.ptr(targets), N.ptr(text_len),
-                                                        C.c_void_p(span_h.data_ptr()), int(span_forward is None or bool(span_forward)), N.ptr(mel_clip_max), B,
-                                                        float(loss_scale),
-                                                        1.0 / accumulation_steps,
-                                                        N.ptr(loss_out), int(accumulate_loss), ev, N.ptr(ws), ws.numel(), N.stream_ptr()),
-                        "oasr_train_fwd_bwd_span")
-            return loss_out, None
-        if mel_clip_max is not None:
-            raise ValueError("mel_clip_max needs span= (the un-finalized log-mel is consumed by oasr_train_fwd_bwd_span only)")
-        with torch.cuda.device(mel.device):
-            N.check(N.lib().oasr_train_fwd_bwd_s(self._ctx, N.ptr(mel), N.ptr(tokens), N.ptr(targets), N.ptr(text_len), B, S,
-                                                 float(loss_scale), 1.0 / accumulation_steps, N.ptr(loss_out), int(accumulate_loss),
-                                                 N.ptr(logits), ev, N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_train_fwd_bwd")
+        args = N.TrainStepArgs(mel=N.ptr(None if xa is not None else mel), xa=N.ptr(xa), tokens=N.ptr(tokens), targets=N.ptr(targets),
+                               text_len=N.ptr(text_len), span_host=N.ptr(span_h), mel_clip_max=N.ptr(mel_clip_max), loss_out=N.ptr(loss_out),
+                               logits_out=N.ptr(logits), pred_out=N.ptr(pred_out), seg_events=None if ev is None else C.cast(ev, C.c_void_p),
+                               B=B, S=S, span_forward=int(span_forward is None or bool(span_forward)), accumulate_loss=int(accumulate_loss),
+                               loss_scale=float(loss_scale), inv_accum=1.0 / accumulation_steps)
+        with torch.cuda.device(dev):
+            N.check(N.lib().oasr_train_step(self._ctx, C.byref(args), N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_train_step")
         return loss_out, logits
 
     @staticmethod
     def supervised_span(targets: Tensor, text_len: Tensor, ignore_index: int = 51864) -> Tensor:
         """HOST int32 [B]: per sample, one past the last decoder position that can carry gradient = max(text_len, index of the last
-        target != ignore_index + 1) -- what ``loss_and_backward(span=...)`` / ``oasr_train_fwd_bwd_span`` take."""
+        target != ignore_index + 1) -- what ``loss_and_backward(span=...)`` / ``oasr_train_step``'s ``span_host`` take."""
         S = targets.shape[1]
         pos = torch.arange(1, S + 1, device=targets.device, dtype=torch.int32)
         last = ((targets != ignore_index).to(torch.int32) * pos).amax(dim=1)

@@ -61,7 +61,7 @@ def synth_sample(index: int, timestamps: bool = False):
 
 def supervised_span_host(text_y: torch.Tensor, text_len: torch.Tensor) -> torch.Tensor:
     """HOST int32 [B] from HOST token tensors: per sample one past the last position that can carry gradient = max(text_len, index of
-    the last target != 51864 + 1) -- the bound ``OLMoASR.loss_and_backward(span=...)`` / ``oasr_train_fwd_bwd_span`` take.  The loaders
+    the last target != 51864 + 1) -- the bound ``OLMoASR.loss_and_backward(span=...)`` / ``oasr_train_step``'s ``span_host`` take.  The loaders
     build the token sequences on the host (like AudioTextDataset.preprocess_text, train_timestamps.py:238-343) and hand this out with
     every batch (``loader.last_span``), so the training loop never reads it back from the device."""
     assert not text_y.is_cuda and not text_len.is_cuda

@@ -54,7 +54,7 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     synthetic=True, n_synthetic=4096, timestamps=False, seed=0, bucket_cap_mb=128.0, reducer="allreduce", resume=False,
     force_dist=False,  # run the RCCL group / bucketed exchange / sharded step even at world_size 1 (single-GPU rehearsal of the N > 1 path)
     zero_stage=0,  # zero_stage 1: AdamW moments sharded over the ranks (olmoasr_amd/zero.py; the reference's FSDP script's role)
-    span_backward=True,  # decoder backward over the supervised span only (oasr_train_fwd_bwd_span; same loss / gradients, forward over all 448)
+    span_backward=True,  # decoder backward over the supervised span only (oasr_train_step's span_host; same loss / gradients, forward over all 448)
     span_forward=True,  # the decoder's forward leaves the padded positions out too (their logits are read by nothing; -4.7 % more); False = forward over all 448
     freeze_encoder=False,  # fine-tuning: encoder.* get requires_grad=False (no gradient, no update; the backward skips the encoder)
     # LoRA fine-tuning (olmoasr_amd/lora.py): rank-r adapters with scale alpha / r on the modules --lora_targets selects (comma-separated

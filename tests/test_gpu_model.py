@@ -149,7 +149,7 @@ def test_loss_scale_and_accumulation_are_linear(native_tiny, tiny_case):
 
 
 def test_trimmed_text_context_gives_the_full_context_step(native_tiny, tiny_case):
-    """oasr_train_fwd_bwd_s: running the decoder over ceil(max(text_len)) positions instead of the padded 448 must give
+    """oasr_train_step with S < n_text_ctx: running the decoder over ceil(max(text_len)) positions instead of the padded 448 must give
     the same loss, the same logits on those positions and the same gradients (padding rows contribute exact zeros)."""
     c = tiny_case
     args = (c["mel"].to(DEV), c["tokens"].to(DEV), c["targets"].to(DEV), c["text_len"].to(DEV))

@@ -1,4 +1,4 @@
-"""The supervised-span micro-step (oasr_train_fwd_bwd_span, olmoasr_amd/csrc/engine_step.hip): the decoder's token rows live in
+"""The supervised-span micro-step (oasr_train_step with span_host, olmoasr_amd/csrc/engine_step.hip): the decoder's token rows live in
 64-position chunks with every chunk that can carry gradient first, and the decoder's backward runs on those rows only.
 
  * the tables it builds (chunk rows, spans, targets in row order) against a host restatement;
@@ -176,7 +176,7 @@ def _rel(a, b):
 
 @pytest.mark.parametrize("variant,B,dtype", [("tiny", 6, "bfloat16"), ("tiny", 6, "float32"), ("base", 9, "bfloat16"), ("base", 3, "float32")])
 def test_span_step_equals_plain_step(variant, B, dtype):
-    """loss and every gradient of oasr_train_fwd_bwd_span == oasr_train_fwd_bwd (the reference schedule over all 448 positions)."""
+    """loss and every gradient of oasr_train_step with span_host == without (the reference schedule over all 448 positions)."""
     from olmoasr_amd import ops
     from olmoasr_amd.config.model_dims import VARIANT_TO_DIMS
     from olmoasr_amd.model import OLMoASR

@@ -1,6 +1,6 @@
 """model.encoder(mel) and model.decoder(tokens, xa) as differentiable modules: the staged autograd entries
 (oasr_train_encode / _encode_bwd / _decode / _decode_bwd), d(mel) through the conv1 fold kernel (csrc/conv_grad.hip), and the fused step
-from given encoder features (loss_and_backward(None, ..., audio_features=xa), oasr_train_dec_fwd_bwd).
+from given encoder features (loss_and_backward(None, ..., audio_features=xa), oasr_train_step from xa).
 
 "The fused rule" below is test_gpu_freeze.py's: bit-identical where the fused step repeats bit-identically, otherwise within 4x its own
 run-to-run spread (split-K weight gradients accumulate with fp32 atomics).  The stages keep their activations in other buffers than the fused

@@ -38,6 +38,7 @@ def test_library_exports_every_declared_symbol(native):
     hdr_ver = int(re.search(r"#define\s+OASR_ABI_VERSION\s+(\d+)", product).group(1))
     assert lib.oasr_version() == hdr_ver == native.ABI_VERSION
     assert lib.oasr_sizeof_attn_args() == ctypes.sizeof(native.AttnArgs)
+    assert lib.oasr_sizeof_train_step_args() == ctypes.sizeof(native.TrainStepArgs)
     assert int(re.search(r"#define\s+OASR_ROWTAB\s+(\d+)", product).group(1)) == native.ROWTAB
 
 

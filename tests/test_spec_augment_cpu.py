@@ -175,7 +175,7 @@ def test_bad_arguments_are_refused_by_the_library_and_the_binding(native):
     import torch
     from olmoasr_amd import augment, ops
     lib = native.lib()
-    assert lib.oasr_version() == 215 == native.ABI_VERSION
+    assert lib.oasr_version() == 216 == native.ABI_VERSION
     assert ctypes.sizeof(native.SpecAug) == lib.oasr_sizeof_specaug() == 20
     buf = torch.zeros(64, dtype=torch.int32)  # (host memory: every call below must be refused before anything is touched or launched)
     ok = native.SpecAug(2, 27, 2, 100, 0.0)

@@ -8,7 +8,7 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRIES = ("oasr_train_encode", "oasr_train_encode_bwd", "oasr_train_decode", "oasr_train_decode_bwd", "oasr_train_dec_fwd_bwd")
+ENTRIES = ("oasr_train_encode", "oasr_train_encode_bwd", "oasr_train_decode", "oasr_train_decode_bwd", "oasr_train_step")
 # oasr_workspace_bytes of the library before the stage entries existed (ABI 213), per (variant, compute dtype): (B, S, mode) -> bytes
 PINNED = {
     ("tiny", 0): {(2, 448, 0): 170051584, (2, 448, 1): 392684800, (128, 448, 0): 10882373632, (128, 448, 1): 24992949248},
@@ -39,8 +39,8 @@ def _ctx(native, variant, cdt=0):
 def test_abi_214_and_exports(native):
     lib = native.lib()
     hdr = open(os.path.join(ROOT, "include", "oasr.h")).read()
-    assert int(re.search(r"#define\s+OASR_ABI_VERSION\s+(\d+)", hdr).group(1)) == 215  # (215 adds test hooks only: the entries below are unchanged)
-    assert lib.oasr_version() == 215 == native.ABI_VERSION
+    assert int(re.search(r"#define\s+OASR_ABI_VERSION\s+(\d+)", hdr).group(1)) == 216  # (215 adds test hooks only; 216 moves the fused step from a given xa into oasr_train_step)
+    assert lib.oasr_version() == 216 == native.ABI_VERSION
     for name, val in (("OASR_MODE_TRAIN_ENC", native.MODE_TRAIN_ENC), ("OASR_MODE_TRAIN_DEC", native.MODE_TRAIN_DEC)):
         assert int(re.search(rf"#define\s+{name}\s+(\d+)", hdr).group(1)) == val
     for n in ENTRIES:
@@ -50,11 +50,12 @@ def test_abi_214_and_exports(native):
 
 def test_null_context_and_null_pointers_are_refused(native):
     lib = native.lib()
+    step = native.TrainStepArgs(B=2, S=448, loss_scale=1.0, inv_accum=1.0)  # every pointer null
     for call in (lambda c: lib.oasr_train_encode(c, None, 2, None, None, 0, None),
                  lambda c: lib.oasr_train_encode_bwd(c, None, 2, None, None, 0, None),
                  lambda c: lib.oasr_train_decode(c, None, None, None, 2, 448, None, None, 0, None),
                  lambda c: lib.oasr_train_decode_bwd(c, None, None, None, 2, 448, None, None, 0, None),
-                 lambda c: lib.oasr_train_dec_fwd_bwd(c, None, None, None, None, None, 0, 2, 448, 1.0, 1.0, None, 0, None, None, 0, None)):
+                 lambda c: lib.oasr_train_step(c, ctypes.byref(step), None, 0, None)):
         assert call(None) != 0
         assert lib.oasr_last_error()
     # a context that is not bound yet is refused before any pointer is looked at; bound to fake (never dereferenced) addresses, the
@@ -73,7 +74,7 @@ def test_null_context_and_null_pointers_are_refused(native):
         assert b"tokens" in lib.oasr_last_error()
         assert lib.oasr_train_decode_bwd(ctx, None, None, None, 2, 448, None, None, 0, None) == -1
         assert b"dlogits" in lib.oasr_last_error()
-        assert lib.oasr_train_dec_fwd_bwd(ctx, None, None, None, None, None, 0, 2, 448, 1.0, 1.0, None, 0, None, None, 0, None) == -1
+        assert lib.oasr_train_step(ctx, ctypes.byref(step), None, 0, None) == -1
         assert b"xa" in lib.oasr_last_error()
         assert lib.oasr_train_decode(ctx, fake, fake, fake, 2, 449, fake, fake, 1 << 40, None) == -1  # S > n_text_ctx
     finally:
