@@ -293,6 +293,14 @@ typedef struct oasr_attn_args {
    * d_o, dq; k_rows: k, v, dk, dv); q_span: optional int32 [B], multiples of 64 (backward): d_o is zero at query positions >=
    * q_span[b]; those rows are not read and their dq (self-attention: dk / dv too) not written. */
   const int32_t *q_rows, *k_rows, *q_span;
+  /* Compact grids over the span (added at the end without a new OASR_ABI_VERSION: a binding compares oasr_sizeof_attn_args with its own
+   * struct before the first call, which refuses a library built without these fields).  qblk128 / qblk256: optional int32 [n128 * H] / [n256 * H] tables of the 128- / 256-query blocks
+   * that start inside their sample's span (n128 = sum_b ceil(q_span[b] / 128), n256 likewise), in (sample, head, block) order, entry =
+   * sample << 16 | head << 4 | block -- as oasr_train_step builds them from span_host (tests: oasr_test_span_block_tables).  A launch
+   * that carries q_rows and q_span then starts n * H workgroups instead of one per block of the padded context; both tables come
+   * together; null = the full grid.  Results are bit-identical.  n128 == 0: nothing is launched. */
+  const int32_t *qblk128, *qblk256;
+  int n128, n256;
 } oasr_attn_args;
 #define OASR_ROWTAB 16
 /* sizeof(oasr_attn_args) as the library was built: a binding compares it with its own before the first call */

@@ -2,7 +2,7 @@
  * the drop-in surface: nothing on the training / decoding path calls them.  Users: bench.py (live GEMM roofline), tests/
  * (kernel-path forcing, hardware-behaviour probes that pin what the kernels rely on), scripts/ (A/B experiments).
  * The setters that change process-wide kernel selection (oasr_gemm_set_variant / _set_stagger / _force_general,
- * oasr_attention_set_pingpong, oasr_decode_set_ln_fold, oasr_span_set_side_streams) are INERT unless the process opts in with OASR_TESTING_HOOKS=1 in its
+ * oasr_attention_set_pingpong, oasr_attention_set_span_grid, oasr_decode_set_ln_fold, oasr_span_set_side_streams) are INERT unless the process opts in with OASR_TESTING_HOOKS=1 in its
  * environment: without it they return OASR_ESTATE and change nothing, so a production process cannot be steered through them. */
 #ifndef OASR_TESTING_H
 #define OASR_TESTING_H
@@ -46,6 +46,10 @@ int oasr_xcd_offsets_ok_debug(const int64_t* layer0, long long lstride, long lon
 /* tests / A-B: 1 (default) = the unmasked attention cases (encoder self-, cross-attention) run the 8-wave ping-pong kernels,
  * 0 = the general (maskable) kernels run everything.  Same results up to accumulation order (tests/test_gpu_ops.py). */
 int oasr_attention_set_pingpong(int on);
+/* tests / A-B: 1 (default) = an attention launch that carries block tables (oasr_attn_args.qblk128 / qblk256; the decoder attentions of
+ * oasr_train_step with span_host) starts one workgroup per query block inside the spans, 0 = the full grid over the padded context, whose
+ * blocks past the span exit at once.  Bit-identical results (tests/test_gpu_span_grid.py). */
+int oasr_attention_set_span_grid(int on);
 int oasr_gemm_set_stagger(int sleeps, int phases); /* experiments: first-wave phase stagger of the 256x256 kernel (0 = off) */
 int oasr_gemm_force_general(int on); /* tests: route every GEMM through the register-staged general kernel */
 /* tests: oasr_gemm with the launch options only the engine sets (csrc/kernels.h GemmArgs): colsum_scratch -- fp32 [2 * ceil(M/256)][N] partial
@@ -66,6 +70,11 @@ int oasr_probe_tr16(const void* src_bf16 /*[16][64]*/, void* dst_bf16 /*[64 lane
  * row order (active rows only); active_rows_out: HOST int64, the number of leading rows the decoder's backward runs over. */
 int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                           int64_t* targets_rows_out, int64_t* active_rows_out, void* stream);
+/* tests: the same launch with the query-block tables of the attention kernels' compact grids for H heads (oasr_attn_args.qblk128 / qblk256):
+ * blk128_out / blk256_out: device int32, B * ceil(S / 128) * H and B * ceil(S / 256) * H entries of room; counts_out: HOST int32 [2] =
+ * n128, n256 (blocks inside the spans, per head). */
+int oasr_test_span_block_tables(const int32_t* span_host, int B, int S, int H, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
+                                int64_t* targets_rows_out, int32_t* blk128_out, int32_t* blk256_out, int32_t* counts_out, void* stream);
 
 /* tests (tests/test_gpu_glue_ops.py): the glue launchers of csrc/kernels.h as unit operators -- the kernels between the GEMMs and the attention
  * that the training step reaches only inside a whole-model run.  Contracts: csrc/kernels.h, argument for argument.  dtype = OASR_DTYPE_BF16 (the

@@ -41,7 +41,8 @@ class AttnArgs(C.Structure):
                 ("H", C.c_int), ("Tq", C.c_int), ("Tk", C.c_int), ("causal", C.c_int), ("d_o", C.c_void_p),
                 ("delta", C.c_void_p), ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p), ("dq_colsum", C.c_void_p),
                 ("dv_colsum", C.c_void_p), ("colsum_scratch", C.c_void_p), ("qtile_flags", C.c_void_p),
-                ("q_rows", C.c_void_p), ("k_rows", C.c_void_p), ("q_span", C.c_void_p)]
+                ("q_rows", C.c_void_p), ("k_rows", C.c_void_p), ("q_span", C.c_void_p),
+                ("qblk128", C.c_void_p), ("qblk256", C.c_void_p), ("n128", C.c_int), ("n256", C.c_int)]
 
 
 class AlignArgs(C.Structure):  # include/oasr.h: oasr_align_args
@@ -71,6 +72,7 @@ class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
 DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_audio_ctx
 # The word-timestamp operators (oasr_alignment_matrix, oasr_dtw, oasr_test_dtw_host) add entry points without a new ABI generation: a library built before them is refused by the oasr_sizeof_align_args check in lib().
 # SpecAugment (oasr_spec_augment, oasr_spec_augment_plan) came the same way: entry points only, a stale library refused by the oasr_sizeof_specaug check in lib().
+# The query-block tables of oasr_attn_args (qblk128 / qblk256 / n128 / n256: compact grids of the span-limited attention launches) grow the struct at its end under the same version number: a library built without them is refused by the oasr_sizeof_attn_args check in lib().
 # Token error counts (oasr_edit_counts, oasr_edit_counts_host) and the prediction kernel's hook (oasr_test_argmax_rows) likewise: a stale library is refused by the oasr_sizeof_edit_args check in lib().
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
@@ -121,6 +123,7 @@ def _declare(lib):
         "oasr_log_mel_raw": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
         "oasr_sizeof_attn_args": (sz, []),
         "oasr_test_span_tables": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "oasr_test_span_block_tables": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "oasr_test_embedding_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp]),
         "oasr_test_embedding_bwd": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i64, i64, vp, vp, vp]),
         "oasr_test_colsum": (i32, [vp, i32, i64, i64, i32, vp, vp]),
@@ -186,6 +189,7 @@ def _declare(lib):
         "oasr_wide_supports_debug": (i32, [i32, i32, i32, i32, i32, i32, i32]),
         "oasr_wide_plan_debug": (i32, [i32, i32, i32, i32, i32, i32, vp, i32]),
         "oasr_attention_set_pingpong": (i32, [i32]),
+        "oasr_attention_set_span_grid": (i32, [i32]),
         "oasr_profile_gemm_collect": (i32, [vp, vp, vp, C.c_char_p, i32]),
     }
     for name, (res, args) in sig.items():

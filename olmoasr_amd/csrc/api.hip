@@ -96,6 +96,11 @@ extern "C" int oasr_attention_set_pingpong(int on) {
   attention_set_pingpong(on);
   return OASR_OK;
 }
+extern "C" int oasr_attention_set_span_grid(int on) {
+  OASR_HOOK_GATE("oasr_attention_set_span_grid");
+  attention_set_span_grid(on);
+  return OASR_OK;
+}
 extern "C" int oasr_gemm_force_general(int on) {
   OASR_HOOK_GATE("oasr_gemm_force_general");
   gemm_force_general(on);
@@ -159,6 +164,10 @@ static AttnArgs to_attn(const oasr_attn_args* a) {
   r.q_rows = a->q_rows;
   r.k_rows = a->k_rows;
   r.q_span = a->q_span;
+  r.qblk128 = a->qblk128;
+  r.qblk256 = a->qblk256;
+  r.n128 = a->n128;
+  r.n256 = a->n256;
   return r;
 }
 extern "C" int oasr_attention_fwd(const oasr_attn_args* a, void* stream) {
@@ -206,6 +215,18 @@ extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, con
   long act = 0;
   const int rc = launch_build_span_tables(span_host, B, S, targets, 51864, rows_out, span_out, targets_rows_out, &act, (hipStream_t)stream);
   *active_rows_out = act;
+  return rc;
+}
+
+extern "C" int oasr_test_span_block_tables(const int32_t* span_host, int B, int S, int H, const int64_t* targets, int32_t* rows_out,
+                                           int32_t* span_out, int64_t* targets_rows_out, int32_t* blk128_out, int32_t* blk256_out,
+                                           int32_t* counts_out, void* stream) {
+  OASR_REQUIRE(counts_out, "oasr_test_span_block_tables: null");
+  long act = 0;
+  SpanBlockTables blk{H, blk128_out, blk256_out, 0, 0};
+  const int rc = launch_build_span_tables(span_host, B, S, targets, 51864, rows_out, span_out, targets_rows_out, &act, (hipStream_t)stream, &blk);
+  counts_out[0] = blk.n128;
+  counts_out[1] = blk.n256;
   return rc;
 }
 

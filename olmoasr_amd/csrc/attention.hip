@@ -169,6 +169,29 @@ __device__ __forceinline__ void store_rows_bf16(char* stg, const f32x16_t (&T)[2
 // Wave-uniform when t is (scalar load); entries past the last chunk hold a row far outside every tensor.
 __device__ __forceinline__ int chunk_row(const int32_t* rows, int b, int t) { return rows[b * OASR_ROWTAB + (t >> 6)] + (t & 63); }
 
+// Which (sample, head, query / key block) a workgroup works on.  Full grid: `bid` counts (b, h, block) with `nblk` blocks per (b, h).
+// Compact grid of a span-limited launch (ROWS only; kernels.h: AttnArgs.qblk128 / qblk256): `bid` indexes the table of the blocks that
+// lie inside the spans, in the same (b, h, block) order -- one scalar load, and no workgroup exists for a block past the span.
+struct BlockId {
+  int b, h, blk;
+};
+template <bool ROWS>
+__device__ __forceinline__ BlockId block_id(const int32_t* tab, int bid, int nblk, int H) {
+  BlockId r;
+  if (ROWS && tab) {  // (block-uniform)
+    const int e = tab[bid];
+    r.b = e >> 16;
+    r.h = (e >> 4) & 0xfff;
+    r.blk = e & 15;
+  } else {
+    const int bh = bid / nblk;
+    r.b = bh / H;
+    r.h = bh - r.b * H;
+    r.blk = bid - bh * nblk;
+  }
+  return r;
+}
+
 // Softmax arithmetic on pairs: gfx950's v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 process two fp32 values per lane per
 // issue slot.  With head_dim 64 these kernels are VALU-issue bound (16 MFMAs against ~145 scalar VALU per 64-key tile and
 // wave in the forward), so halving the fma / add / mul counts is what moves them; the exponential stays one v_exp_f32 each.
@@ -242,9 +265,9 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnArgs a) {
   // L2 once and re-used by the other query blocks (round-robin dispatch would fetch them through all 8 L2s).
   const int nqb = (a.Tq + 127) >> 7;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = bid / nqb;
-  const int b = bh / a.H, h = bh - b * a.H;
-  const int q0 = (bid - bh * nqb) * 128;
+  const BlockId id = block_id<ROWS>(a.qblk128, bid, nqb, a.H);
+  const int b = id.b, h = id.h, qblk = id.blk;
+  const int q0 = qblk * 128;
   const int myq = q0 + wave * 32 + (lane & 31);
   const int myq_c = myq < a.Tq ? myq : a.Tq - 1;
   const bool krows = ROWS && a.k_rows != nullptr;  // (block-uniform)
@@ -433,15 +456,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
   // L2 once and re-used by the other query blocks (round-robin dispatch would fetch them through all 8 L2s).
   const int nqb = (a.Tq + 127) >> 7;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = bid / nqb;
-  const int b = bh / a.H, h = bh - b * a.H;
-  const int q0 = (bid - bh * nqb) * 128;
+  const BlockId id = block_id<ROWS>(a.qblk128, bid, nqb, a.H);
+  const int b = id.b, h = id.h, qblk = id.blk;
+  const int q0 = qblk * 128;
   const int myq = q0 + wave * 32 + (lane & 31);
   const bool krows = ROWS && a.k_rows != nullptr;  // (block-uniform)
   // span-limited backward: query positions >= q_span[b] hold no gradient -- their d_o / o rows are not read, dq is not written
   const int q_lim = (ROWS && a.q_span) ? min(a.q_span[b], a.Tq) : a.Tq;
   if (ROWS && q0 >= q_lim) {  // (block-uniform) nothing to do, but the partial bias-gradient row of this block must read as zeros
-    if (a.dq_colsum && tid < 64) a.colsum_scratch[((long)(b * nqb + (bid - bh * nqb)) * a.H + h) * 64 + tid] = 0.f;
+    if (a.dq_colsum && tid < 64) a.colsum_scratch[((long)(b * nqb + qblk) * a.H + h) * 64 + tid] = 0.f;
     return;
   }
   const bool w_act = !ROWS || q0 + wave * 32 < q_lim;        // (wave-uniform; spans are multiples of 64)
@@ -586,7 +609,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs a) {
   if (a.dq_colsum) {  // one partial row per workgroup: colsum_scratch[(b, query block)][h*64 + c], reduced by the launcher
     __syncthreads();
     if (tid < 64)
-      a.colsum_scratch[((long)(b * nqb + (bid - bh * nqb)) * a.H + h) * 64 + tid] =
+      a.colsum_scratch[((long)(b * nqb + qblk) * a.H + h) * 64 + tid] =
           (wsum[tid] + wsum[64 + tid]) + (wsum[128 + tid] + wsum[192 + tid]);
   }
 }
@@ -622,14 +645,14 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dq_pp_kernel(AttnArgs a) {
   const unsigned smem_a = (unsigned)(size_t)smem;
   const int nqb = (a.Tq + 255) >> 8;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = bid / nqb;
-  const int b = bh / a.H, h = bh - b * a.H;
-  const int q0 = (bid - bh * nqb) * 256;
+  const BlockId id = block_id<ROWS>(a.qblk256, bid, nqb, a.H);
+  const int b = id.b, h = id.h, qblk = id.blk;
+  const int q0 = qblk * 256;
   const int myq = q0 + wave * 32 + (lane & 31);
   const int q_lim = (ROWS && a.q_span) ? min(a.q_span[b], a.Tq) : a.Tq;
   if (ROWS && q0 >= q_lim) {  // (block-uniform) no gradient in this block: only its two partial bias-gradient rows must read as zeros
     if (a.dq_colsum && tid < 128) {
-      const int nqb128 = (a.Tq + 127) >> 7, blk128 = (bid - bh * nqb) * 2 + (tid >> 6);
+      const int nqb128 = (a.Tq + 127) >> 7, blk128 = qblk * 2 + (tid >> 6);
       if (blk128 < nqb128) a.colsum_scratch[((long)(b * nqb128 + blk128) * a.H + h) * 64 + (tid & 63)] = 0.f;
     }
     return;
@@ -869,7 +892,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dq_pp_kernel(AttnArgs a) {
     if (tid < 128) {
       const int half = tid >> 6, c = tid & 63;
       const int nqb128 = (a.Tq + 127) >> 7;
-      const int blk128 = (bid - bh * nqb) * 2 + half;
+      const int blk128 = qblk * 2 + half;
       if (blk128 < nqb128)
         a.colsum_scratch[((long)(b * nqb128 + blk128) * a.H + h) * 64 + c] =
             (wsum[half * 256 + c] + wsum[half * 256 + 64 + c]) + (wsum[half * 256 + 128 + c] + wsum[half * 256 + 192 + c]);
@@ -895,9 +918,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
   const int nkb = (a.Tk + 127) >> 7;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = bid / nkb;
-  const int b = bh / a.H, h = bh - b * a.H;
-  const int k0 = (bid - bh * nkb) * 128;
+  // (a block table here is the query-block table of a self-attention over chunked key rows: the key blocks past the span are the empty ones)
+  const BlockId id = block_id<ROWS>(a.qblk128, bid, nkb, a.H);
+  const int b = id.b, h = id.h, kblk = id.blk;
+  const int k0 = kblk * 128;
   const int mykey = k0 + wave * 32 + (lane & 31);
   const bool krows = ROWS && a.k_rows != nullptr;  // (block-uniform) chunked key rows: decoder self-attention
   // span-limited backward: query positions >= q_span[b] hold no gradient (their d_o rows are never read); with chunked key rows the
@@ -905,7 +929,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs a) {
   const int q_lim = (ROWS && a.q_span) ? min(a.q_span[b], a.Tq) : a.Tq;
   const long dv_scratch_off0 = (long)a.B * ((a.Tq + 127) >> 7) * a.H * 64;
   if (krows && a.q_span && k0 >= q_lim) {
-    if (a.dv_colsum && tid < 64) a.colsum_scratch[dv_scratch_off0 + ((long)(b * nkb + (bid - bh * nkb)) * a.H + h) * 64 + tid] = 0.f;
+    if (a.dv_colsum && tid < 64) a.colsum_scratch[dv_scratch_off0 + ((long)(b * nkb + kblk) * a.H + h) * 64 + tid] = 0.f;
     return;
   }
   const bool w_store = !(krows && a.q_span) || k0 + wave * 32 < q_lim;  // (wave-uniform)
@@ -962,7 +986,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs a) {
   // dv partial rows live behind the dq ones: [B * ceil(Tq/128)][H*64] then [B * ceil(Tk/128)][H*64]
   const long dv_scratch_off = dv_scratch_off0;
   if (!any) {  // every key of this block is padding: dK = dV = 0 (uniform early exit, before any load is issued)
-    if (a.dv_colsum && tid < 64) a.colsum_scratch[dv_scratch_off + ((long)(b * nkb + (bid - bh * nkb)) * a.H + h) * 64 + tid] = 0.f;
+    if (a.dv_colsum && tid < 64) a.colsum_scratch[dv_scratch_off + ((long)(b * nkb + kblk) * a.H + h) * 64 + tid] = 0.f;
     if (mykey < a.Tk && w_store) {
       bf16_t* dkp0 = krows ? a.dk + (long)chunk_row(a.k_rows, b, mykey) * a.ldk + h * 64 : a.dk + (long)b * a.bsk + (long)mykey * a.ldk + h * 64;
       bf16_t* dvp0 = krows ? a.dv + (long)chunk_row(a.k_rows, b, mykey) * a.ldv + h * 64 : a.dv + (long)b * a.bsv + (long)mykey * a.ldv + h * 64;
@@ -1064,7 +1088,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnArgs a) {
     if (a.dv_colsum) {
       __syncthreads();
       if (tid < 64)
-        a.colsum_scratch[dv_scratch_off + ((long)(b * nkb + (bid - bh * nkb)) * a.H + h) * 64 + tid] =
+        a.colsum_scratch[dv_scratch_off + ((long)(b * nkb + kblk) * a.H + h) * 64 + tid] =
             (wsum[tid] + wsum[64 + tid]) + (wsum[128 + tid] + wsum[192 + tid]);
     }
   }
@@ -1431,6 +1455,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnArgs a) {
 }
 
 int g_attn_pingpong = 1;  // tests / A-B (oasr_attention_set_pingpong): 0 routes the unmasked case through the general kernels
+int g_attn_span_grid = 1;  // tests / A-B (oasr_attention_set_span_grid): 0 launches the full grid even when a block table is given
+
+// A block table is used where the blocks it leaves out are the ones that exit at once: chunked query rows limited by q_span.
+bool span_grid(const AttnArgs& a) { return g_attn_span_grid && a.q_rows && a.q_span && a.qblk128 && a.qblk256; }
 
 int check_args(const AttnArgs& a, bool bwd) {
   OASR_REQUIRE(a.q && a.k && a.v && a.o, "attention: null pointer");
@@ -1443,12 +1471,17 @@ int check_args(const AttnArgs& a, bool bwd) {
   OASR_REQUIRE(!a.q_span || a.q_rows, "attention: q_span needs q_rows");
   OASR_REQUIRE(!a.q_rows || ((a.Tq % 64) == 0 && a.Tq <= 64 * OASR_ROWTAB), "attention: chunked query rows need Tq %% 64 == 0 and Tq <= %d", 64 * OASR_ROWTAB);
   OASR_REQUIRE(!a.k_rows || ((a.Tk % 64) == 0 && a.Tk <= 64 * OASR_ROWTAB), "attention: chunked key rows need Tk %% 64 == 0 and Tk <= %d", 64 * OASR_ROWTAB);
+  OASR_REQUIRE(!a.qblk128 == !a.qblk256, "attention: the 128- and the 256-query block tables come together");
+  OASR_REQUIRE(!a.qblk128 || (a.n128 >= 0 && a.n128 <= a.B * cdiv(a.Tq, 128) && a.n256 >= 0 && a.n256 <= a.B * cdiv(a.Tq, 256) && a.n256 <= a.n128 &&
+                              a.n128 <= 2 * a.n256),
+               "attention: block counts n128 = %d, n256 = %d do not fit B = %d, Tq = %d", a.n128, a.n256, a.B, a.Tq);
   return OASR_OK;
 }
 
 }  // namespace
 
 void attention_set_pingpong(int on) { g_attn_pingpong = on; }
+void attention_set_span_grid(int on) { g_attn_span_grid = on; }
 
 int launch_attention_fwd(const AttnArgs& a, hipStream_t s) {
   int rc = check_args(a, false);
@@ -1460,10 +1493,17 @@ int launch_attention_fwd(const AttnArgs& a, hipStream_t s) {
   }
   dim3 grid(cdiv(a.Tq, 128) * a.B * a.H);
   if (a.q_rows) {
+    AttnArgs r = a;
+    if (span_grid(a)) {  // only the query blocks inside the spans
+      if (a.n128 == 0) return OASR_OK;
+      grid = dim3(a.n128 * a.H);
+    } else {
+      r.qblk128 = r.qblk256 = nullptr;
+    }
     if (a.causal)
-      hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), 0, s, r);
     else
-      hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, s, r);
   } else if (a.causal) {
     hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, dim3(256), 0, s, a);
   } else {
@@ -1476,12 +1516,31 @@ int launch_attention_fwd(const AttnArgs& a, hipStream_t s) {
 int launch_attention_bwd(const AttnArgs& a, hipStream_t s) {
   int rc = check_args(a, true);
   if (rc) return rc;
-  dim3 gq(cdiv(a.Tq, 128) * a.B * a.H), gk(cdiv(a.Tk, 128) * a.B * a.H);
+  dim3 gq(cdiv(a.Tq, 128) * a.B * a.H), gk(cdiv(a.Tk, 128) * a.B * a.H), gq256(cdiv(a.Tq, 256) * a.B * a.H);
   const bool rows = a.q_rows != nullptr;
+  const int d = a.H * 64;
+  const long rq = (long)a.B * cdiv(a.Tq, 128), rk = (long)a.B * cdiv(a.Tk, 128);
+  // Compact grids (kernels.h: AttnArgs.qblk128 / qblk256).  aq: the arguments of the dQ kernel; ak: of the dK/dV kernel, which takes the
+  // table only where its empty blocks are the same ones -- chunked KEY rows, i.e. the decoder's self-attention.
+  AttnArgs aq = a, ak = a;
+  const bool cq = rows && span_grid(a), ck = cq && a.k_rows != nullptr && a.Tk == a.Tq;
+  if (!cq) aq.qblk128 = aq.qblk256 = nullptr;
+  if (!ck) ak.qblk128 = ak.qblk256 = nullptr;
+  if (cq) {
+    if (a.n128 == 0) return OASR_OK;  // every span is 0: no gradient anywhere, nothing to add to the bias gradients
+    gq = dim3(a.n128 * a.H);
+    gq256 = dim3(a.n256 * a.H);
+    if (ck) gk = gq;
+    // The partial bias-gradient rows keep their [B * ceil(T / 128)] layout (the reduction below sums the same rows as with the full
+    // grid); the rows of the blocks that are no longer launched are zeroed here instead of by their workgroups.
+    const long zrows = (a.dq_colsum ? rq : 0) + (ck && a.dv_colsum ? rk : 0);
+    float* z0 = a.dq_colsum ? a.colsum_scratch : a.colsum_scratch + rq * d;
+    if (zrows) OASR_CHECK_HIP(hipMemsetAsync(z0, 0, (size_t)zrows * d * sizeof(float), s));
+  }
   if (a.causal) {
     if (rows) {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), gq, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, true>), gk, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), gq, dim3(256), 0, s, aq);
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, true>), gk, dim3(256), 0, s, ak);
     } else {
       hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), gq, dim3(256), 0, s, a);
       hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, false>), gk, dim3(256), 0, s, a);
@@ -1495,7 +1554,7 @@ int launch_attention_bwd(const AttnArgs& a, hipStream_t s) {
     // NOT taken: with the same kernels on both sides the span step reproduces the plain step's arithmetic row by row (gradients equal to
     // 1e-7, fp32 summation order only; tests/test_gpu_span.py), with a different dK/dV kernel only to bf16 rounding (2.6e-4).
     if (pp) {
-      if (rows) hipLaunchKernelGGL(attn_bwd_dq_pp_kernel<true>, dim3(cdiv(a.Tq, 256) * a.B * a.H), dim3(512), 0, s, a);
+      if (rows) hipLaunchKernelGGL(attn_bwd_dq_pp_kernel<true>, gq256, dim3(512), 0, s, aq);
       else hipLaunchKernelGGL(attn_bwd_dq_pp_kernel<false>, dim3(cdiv(a.Tq, 256) * a.B * a.H), dim3(512), 0, s, a);
       static LdsAttrOnce attr_rows, attr_plain;
       rc = rows ? ensure_dynamic_lds(attr_rows, (const void*)attn_bwd_dkdv_pp_kernel<true>, KLDS)
@@ -1504,8 +1563,8 @@ int launch_attention_bwd(const AttnArgs& a, hipStream_t s) {
       if (rows) hipLaunchKernelGGL(attn_bwd_dkdv_pp_kernel<true>, dim3(cdiv(a.Tk, 256) * a.B * a.H), dim3(512), KLDS, s, a);
       else hipLaunchKernelGGL(attn_bwd_dkdv_pp_kernel<false>, dim3(cdiv(a.Tk, 256) * a.B * a.H), dim3(512), KLDS, s, a);
     } else if (rows) {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true>), gk, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), 0, s, aq);
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true>), gk, dim3(256), 0, s, ak);
     } else {
       hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), gq, dim3(256), 0, s, a);
       hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false>), gk, dim3(256), 0, s, a);
@@ -1513,8 +1572,6 @@ int launch_attention_bwd(const AttnArgs& a, hipStream_t s) {
   }
   OASR_LAUNCH_CHECK();
   // fused query / value bias gradients: reduce the per-workgroup partial rows (a few MB) into the fp32 gradients
-  const int d = a.H * 64;
-  const long rq = (long)a.B * cdiv(a.Tq, 128), rk = (long)a.B * cdiv(a.Tk, 128);
   if (a.dq_colsum) {
     int rc2 = launch_colsum_accum(a.colsum_scratch, d, rq, d, a.dq_colsum, s);
     if (rc2) return rc2;

@@ -306,11 +306,30 @@ struct SpanArg {
 // position-block-major (c outer, b inner), then the inactive ones in the same order.
 __global__ __launch_bounds__(1024) void build_span_tables_kernel(SpanArg sp, int B, int S, const int64_t* __restrict__ targets, long ignore,
                                                                  int32_t* __restrict__ rows, int32_t* __restrict__ span_dev,
-                                                                 int64_t* __restrict__ targets_phys) {
+                                                                 int64_t* __restrict__ targets_phys, int H, int32_t* __restrict__ blk128,
+                                                                 int32_t* __restrict__ blk256) {
   __shared__ int cnt_act[OASR_ROWTAB + 1];  // active chunks in position blocks < c
   __shared__ int rows_s[512 * OASR_ROWTAB];
   const int nch = S >> 6, tid = threadIdx.x;
   if (tid <= OASR_ROWTAB) cnt_act[tid] = 0;
+  // Query-block tables of the attention kernels' compact grids (kernels.h: AttnArgs.qblk128 / qblk256): the 128- / 256-query blocks that
+  // start inside their sample's span, in (sample, head, block) order -- all blocks of one (sample, head) adjacent, as the kernels'
+  // XCD-contiguous block order wants them.  Entry count: H * sum_b ceil(ceil64(span[b]) / gran), what the launcher returns on the host.
+  if (blk128) {
+    for (int i = tid; i < B * H; i += 1024) {
+      const int b = i / H, h = i - b * H;
+      int pre128 = 0, pre256 = 0;  // blocks of the samples before b
+      for (int bb = 0; bb < b; ++bb) {
+        const int s64 = ((int)sp.span[bb] + 63) & ~63;
+        pre128 += (s64 + 127) >> 7;
+        pre256 += (s64 + 255) >> 8;
+      }
+      const int s64 = ((int)sp.span[b] + 63) & ~63;
+      const int n1 = (s64 + 127) >> 7, n2 = (s64 + 255) >> 8;
+      for (int j = 0; j < n1; ++j) blk128[(pre128 * H + h * n1) + j] = attn_qblk_pack(b, h, j);
+      for (int j = 0; j < n2; ++j) blk256[(pre256 * H + h * n2) + j] = attn_qblk_pack(b, h, j);
+    }
+  }
   __syncthreads();
   if (tid < nch) {  // active samples of position block tid
     int n = 0;
@@ -344,20 +363,27 @@ __global__ __launch_bounds__(1024) void build_span_tables_kernel(SpanArg sp, int
 }
 }  // namespace
 int launch_build_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, long ignore, int32_t* rows, int32_t* span_dev,
-                             int64_t* targets_phys, long* active_rows, hipStream_t s) {
+                             int64_t* targets_phys, long* active_rows, hipStream_t s, SpanBlockTables* blocks) {
   OASR_REQUIRE(span_host && targets && rows && span_dev && targets_phys && active_rows, "build_span_tables: null pointer");
+  OASR_REQUIRE(!blocks || (blocks->H > 0 && blocks->H < 4096 && blocks->blk128 && blocks->blk256), "build_span_tables: bad block tables");
   OASR_REQUIRE(B > 0 && B <= 512 && S > 0 && S % 64 == 0 && S <= 64 * OASR_ROWTAB, "build_span_tables: need B <= 512, S %% 64 == 0, S <= %d (B=%d S=%d)",
                64 * OASR_ROWTAB, B, S);
   SpanArg sp;
   long act = 0;
+  int n128 = 0, n256 = 0;
   for (int b = 0; b < B; ++b) {
     OASR_REQUIRE(span_host[b] >= 0 && span_host[b] <= S, "build_span_tables: span[%d] = %d outside [0, %d]", b, span_host[b], S);
     sp.span[b] = (uint16_t)span_host[b];
-    act += (span_host[b] + 63) / 64 * 64;
+    const int s64 = (span_host[b] + 63) / 64 * 64;
+    act += s64;
+    n128 += (s64 + 127) / 128;
+    n256 += (s64 + 255) / 256;
   }
   for (int b = B; b < 512; ++b) sp.span[b] = 0;
   *active_rows = act;
-  hipLaunchKernelGGL(build_span_tables_kernel, dim3(1), dim3(1024), 0, s, sp, B, S, targets, ignore, rows, span_dev, targets_phys);
+  if (blocks) blocks->n128 = n128, blocks->n256 = n256;
+  hipLaunchKernelGGL(build_span_tables_kernel, dim3(1), dim3(1024), 0, s, sp, B, S, targets, ignore, rows, span_dev, targets_phys,
+                     blocks ? blocks->H : 0, blocks ? blocks->blk128 : nullptr, blocks ? blocks->blk256 : nullptr);
   OASR_LAUNCH_CHECK();
   return OASR_OK;
 }

@@ -53,6 +53,10 @@ struct Plan {
   int32_t* qtile_flags;  // attention backward of the decoder: which 64-position tiles of d_o are non-zero
   // supervised-span step (oasr_train_step with span_host): chunk-row table of the decoder's token rows, spans, targets in row order
   int32_t *rows, *span_dev;
+  // query-block tables of the decoder attentions' compact grids (kernels.h: AttnArgs.qblk128 / qblk256).  They live in the slot of
+  // qtile_flags: a span step does not use the flags (the span says where the all-zero tiles of d_o are), a plain step has no tables.
+  // Null when the slot is too small for them (a 64-position context): the step then launches the full grids.
+  int32_t *blk128, *blk256;
   int64_t* targets_phys;
   float *lora_dw, *lora_part;  // adapter contexts: the adapted weights' gradients (oasr_ctx::Lora::dw) and lora_grad's partial sums
 };
@@ -162,7 +166,14 @@ static void make_plan(const oasr_ctx* c, Arena& A, Plan& p, int B, int S, bool t
     // (the largest of the three attention shapes)
     p.cs_scratch = A.f32(stage == STAGE_DEC ? attn_colsum_scratch_floats(B, c->H, S, S > c->Te ? S : c->Te)
                                             : attn_colsum_scratch_floats(B, c->H, c->Te, c->Te));
-    if (dec) p.qtile_flags = (int32_t*)A.f32((size_t)B * c->H * ((S + 63) / 64) + 16);
+    if (dec) {
+      const size_t n_flags = (size_t)B * c->H * ((S + 63) / 64) + 16, n128 = span_block_entries(B, S, c->H, 128);
+      p.qtile_flags = (int32_t*)A.f32(n_flags);
+      if (n128 + span_block_entries(B, S, c->H, 256) <= n_flags) {  // (every context of two or more 64-position chunks)
+        p.blk128 = p.qtile_flags;
+        p.blk256 = p.qtile_flags + n128;
+      }
+    }
     p.gemm_cs_scratch = A.f32((size_t)2 * cdiv(Mmax, 256) * 4 * d + 64);
     if (enc) {
       p.tmp_w1p = A.f32((long)d * 256);
@@ -193,6 +204,9 @@ struct Runner {
   const int32_t* dec_rows = nullptr;  // chunk-row table [B][OASR_ROWTAB] (device) or null = plain [B, S] rows
   const int32_t* dec_span = nullptr;  // [B] spans rounded up to 64 (device); backward only
   long dec_rows_bwd = 0;              // active decoder rows (0 = all B*S)
+  // the query blocks inside the spans, and how many there are per head: the span-limited decoder attentions are launched over these
+  const int32_t *dec_blk128 = nullptr, *dec_blk256 = nullptr;
+  int dec_n128 = 0, dec_n256 = 0;
   // opt-in (OASR_SPAN_FORWARD_ACTIVE): the decoder's FORWARD covers the active rows only as well.  The rows left out are the padded
   // positions whose logits the reference computes and nothing ever reads (no supervised query attends to them, the loss ignores them).
   long dec_rows_fwd = 0;
@@ -417,6 +431,10 @@ struct Runner {
       a.q_rows = dec_rows;
       a.k_rows = cross ? nullptr : dec_rows;
       if (dec_rows_fwd) a.q_span = dec_span;  // (the backward sets it itself)
+      a.qblk128 = dec_blk128;  // (used by the launches that carry q_span: the blocks past the span are the ones they do not compute)
+      a.qblk256 = dec_blk256;
+      a.n128 = dec_n128;
+      a.n256 = dec_n256;
     }
     return OASR_OK;
   }

@@ -152,10 +152,15 @@ static int train_step_impl(oasr_ctx* c, const oasr_train_step_args& a, bool chun
   long ce_rows = Md;
   if (chunked) {
     long R = 0;
-    RC(launch_build_span_tables(a.span_host, B, S, a.targets, PAD_ID, p.rows, p.span_dev, p.targets_phys, &R, st));
+    SpanBlockTables blk{c->H, p.blk128, p.blk256, 0, 0};
+    RC(launch_build_span_tables(a.span_host, B, S, a.targets, PAD_ID, p.rows, p.span_dev, p.targets_phys, &R, st, p.blk128 ? &blk : nullptr));
     OASR_REQUIRE(R > 0, "oasr_train_step: no position of the micro-batch carries gradient (every span is 0)");
     r.dec_rows = p.rows;
     r.dec_span = p.span_dev;
+    r.dec_blk128 = p.blk128;
+    r.dec_blk256 = p.blk256;
+    r.dec_n128 = blk.n128;
+    r.dec_n256 = blk.n256;
     r.dec_rows_bwd = R;
     r.dec_rows_fwd = a.span_forward == OASR_SPAN_FORWARD_ACTIVE ? R : 0;
     if (const int mode = span_side_streams()) RC(r.side_begin(mode));

@@ -557,7 +557,10 @@ int launch_embedding_bwd(const int64_t* tok, const float* dx, float* dE, float* 
 int launch_colsum_accum(const float* x, long ld, long M, int ncols, float* out, hipStream_t s) {
   OASR_REQUIRE(x && out && ncols > 0, "colsum(f32): bad args");
   if (M <= 0) return OASR_OK;
-  long gy = M < 256 ? M : 256;
+  // Up to 64 rows one workgroup per 256 columns adds them in row order: no atomics between workgroups, so the sums are bit-stable from run
+  // to run (small batches; tests/test_gpu_span_grid.py compares bias gradients exactly).  More rows are spread over y-blocks whose fp32
+  // atomics land in any order.
+  long gy = M <= 64 ? 1 : (M < 256 ? M : 256);
   hipLaunchKernelGGL(colsum_f32_kernel, dim3(cdiv(ncols, 256), (unsigned)gy), dim3(256), 0, s, x, ld, M, ncols, out);
   OASR_LAUNCH_CHECK();
   return OASR_OK;

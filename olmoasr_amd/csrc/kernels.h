@@ -136,7 +136,17 @@ struct AttnArgsT {
   // q_span: optional int32 [B], multiples of 64 (backward only): d_o of sample b is zero at every query position >= q_span[b];
   // those rows of d_o / o are not read, dq (and, for self-attention, dk / dv: their keys see no supervised query) not written.
   const int32_t* q_span;
+  // ---- compact grids over the span (with q_rows and q_span) --------------------------------------------------------------------
+  // qblk128 / qblk256: optional int32 [n128 * H] / [n256 * H] block tables written by launch_build_span_tables from the SAME spans as
+  // q_span: entry v = attn_qblk_pack(b, h, query block) of the v-th 128- / 256-query block that lies inside its sample's span, in
+  // (b, h, block) order; n128 = sum_b ceil(q_span[b] / 128), n256 likewise.  The chunked-row kernels are then launched over n * H
+  // workgroups instead of ceil(Tq / 128 | 256) * B * H of which those past the span only exit.  Null = the full grid.  n128 == 0 (every
+  // span 0): nothing is launched.  Results are bit-identical to the full grid's.
+  const int32_t *qblk128, *qblk256;
+  int n128, n256;
 };
+// block-table entry: sample << 16 | head << 4 | query block (B <= 512, <= 16 blocks)
+__host__ __device__ static inline int32_t attn_qblk_pack(int b, int h, int blk) { return (int32_t)((b << 16) | (h << 4) | blk); }
 #ifndef OASR_ROWTAB
 #define OASR_ROWTAB 16  // (also defined by include/oasr.h)
 #endif
@@ -150,6 +160,7 @@ int launch_attention_bwd(const AttnArgs& a, hipStream_t s);
 // qk of MultiHeadAttention.qkv_attention (model.py:347-442): fp32 pre-softmax scaled scores [B, H, Tq, Tk], masked entries -inf (scores.hip)
 int launch_attention_scores(const AttnArgs& a, float* out, hipStream_t s);
 void attention_set_pingpong(int on);  // testing hook: 0 = general kernels for the unmasked case too
+void attention_set_span_grid(int on);  // testing hook: 0 = the full grid even when a block table (AttnArgs.qblk128 / qblk256) is given
 int launch_attention_fwd(const AttnArgsF& a, hipStream_t s);  // fp32 validation kernels (o_lo unused: O is fp32)
 int launch_attention_bwd(const AttnArgsF& a, hipStream_t s);
 int launch_attention_scores(const AttnArgsF& a, float* out, hipStream_t s);
@@ -213,8 +224,16 @@ int launch_embedding_bwd(const int64_t* tok, const bf16_t* dx, float* dE, float*
 //   rows [B][OASR_ROWTAB]: the chunk-row table -- the active chunks (64*c < span[b]) of all samples first, position-block-major,
 //                          then the inactive ones; span_dev [B] = span rounded up to 64; targets_phys [B*S]: targets in row order
 // Returns the number of active token rows through *active_rows (host).  S % 64 == 0, S <= 64 * OASR_ROWTAB, B <= 512.
+// blocks (optional): the query-block tables of AttnArgs.qblk128 / qblk256 for H heads, written by the same launch; the counts come back
+// on the host (they follow from span_host alone: no synchronisation).
+struct SpanBlockTables {
+  int H;
+  int32_t *blk128, *blk256;  // device, span_block_entries(B, S, H, 128 | 256) entries
+  int n128, n256;            // out (host): blocks inside the spans, per head
+};
+static inline size_t span_block_entries(int B, int S, int H, int gran) { return (size_t)B * ((S + gran - 1) / gran) * H; }
 int launch_build_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, long ignore, int32_t* rows, int32_t* span_dev,
-                             int64_t* targets_phys, long* active_rows, hipStream_t s);
+                             int64_t* targets_phys, long* active_rows, hipStream_t s, SpanBlockTables* blocks = nullptr);
 // out[n] += sum_m x[m, n]   (x bf16 [M, ld], columns [0, ncols))
 int launch_colsum_accum(const bf16_t* x, long ld, long M, int ncols, float* out, hipStream_t s);
 // conv2 input-gradient fold + conv1 GELU backward: dpre1[b,t,c] = gelu'(u1) * sum of the dA windows covering t

@@ -178,6 +178,32 @@ def from_chunked(xc, tab, B, T):
     return out
 
 
+def span_block_tables(span, B, S, H, device="cuda", with_rows=False):
+    """The query-block tables of the span-limited attention launches (include/oasr.h: oasr_attn_args.qblk128 / qblk256) for the HOST
+    spans ``span`` (int32 [B]) and H heads, built by the device kernel oasr_train_step uses: returns (blk128, blk256, n128, n256) --
+    device int32 tensors with room for every block of the padded context, and the number of blocks inside the spans per head.
+    with_rows: also the chunk-row table [B, ROWTAB] and the spans rounded up to 64 (device int32) of the same launch."""
+    span = torch.as_tensor(span, dtype=torch.int32).cpu().contiguous()
+    assert span.numel() == B
+    blk128 = torch.full((B * ((S + 127) // 128) * H,), -1, dtype=torch.int32, device=device)
+    blk256 = torch.full((B * ((S + 255) // 256) * H,), -1, dtype=torch.int32, device=device)
+    targets = torch.full((B, S), 51864, dtype=torch.int64, device=device)
+    rows = torch.empty(B, N.ROWTAB, dtype=torch.int32, device=device)
+    span_d = torch.empty(B, dtype=torch.int32, device=device)
+    tphys = torch.empty(B * S, dtype=torch.int64, device=device)
+    counts = (C.c_int32 * 2)()
+    N.check(N.lib().oasr_test_span_block_tables(C.c_void_p(span.data_ptr()), B, S, H, N.ptr(targets), N.ptr(rows), N.ptr(span_d), N.ptr(tphys),
+                                                N.ptr(blk128), N.ptr(blk256), counts, N.stream_ptr(device)), "span_block_tables")
+    blocks = (blk128, blk256, int(counts[0]), int(counts[1]))
+    return (blocks, rows, span_d) if with_rows else blocks
+
+
+def _set_blocks(a, q_blocks):
+    if q_blocks is not None:
+        blk128, blk256, n128, n256 = q_blocks
+        a.qblk128, a.qblk256, a.n128, a.n256 = blk128.data_ptr(), blk256.data_ptr(), n128, n256
+
+
 def _attn_args_rows(qc, kc, vc, oc, lse, B, H, Tq, Tk, q_rows, k_rows, kv_len, causal):
     """qc / oc: chunked [B*Tq, H, 64] views (any token stride); kc / vc: chunked [B*Tk, H, 64] when k_rows is given, else plain [B, Tk, H, 64]."""
     a = N.AttnArgs()
@@ -195,21 +221,31 @@ def _attn_args_rows(qc, kc, vc, oc, lse, B, H, Tq, Tk, q_rows, k_rows, kv_len, c
     return a
 
 
-def attention_fwd_rows(qc, kc, vc, B, H, Tq, Tk, q_rows, k_rows=None, kv_len=None, causal=False, want_o_lo=False):
-    """attention_fwd on chunked token rows: returns oc [B*Tq, H*64] (chunked like qc), lse [B, H, Tq] (logical)(, o_lo)."""
+def attention_fwd_rows(qc, kc, vc, B, H, Tq, Tk, q_rows, k_rows=None, kv_len=None, causal=False, want_o_lo=False, q_span=None, q_blocks=None,
+                       fill=None):
+    """attention_fwd on chunked token rows: returns oc [B*Tq, H*64] (chunked like qc), lse [B, H, Tq] (logical)(, o_lo).
+    q_span (device int32 [B]): the span-limited forward -- rows past it are not computed; q_blocks: ``span_block_tables`` of the same spans
+    (compact grid); fill: the outputs are pre-filled with it, so that a test can see which rows were left untouched."""
     oc = torch.empty(B * Tq, H * 64, device=qc.device, dtype=BF)
     lse = torch.empty(B, H, Tq, device=qc.device, dtype=torch.float32)
-    a = _attn_args_rows(qc, kc, vc, oc.view(B * Tq, H, 64), lse, B, H, Tq, Tk, q_rows, k_rows, kv_len, causal)
     o_lo = torch.empty_like(oc) if want_o_lo else None
+    if fill is not None:
+        for t in (oc, lse, o_lo):
+            if t is not None:
+                t.fill_(fill)
+    a = _attn_args_rows(qc, kc, vc, oc.view(B * Tq, H, 64), lse, B, H, Tq, Tk, q_rows, k_rows, kv_len, causal)
     a.o_lo = o_lo.data_ptr() if want_o_lo else None
+    a.q_span = q_span.data_ptr() if q_span is not None else None
+    _set_blocks(a, q_blocks)
     N.check(N.lib().oasr_attention_fwd(C.byref(a), N.stream_ptr()), "attention_fwd(rows)")
     return (oc, lse, o_lo) if want_o_lo else (oc, lse)
 
 
 def attention_bwd_rows(qc, kc, vc, oc, lse, doc, B, H, Tq, Tk, q_rows, k_rows=None, q_span=None, kv_len=None, causal=False, o_lo=None,
-                       dq_colsum=None, dv_colsum=None, fill=None):
+                       dq_colsum=None, dv_colsum=None, fill=None, q_blocks=None, scratch_fill=None):
     """attention_bwd on chunked token rows.  Gradients are allocated with the operands' strides and pre-filled with ``fill`` (e.g. NaN)
-    so that a test can see which rows the kernels left untouched."""
+    so that a test can see which rows the kernels left untouched.  q_blocks: ``span_block_tables`` of the spans in q_span (compact
+    grids); scratch_fill: what the bias gradients' scratch rows hold on entry (nothing may depend on it)."""
     def like(t):
         g = torch.empty_strided(t.shape, t.stride(), device=t.device, dtype=t.dtype)
         if fill is not None:
@@ -227,7 +263,10 @@ def attention_bwd_rows(qc, kc, vc, oc, lse, doc, B, H, Tq, Tk, q_rows, k_rows=No
     scratch = None
     if dq_colsum is not None or dv_colsum is not None:
         scratch = torch.empty(B * ((Tq + 127) // 128 + (Tk + 127) // 128) * H * 64, device=qc.device, dtype=torch.float32)
+        if scratch_fill is not None:
+            scratch.fill_(scratch_fill)
         a.colsum_scratch = scratch.data_ptr()
+    _set_blocks(a, q_blocks)
     N.check(N.lib().oasr_attention_bwd(C.byref(a), N.stream_ptr()), "attention_bwd(rows)")
     return dq, dk, dv
 
