@@ -202,6 +202,23 @@ typedef struct oasr_train_step_args {
   int32_t span_forward; /* OASR_SPAN_FORWARD_*; read with span_host only */
   int32_t accumulate_loss;
   float loss_scale, inv_accum; /* inv_accum = 1 / accumulation steps */
+  /* Regularisers of the objective (added at the end without a new OASR_ABI_VERSION, like oasr_attn_args' compact-grid fields: a binding
+   * compares oasr_sizeof_train_step_args before the first call).  All zero / NULL: exactly the step without them, launch for launch.  For a
+   * valid row (target t in [0, V), t != ignore_index) with logits x over the V = n_vocab + 1 classes, lse = logsumexp(x), p = softmax(x):
+   *     row_loss  = lse - (1 - eps) * x_t - (eps / V) * sum_{c < V} x_c + z * lse^2
+   *     dlogits_c = g * [(1 + 2 * z * lse) * p_c - (1 - eps) * [c == t] - eps / V]        g = loss_scale * inv_accum / n_valid
+   * = F.cross_entropy(ignore_index, label_smoothing = eps) + z * mean_valid(lse^2) (the PaLM / OLMo z-loss); ignored rows and the padded
+   * columns of the tied head keep zero loss and exactly zero gradient; loss_out = mean_valid(row_loss) * inv_accum, the objective that is
+   * differentiated.  One more workgroup reduction (sum x) inside the cross-entropy kernel, no extra pass over the logits.  Every form of the
+   * step (plain, span_host in both forward modes, xa, logits_out, pred_out) and both compute dtypes take them.
+   * label_smoothing in [0, 1), z_loss >= 0, both finite; else OASR_EINVAL. */
+  float label_smoothing; /* eps */
+  float z_loss;          /* z */
+  /* The objective's parts on request: NULL, or device f32 [2] = { mean_valid(lse - x_t), mean_valid(lse^2) } * inv_accum, overwritten /
+   * accumulated like loss_out (so loss_out = (1 - eps) * parts[0] + z * parts[1] + eps * mean_valid(lse - mean_c x) * inv_accum). */
+  float* loss_parts_out;
+  /* With loss_parts_out (OASR_EINVAL without): device f32 [2, B * S] per-row scratch the caller owns (the workspace plans do not grow). */
+  float* loss_parts_rows;
 } oasr_train_step_args;
 size_t oasr_sizeof_train_step_args(void);
 int oasr_train_step(oasr_ctx*, const oasr_train_step_args*, void* workspace, size_t workspace_bytes, void* stream);
@@ -410,6 +427,14 @@ int oasr_edit_counts(const oasr_edit_args*, void* stream);
 int oasr_edit_counts_host(const oasr_edit_args*);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
+/* The same operator with the regularisers of oasr_train_step_args (label_smoothing, z_loss: the formula there; gscale takes the place of
+ * loss_scale * inv_accum) -- an entry point only, OASR_ABI_VERSION is unchanged.  row_loss / loss_out hold the regularised objective.
+ * row_parts: NULL, or device f32 [2, rows]: row_parts[0][r] = lse - x_t, row_parts[1][r] = lse^2 (0 for ignored rows).
+ * label_smoothing = z_loss = 0 and row_parts = NULL: oasr_cross_entropy itself, which forwards here.  Values outside [0, 1) / below 0 / not
+ * finite: OASR_EINVAL. */
+int oasr_cross_entropy_ex(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
+                          int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, float label_smoothing, float z_loss,
+                          float* row_parts, void* stream);
 int oasr_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
 /* The two LoRA kernels as unit operators (the engine calls the same launchers).  merge: out = w0 + scale * B . A (w0 [rows, cols] f32,
  * A [rank, cols], B [rows, rank]; out_dtype OASR_DTYPE_BF16 / OASR_DTYPE_F32; out may be w0 for f32).  grad: dA += scale * B^T . dW,

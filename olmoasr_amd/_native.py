@@ -66,7 +66,8 @@ class EditArgs(C.Structure):  # include/oasr.h: oasr_edit_args
 class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
     _fields_ = [(n, C.c_void_p) for n in ("mel", "xa", "tokens", "targets", "text_len", "span_host", "mel_clip_max", "loss_out", "logits_out",
                                           "pred_out", "seg_events")] + \
-               [(n, C.c_int32) for n in ("B", "S", "span_forward", "accumulate_loss")] + [("loss_scale", C.c_float), ("inv_accum", C.c_float)]
+               [(n, C.c_int32) for n in ("B", "S", "span_forward", "accumulate_loss")] + [("loss_scale", C.c_float), ("inv_accum", C.c_float)] + \
+               [("label_smoothing", C.c_float), ("z_loss", C.c_float), ("loss_parts_out", C.c_void_p), ("loss_parts_rows", C.c_void_p)]
 
 
 DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_audio_ctx
@@ -74,6 +75,7 @@ DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_
 # SpecAugment (oasr_spec_augment, oasr_spec_augment_plan) came the same way: entry points only, a stale library refused by the oasr_sizeof_specaug check in lib().
 # The query-block tables of oasr_attn_args (qblk128 / qblk256 / n128 / n256: compact grids of the span-limited attention launches) grow the struct at its end under the same version number: a library built without them is refused by the oasr_sizeof_attn_args check in lib().
 # Token error counts (oasr_edit_counts, oasr_edit_counts_host) and the prediction kernel's hook (oasr_test_argmax_rows) likewise: a stale library is refused by the oasr_sizeof_edit_args check in lib().
+# Label smoothing / z-loss (oasr_train_step_args.label_smoothing, z_loss, loss_parts_out, loss_parts_rows; oasr_cross_entropy_ex) grow the step's struct at its end and add one entry point under the same version number: a library built without them is refused by the oasr_sizeof_train_step_args check in lib().
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
@@ -170,6 +172,7 @@ def _declare(lib):
         "oasr_edit_counts_host": (i32, [C.POINTER(EditArgs)]),
         "oasr_test_argmax_rows": (i32, [vp, i32, i64, i32, i64, vp, vp, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
+        "oasr_cross_entropy_ex": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, f32, f32, vp, vp]),
         "oasr_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
         "oasr_pick_tokens": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, vp]),
         "oasr_pick_tokens_ts": (i32, [vp, i64, i32, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp]),

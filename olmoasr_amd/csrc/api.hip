@@ -321,15 +321,27 @@ extern "C" int oasr_test_argmax_rows(const void* logits, int dtype, int64_t ld, 
   return launch_argmax_rows((const float*)logits, (long)ld, V, (long)n_rows, rows, span, B, S, pred_out, (hipStream_t)stream);
 }
 
-extern "C" int oasr_cross_entropy(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
-                                  int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream) {
+extern "C" int oasr_cross_entropy_ex(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
+                                     int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, float label_smoothing, float z_loss,
+                                     float* row_parts, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = launch_count_valid(targets, rows, ignore, V, n_valid_dev, st);
+  int rc = check_ce_reg("oasr_cross_entropy_ex", label_smoothing, z_loss);
   if (rc) return rc;
-  rc = launch_cross_entropy((bf16_t*)logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, write_grad, st);
+  CeReg reg;
+  reg.eps = label_smoothing;
+  reg.z = z_loss;
+  reg.parts = row_parts;
+  reg.parts_stride = (long)rows;
+  rc = launch_count_valid(targets, rows, ignore, V, n_valid_dev, st);
+  if (rc) return rc;
+  rc = launch_cross_entropy((bf16_t*)logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, write_grad, st, reg);
   if (rc) return rc;
   if (loss_out) rc = launch_loss_reduce(row_loss, rows, n_valid_dev, 1.0f, loss_out, 0, st);
   return rc;
+}
+extern "C" int oasr_cross_entropy(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
+                                  int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream) {
+  return oasr_cross_entropy_ex(logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, loss_out, write_grad, 0.f, 0.f, nullptr, stream);
 }
 
 extern "C" int oasr_pick_tokens(const float* logits, int64_t ld, int V, int64_t rows, const float* mask, const float* mask2, int64_t* tok,

@@ -129,6 +129,8 @@ static int train_step_check(const oasr_ctx* c, const oasr_train_step_args* a, co
   // pred_out is indexed through the row table: no plain-step fall-back with it
   OASR_REQUIRE(!a->pred_out || span_chunkable(c, a->B),
                "pred_out needs the chunk-row table: n_text_ctx = %d must be a multiple of 64 (<= %d) and B = %d <= 512", c->S_max, 64 * OASR_ROWTAB, a->B);
+  RC(check_ce_reg("oasr_train_step", a->label_smoothing, a->z_loss));
+  OASR_REQUIRE(!a->loss_parts_out || a->loss_parts_rows, "oasr_train_step: loss_parts_out needs loss_parts_rows (f32 [2, B * S] of per-row scratch the caller owns)");
   OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, a->B, a->S, a->xa ? OASR_MODE_TRAIN_DEC : OASR_MODE_TRAIN), "oasr_train_step: workspace too small");
   if (a->xa && c->pr.enc_any) {
     oasr_set_error("oasr_train_step: an encoder tensor is trainable -- the step from a given xa has no encoder backward (freeze the "
@@ -176,8 +178,18 @@ static int train_step_impl(oasr_ctx* c, const oasr_train_step_args& a, bool chun
   if (a.pred_out) RC(launch_argmax_rows(p.logits, c->Vp, c->V, Md, p.rows, p.span_dev, B, S, a.pred_out, st));
   // loss (chunked: over the active rows; the other rows' targets are ignore_index: they add nothing to the sum and nothing to the count)
   RC(launch_count_valid(a.targets, Md, PAD_ID, c->V, p.n_valid, st));
-  RC(launch_cross_entropy(p.logits, c->Vp, c->V, ce_targets, ce_rows, PAD_ID, a.loss_scale * a.inv_accum, p.n_valid, p.row_loss, 1, st));
+  // label smoothing / z-loss (all zero: the plain kernel); the parts' per-row values go to the caller's scratch, never to the workspace
+  CeReg reg;
+  reg.eps = a.label_smoothing;
+  reg.z = a.z_loss;
+  reg.parts = a.loss_parts_out ? a.loss_parts_rows : nullptr;
+  reg.parts_stride = Md;
+  RC(launch_cross_entropy(p.logits, c->Vp, c->V, ce_targets, ce_rows, PAD_ID, a.loss_scale * a.inv_accum, p.n_valid, p.row_loss, 1, st, reg));
   RC(launch_loss_reduce(p.row_loss, ce_rows, p.n_valid, a.inv_accum, a.loss_out, a.accumulate_loss, st));
+  if (reg.parts) {
+    RC(launch_loss_reduce(reg.parts, ce_rows, p.n_valid, a.inv_accum, a.loss_parts_out, a.accumulate_loss, st));
+    RC(launch_loss_reduce(reg.parts + Md, ce_rows, p.n_valid, a.inv_accum, a.loss_parts_out + 1, a.accumulate_loss, st));
+  }
   return train_backward<T>(c, r, p, a.tokens, B, S, a.seg_events);
 }
 extern "C" size_t oasr_sizeof_train_step_args(void) { return sizeof(oasr_train_step_args); }

@@ -440,9 +440,12 @@ __device__ __forceinline__ float block_reduce_f(float v, float* red, bool is_max
   __syncthreads();
   return is_max ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
 }
+// REG: label smoothing eps and z-loss z (include/oasr.h at oasr_train_step_args.label_smoothing), one more reduction (sum_{c<V} x_c)
+template <bool REG>
 __global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits, long ld, int V, const int64_t* __restrict__ targets,
                                                     long ignore, float gscale, const int32_t* __restrict__ n_valid_dev,
-                                                    float* __restrict__ row_loss, int write_grad) {
+                                                    float* __restrict__ row_loss, int write_grad, float eps, float zc,
+                                                    float* __restrict__ parts, long parts_stride) {
   __shared__ float red[4];
   const long row = blockIdx.x;
   float* lr = logits + row * ld;
@@ -450,21 +453,46 @@ __global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits,
   if (tgt == ignore || tgt < 0 || tgt >= V) {
     if (write_grad)
       for (int c = threadIdx.x; c < ld; c += 256) lr[c] = 0.f;
-    if (threadIdx.x == 0) row_loss[row] = 0.f;
+    if (threadIdx.x == 0) {
+      row_loss[row] = 0.f;
+      if (REG && parts) parts[row] = parts[parts_stride + row] = 0.f;
+    }
     return;
   }
   float mx = -INFINITY;
-  for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, lr[c]);
+  float xs = 0.f;
+  for (int c = threadIdx.x; c < V; c += 256) {
+    mx = fmaxf(mx, lr[c]);
+    if (REG) xs += lr[c];
+  }
   mx = block_reduce_f(mx, red, true);
+  if (REG) xs = block_reduce_f(xs, red, false);
   float sum = 0.f;
   for (int c = threadIdx.x; c < V; c += 256) sum += expf(lr[c] - mx);
   sum = block_reduce_f(sum, red, false);
   const float lse = mx + logf(sum);
-  if (threadIdx.x == 0) row_loss[row] = lse - lr[tgt];
+  const float ev = REG ? eps / (float)V : 0.f;
+  if (threadIdx.x == 0) {
+    const float nll = lse - lr[tgt];
+    if (REG) {
+      row_loss[row] = nll + eps * lr[tgt] - ev * xs + zc * lse * lse;
+      if (parts) {
+        parts[row] = nll;
+        parts[parts_stride + row] = lse * lse;
+      }
+    } else {
+      row_loss[row] = nll;
+    }
+  }
   if (!write_grad) return;
   __syncthreads();
   const float g = gscale / (float)max(1, *n_valid_dev);
-  for (int c = threadIdx.x; c < ld; c += 256) lr[c] = c < V ? (expf(lr[c] - lse) - (c == tgt ? 1.f : 0.f)) * g : 0.f;
+  if (REG) {
+    const float k = 1.f + 2.f * zc * lse;
+    for (int c = threadIdx.x; c < ld; c += 256) lr[c] = c < V ? (k * expf(lr[c] - lse) - (c == tgt ? 1.f - eps : 0.f) - ev) * g : 0.f;
+  } else {
+    for (int c = threadIdx.x; c < ld; c += 256) lr[c] = c < V ? (expf(lr[c] - lse) - (c == tgt ? 1.f : 0.f)) * g : 0.f;
+  }
 }
 
 }  // namespace
@@ -592,11 +620,16 @@ int launch_logits_to_f32(const float* logits, long ld, long rows, int V, float* 
   return OASR_OK;
 }
 int launch_cross_entropy(float* logits, long ld, int V, const int64_t* targets, long rows, long ignore, float gscale,
-                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s) {
+                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s, const CeReg& reg) {
   OASR_REQUIRE(logits && targets && n_valid_dev && row_loss && V <= ld, "cross_entropy(f32): bad args");
+  OASR_REQUIRE(!reg.parts || reg.parts_stride >= rows, "cross_entropy(f32): row_parts stride %ld below rows = %ld", reg.parts_stride, rows);
   if (rows <= 0) return OASR_OK;
-  hipLaunchKernelGGL(ce_f32_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, V, targets, ignore, gscale, n_valid_dev, row_loss,
-                     write_grad);
+  if (reg.on())
+    hipLaunchKernelGGL(ce_f32_kernel<true>, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, V, targets, ignore, gscale, n_valid_dev, row_loss,
+                       write_grad, reg.eps, reg.z, reg.parts, reg.parts_stride);
+  else
+    hipLaunchKernelGGL(ce_f32_kernel<false>, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, V, targets, ignore, gscale, n_valid_dev, row_loss,
+                       write_grad, 0.f, 0.f, (float*)nullptr, 0L);
   OASR_LAUNCH_CHECK();
   return OASR_OK;
 }

@@ -266,10 +266,21 @@ int launch_dlogits_from_f32(const float* src, int V, long rows, long ld, float* 
 // (zeros for ignored rows and pad columns), row_loss[r] = lse - logit[target] (0 for ignored rows).
 // n_valid_dev: device int32 (count of targets != ignore).  loss_out += sum(row_loss)/n_valid * loss_mul.
 int launch_count_valid(const int64_t* targets, long rows, long ignore, int V, int32_t* n_valid_dev, hipStream_t s);
+// CeReg: the regularisers of the objective (include/oasr.h at oasr_train_step_args.label_smoothing); all zero = the plain kernel, launch for
+// launch.  Otherwise row_loss[r] = lse - (1 - eps) x_t - eps / V sum_{c<V} x_c + z lse^2, dlogits = g [(1 + 2 z lse) softmax - (1 - eps) onehot
+// - eps / V] on the first V columns (pad columns and ignored rows stay exactly zero); parts (optional): parts[r] = lse - x_t,
+// parts[parts_stride + r] = lse^2.
+struct CeReg {
+  float eps = 0.f, z = 0.f;
+  float* parts = nullptr;
+  long parts_stride = 0;
+  bool on() const { return eps != 0.f || z != 0.f || parts; }
+};
+int check_ce_reg(const char* who, float label_smoothing, float z_loss);  // OASR_EINVAL naming the field: eps outside [0, 1), z < 0, non-finite
 int launch_cross_entropy(bf16_t* logits, long ld, int V, const int64_t* targets, long rows, long ignore, float gscale,
-                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s);
+                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s, const CeReg& reg = CeReg());
 int launch_cross_entropy(float* logits, long ld, int V, const int64_t* targets, long rows, long ignore, float gscale,
-                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s);  // fp32 validation
+                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s, const CeReg& reg = CeReg());  // fp32 validation
 int launch_loss_reduce(const float* row_loss, long rows, const int32_t* n_valid_dev, float mul, float* loss_out, int accumulate,
                        hipStream_t s);
 

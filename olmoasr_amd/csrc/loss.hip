@@ -36,9 +36,17 @@ __device__ __forceinline__ float block_reduce8(float v, float* red, bool is_max)
   return r;
 }
 
-__global__ __launch_bounds__(CE_THREADS) void ce_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ targets,
+// REG = false is the plain objective and the kernel of every step that sets no regulariser.  REG = true (label smoothing eps, z-loss z;
+// the formula: include/oasr.h at oasr_train_step_args.label_smoothing) is the same single pass with one more workgroup reduction, sum_{c<V} x_c,
+// taken from the registers the maximum is taken from: full chunks add their eight values unguarded, and only the chunks that straddle V
+// (the branch that already exists for the -inf overwrite) test columns -- there the padded columns add 0 to the sum and, in the epilogue,
+// are written as exact zeros instead of -g eps / V (the tied-head GEMM reads them).
+// The second __launch_bounds__ argument (waves per SIMD) holds REG at the plain kernel's two workgroups per CU: left alone it takes 66 VGPRs.
+template <bool REG>
+__global__ __launch_bounds__(CE_THREADS, REG ? 8 : 1) void ce_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ targets,
                                                  long ignore, float gscale, const int32_t* __restrict__ n_valid_dev,
-                                                 float* __restrict__ row_loss, int write_grad) {
+                                                 float* __restrict__ row_loss, int write_grad, float eps, float zc,
+                                                 float* __restrict__ parts, long parts_stride) {
   __shared__ float red[CE_THREADS / 64];
   const long row = blockIdx.x;
   bf16_t* lr = logits + row * ld;
@@ -51,7 +59,10 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(bf16_t* __restrict__ log
       const u32x4_t z = {0u, 0u, 0u, 0u};
       for (int ch = threadIdx.x; ch < nchunk; ch += CE_THREADS) *(u32x4_t*)(lr + ch * 8) = z;
     }
-    if (threadIdx.x == 0) row_loss[row] = 0.f;
+    if (threadIdx.x == 0) {
+      row_loss[row] = 0.f;
+      if (REG && parts) parts[row] = parts[parts_stride + row] = 0.f;
+    }
     return;
   }
   // The row is VALU-heavy once it sits in registers (two exponentials per logit), so the per-element work is kept minimal: columns
@@ -61,6 +72,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(bf16_t* __restrict__ log
   constexpr float L2E = 1.4426950408889634f;
   u32x4_t v[CE_CHUNKS];
   float mx = -3.0e38f;
+  float xs = 0.f;  // REG: this thread's share of sum_{c<V} x_c
 #pragma unroll
   for (int c = 0; c < CE_CHUNKS; ++c) {
     const int ch = threadIdx.x + CE_THREADS * c;
@@ -70,9 +82,13 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(bf16_t* __restrict__ log
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int col = ch * 8 + 2 * i;
+          if (REG) xs += (col < V ? bf_lo(v[c][i]) : 0.f) + (col + 1 < V ? bf_hi(v[c][i]) : 0.f);
           if (col >= V) v[c][i] = (v[c][i] & 0xffff0000u) | 0x0000ff80u;
           if (col + 1 >= V) v[c][i] = (v[c][i] & 0x0000ffffu) | 0xff800000u;
         }
+      } else if (REG) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xs += bf_lo(v[c][i]) + bf_hi(v[c][i]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) mx = fmaxf(mx, fmaxf(bf_lo(v[c][i]), bf_hi(v[c][i])));
@@ -91,12 +107,28 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(bf16_t* __restrict__ log
     }
   }
   sum = block_reduce8(sum, red, false);
+  // (here, next to its only use: reduced before the exponential pass, the sixteen partial sums stay live across it and spill)
+  if (REG) xs = block_reduce8(xs, red, false);
   const float lse = mx + __logf(sum);
-  if (threadIdx.x == 0) row_loss[row] = lse - bf2f(lr[tgt]);
+  const float ev = REG ? eps / (float)V : 0.f;  // eps / V: V is the class count, not ld
+  if (threadIdx.x == 0) {
+    const float nll = lse - bf2f(lr[tgt]);
+    if (REG) {
+      // lse - (1 - eps) x_t - eps / V sum x + z lse^2, written as the plain loss plus the two corrections
+      row_loss[row] = nll + eps * bf2f(lr[tgt]) - ev * xs + zc * lse * lse;
+      if (parts) {
+        parts[row] = nll;
+        parts[parts_stride + row] = lse * lse;
+      }
+    } else {
+      row_loss[row] = nll;
+    }
+  }
   if (!write_grad) return;
   __syncthreads();  // lr[tgt] read above must precede the in-place overwrite
   const float g = gscale / (float)max(1, *n_valid_dev);
-  const float sg = g / sum;  // softmax * g = exp2(..) * sg
+  const float sg = REG ? g * (1.f + 2.f * zc * lse) / sum : g / sum;  // softmax * g (* (1 + 2 z lse)) = exp2(..) * sg
+  const float ge = g * ev, gt = REG ? g * (1.f - eps) : g;
   const int tch = (int)(tgt >> 3), tpos = (int)(tgt & 7);
 #pragma unroll
   for (int c = 0; c < CE_CHUNKS; ++c) {
@@ -108,10 +140,19 @@ __global__ __launch_bounds__(CE_THREADS) void ce_kernel(bf16_t* __restrict__ log
         e[2 * i] = __builtin_amdgcn_exp2f(fmaf(bf_lo(v[c][i]), L2E, nm2)) * sg;
         e[2 * i + 1] = __builtin_amdgcn_exp2f(fmaf(bf_hi(v[c][i]), L2E, nm2)) * sg;
       }
+      if (REG) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) e[i] -= ge;
+        if (ch * 8 + 8 > V) {  // the padded columns' gradient stays bit-zero
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+            if (ch * 8 + i >= V) e[i] = 0.f;
+        }
+      }
       if (ch == tch) {  // (one thread of the row)
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          if (i == tpos) e[i] -= g;
+          if (i == tpos) e[i] -= gt;
       }
       u32x4_t o;
 #pragma unroll
@@ -581,13 +622,24 @@ int launch_count_valid(const int64_t* targets, long rows, long ignore, int V, in
   return OASR_OK;
 }
 
+int check_ce_reg(const char* who, float label_smoothing, float z_loss) {
+  OASR_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "%s: label_smoothing = %g must be finite and inside [0, 1)", who, (double)label_smoothing);
+  OASR_REQUIRE(z_loss >= 0.f && z_loss <= 3.0e38f, "%s: z_loss = %g must be finite and >= 0", who, (double)z_loss);
+  return OASR_OK;
+}
+
 int launch_cross_entropy(bf16_t* logits, long ld, int V, const int64_t* targets, long rows, long ignore, float gscale,
-                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s) {
+                         const int32_t* n_valid_dev, float* row_loss, int write_grad, hipStream_t s, const CeReg& reg) {
   OASR_REQUIRE(logits && targets && n_valid_dev && row_loss, "cross_entropy: null pointer");
   OASR_REQUIRE(ld % 8 == 0 && V <= ld && ld <= CE_CHUNKS * CE_THREADS * 8, "cross_entropy: ld=%ld V=%d unsupported", ld, V);
+  OASR_REQUIRE(!reg.parts || reg.parts_stride >= rows, "cross_entropy: row_parts stride %ld below rows = %ld", reg.parts_stride, rows);
   if (rows <= 0) return OASR_OK;
-  hipLaunchKernelGGL(ce_kernel, dim3((unsigned)rows), dim3(CE_THREADS), 0, s, logits, ld, V, targets, ignore, gscale, n_valid_dev,
-                     row_loss, write_grad);
+  if (reg.on())
+    hipLaunchKernelGGL(ce_kernel<true>, dim3((unsigned)rows), dim3(CE_THREADS), 0, s, logits, ld, V, targets, ignore, gscale, n_valid_dev,
+                       row_loss, write_grad, reg.eps, reg.z, reg.parts, reg.parts_stride);
+  else
+    hipLaunchKernelGGL(ce_kernel<false>, dim3((unsigned)rows), dim3(CE_THREADS), 0, s, logits, ld, V, targets, ignore, gscale, n_valid_dev,
+                       row_loss, write_grad, 0.f, 0.f, (float*)nullptr, 0L);
   OASR_LAUNCH_CHECK();
   return OASR_OK;
 }

@@ -1045,7 +1045,8 @@ class OLMoASR(nn.Module):
                           accumulation_steps: int = 1, loss_out: Optional[Tensor] = None, accumulate_loss: bool = False,
                           return_logits: bool = False, segment_events=None, text_ctx: Optional[int] = None, span=None,
                           span_forward: Optional[bool] = None, mel_clip_max: Optional[Tensor] = None,
-                          audio_features: Optional[Tensor] = None, pred_out: Optional[Tensor] = None):
+                          audio_features: Optional[Tensor] = None, pred_out: Optional[Tensor] = None, label_smoothing: float = 0.0,
+                          z_loss: float = 0.0, loss_parts_out: Optional[Tensor] = None):
         """forward + F.cross_entropy(ignore_index=51864)/accumulation_steps + backward of (loss * loss_scale)
         (train_timestamps.py:1440-1454).  Gradients accumulate into ``flat_grads``.  Returns (loss tensor [1], logits|None).
 
@@ -1075,7 +1076,29 @@ class OLMoASR(nn.Module):
         teacher-forced predictions (``oasr_train_step``'s ``pred_out``): ``argmax_c logits[b, s, c]`` over the n_vocab + 1 columns (lowest index
         among equal maxima) at every position ``s`` below ``span[b]`` rounded up to 64 -- the rows every forward mode computes -- and -1
         elsewhere.  One kernel between the decoder forward and the loss; no fp32 logits exist.  Loss and gradients are unchanged.  Without
-        ``span``, or with ``return_logits`` / ``text_ctx``, it raises ``ValueError``."""
+        ``span``, or with ``return_logits`` / ``text_ctx``, it raises ``ValueError``.
+
+        ``label_smoothing`` (eps, in [0, 1)) and ``z_loss`` (z >= 0), both 0 by default = the objective above, launch for launch
+        (``oasr_train_step``'s fields of the same names).  For a valid row (target ``t`` in [0, V), ``t != 51864``) with logits ``x`` over the
+        V = n_vocab + 1 classes, ``lse = logsumexp(x)``, ``p = softmax(x)``::
+
+            row_loss  = lse - (1 - eps) * x_t - (eps / V) * sum_{c < V} x_c + z * lse^2
+            dlogits_c = g * [(1 + 2 * z * lse) * p_c - (1 - eps) * [c == t] - eps / V]       g = loss_scale / accumulation_steps / n_valid
+
+        i.e. ``F.cross_entropy(ignore_index=51864, label_smoothing=eps) + z * mean_valid(lse^2)`` (the PaLM / OLMo z-loss), divided by
+        ``accumulation_steps``; ignored rows give zero loss and zero gradient and are not counted.  The returned loss is this objective.  Both
+        are computed inside the cross-entropy kernel (one more reduction per row, no extra pass over the logits) and work with every form
+        of the step and both compute dtypes.  ``loss_parts_out``: a contiguous float32 [2] device tensor that receives
+        ``mean_valid(lse - x_t) / accumulation_steps`` (the plain NLL) and ``mean_valid(lse^2) / accumulation_steps``, overwritten or
+        (``accumulate_loss``) accumulated like the loss; the per-row scratch it needs is allocated here once per batch shape.  A value
+        outside those ranges, a non-finite one, or a ``loss_parts_out`` of another shape / dtype raises ``ValueError``."""
+        from . import ops
+        eps, zc = ops.check_loss_regularisers(label_smoothing, z_loss, "loss_and_backward")
+        if loss_parts_out is not None:
+            if not (isinstance(loss_parts_out, torch.Tensor) and loss_parts_out.dtype == torch.float32 and tuple(loss_parts_out.shape) == (2,)
+                    and loss_parts_out.is_contiguous()):
+                raise ValueError("loss_and_backward(loss_parts_out=...): loss_parts_out must be a contiguous float32 [2] device tensor")
+            N.require_gpu(loss_parts_out, "loss_parts_out")
         if pred_out is not None:
             if span is None or span is False or return_logits or text_ctx is not None:
                 raise ValueError("loss_and_backward(pred_out=...): the predictions come from the span step -- pass span=, and neither "
@@ -1140,11 +1163,17 @@ class OLMoASR(nn.Module):
             span_h = self.supervised_span(targets, text_len) if span is True else torch.as_tensor(span, dtype=torch.int32, device="cpu")
             span_h = span_h.to(torch.int32).contiguous()
             assert span_h.numel() == B and not span_h.is_cuda
+        parts_rows = None
+        if loss_parts_out is not None:  # f32 [2, B * S]: the caller-owned row scratch of oasr_train_step_args.loss_parts_rows
+            parts_rows = getattr(self, "_loss_parts_rows", None)
+            if parts_rows is None or parts_rows.numel() < 2 * B * S or parts_rows.device != dev:
+                parts_rows = self._loss_parts_rows = torch.empty(2 * B * S, device=dev, dtype=torch.float32)
         args = N.TrainStepArgs(mel=N.ptr(None if xa is not None else mel), xa=N.ptr(xa), tokens=N.ptr(tokens), targets=N.ptr(targets),
                                text_len=N.ptr(text_len), span_host=N.ptr(span_h), mel_clip_max=N.ptr(mel_clip_max), loss_out=N.ptr(loss_out),
                                logits_out=N.ptr(logits), pred_out=N.ptr(pred_out), seg_events=None if ev is None else C.cast(ev, C.c_void_p),
                                B=B, S=S, span_forward=int(span_forward is None or bool(span_forward)), accumulate_loss=int(accumulate_loss),
-                               loss_scale=float(loss_scale), inv_accum=1.0 / accumulation_steps)
+                               loss_scale=float(loss_scale), inv_accum=1.0 / accumulation_steps, label_smoothing=eps, z_loss=zc,
+                               loss_parts_out=N.ptr(loss_parts_out), loss_parts_rows=N.ptr(parts_rows))
         with torch.cuda.device(dev):
             N.check(N.lib().oasr_train_step(self._ctx, C.byref(args), N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_train_step")
         return loss_out, logits

@@ -1,6 +1,7 @@
 """Thin tensor-level wrappers over the unit operators of liboasr (used by the op-level parity tests and by the
 host-side mirrors).  bf16 tensors are torch.bfloat16; everything runs on the current HIP stream."""
 import ctypes as C
+import math
 
 import torch
 
@@ -459,15 +460,31 @@ def edit_counts_host(hyp, hyp_len, ref, ref_len):
     return out
 
 
-def cross_entropy_(logits, V, targets, ignore, gscale=1.0, write_grad=True):
-    """In place on bf16 logits [rows, ld]: returns (mean loss over non-ignored rows, row_loss); logits become the gradient."""
+def check_loss_regularisers(label_smoothing, z_loss, who):
+    """The refusals of the C side (``check_ce_reg``): label_smoothing in [0, 1), z_loss >= 0, both finite.  Returns them as floats."""
+    eps, z = float(label_smoothing), float(z_loss)
+    if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
+        raise ValueError(f"{who}: label_smoothing = {label_smoothing!r} must be finite and inside [0, 1)")
+    if not (math.isfinite(z) and z >= 0.0):
+        raise ValueError(f"{who}: z_loss = {z_loss!r} must be finite and >= 0")
+    return eps, z
+
+
+def cross_entropy_(logits, V, targets, ignore, gscale=1.0, write_grad=True, label_smoothing=0.0, z_loss=0.0, return_parts=False):
+    """In place on bf16 logits [rows, ld]: returns (mean loss over non-ignored rows, row_loss); logits become the gradient.
+    ``label_smoothing`` eps / ``z_loss`` z (``oasr_cross_entropy_ex``; both 0 and no parts: the plain kernel, as ``oasr_cross_entropy``): per valid row
+    ``lse - (1 - eps) x_t - eps / V sum_{c<V} x_c + z lse^2`` with the gradient ``g [(1 + 2 z lse) softmax - (1 - eps) onehot - eps / V]``.
+    ``return_parts``: a third result, f32 [2, rows] = per-row (lse - x_t, lse^2)."""
+    eps, z = check_loss_regularisers(label_smoothing, z_loss, "cross_entropy_")
     rows, ld = logits.shape
     nv = torch.zeros(1, device=logits.device, dtype=torch.int32)
     row_loss = torch.empty(rows, device=logits.device, dtype=torch.float32)
     loss = torch.zeros(1, device=logits.device, dtype=torch.float32)
-    N.check(N.lib().oasr_cross_entropy(N.ptr(logits), logits.stride(0), V, N.ptr(targets), rows, ignore, gscale, N.ptr(nv),
-                                       N.ptr(row_loss), N.ptr(loss), int(write_grad), N.stream_ptr()), "cross_entropy")
-    return loss, row_loss
+    parts = torch.empty(2, rows, device=logits.device, dtype=torch.float32) if return_parts else None
+    N.check(N.lib().oasr_cross_entropy_ex(N.ptr(logits), logits.stride(0), V, N.ptr(targets), rows, ignore, gscale, N.ptr(nv),
+                                          N.ptr(row_loss), N.ptr(loss), int(write_grad), eps, z, N.ptr(parts), N.stream_ptr()),
+            "cross_entropy")
+    return (loss, row_loss, parts) if return_parts else (loss, row_loss)
 
 
 def cast_bf16(x):

@@ -71,7 +71,12 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     # train_dels / train_ins; evaluate() scores with the same kernel.  ONE difference: a prediction without <|endoftext|> inside the computed
     # prefix ends at span[b] rounded up to 64 instead of at position 448 -- the host path also scores the argmax of padded positions, which
     # the loss ignores (and which the span step's forward does not compute).
-    train_error_counts="host")
+    train_error_counts="host",
+    # Regularisers of the fused step's objective (loss_and_backward(label_smoothing=, z_loss=); csrc/loss.hip): label smoothing eps in [0, 1)
+    # -- F.cross_entropy(label_smoothing=eps), the usual companion of SpecAugment -- and the z-loss coefficient z >= 0 -- + z * mean(logsumexp^2),
+    # PaLM's auxiliary term.  Both 0 = the reference's objective, step and log records unchanged.  With either set, train_loss is the regularised
+    # objective and a logging step's record gains train_nll (the plain cross-entropy) and train_lse_sq (mean logsumexp^2), read with the loss.
+    label_smoothing=0.0, z_loss=0.0)
 ERROR_COUNTS = ("host", "device")
 SPEC_OVERRIDES = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_time_ratio", "spec_fill")
 SPEC_PRESETS = ("off", "LD", "LB")
@@ -159,6 +164,12 @@ def parse_args(argv=None):
         raise SystemExit(f"--precision must be bfloat16 | float32 | float16, got {args.precision!r}")
     if not isinstance(args.lora_rank, int) or args.lora_rank < 0:
         raise SystemExit(f"--lora_rank must be a non-negative integer (0 = no adapters), got {args.lora_rank!r}")
+    for flag, ok, want in (("label_smoothing", lambda v: 0.0 <= v < 1.0, "a number in [0, 1) (0 = off)"),
+                           ("z_loss", lambda v: v >= 0.0, "a non-negative number (0 = off)")):
+        v = args[flag]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not ok(v):
+            raise SystemExit(f"--{flag} must be {want}, got {v!r}")
+        args[flag] = float(v)
     if isinstance(args.lora_targets, str):
         args.lora_targets = tuple(t.strip() for t in args.lora_targets.split(",") if t.strip())
     args.lora_targets = tuple(args.lora_targets)
@@ -446,7 +457,11 @@ def main(argv=None):
     scaler = GradScalerState()
     accum = accumulation_steps(args.eff_batch_size, world_size, args.train_batch_size)
     mine = ddp.shard_indices(args.n_synthetic, rank, world_size)
-    loss_buf = torch.zeros(1, device=dev)
+    # label smoothing / z-loss: the objective's two parts sit behind the loss in ONE buffer, so a logging step still reads the device once
+    regularised = args.label_smoothing > 0.0 or args.z_loss > 0.0
+    loss_all = torch.zeros(3 if regularised else 1, device=dev)
+    loss_buf = loss_all[:1]
+    step_reg = dict(label_smoothing=args.label_smoothing, z_loss=args.z_loss, loss_parts_out=loss_all[1:]) if regularised else {}
     global_step, local_step, cursor, epoch, optimizer_steps = 0, 0, 0, 0, 0
     run_id = get_run_id(args, rank, world_size)
     if args.resume or args.ckpt_file_name:
@@ -487,6 +502,8 @@ def main(argv=None):
         print(json.dumps({"event": "spec_augment", "policy": args.spec_augment, "freq_masks": policy.freq_masks, "freq_width": policy.freq_width,
                           "time_masks": policy.time_masks, "time_width": policy.time_width, "time_ratio": policy.time_ratio,
                           "fill": policy.fill if math.isfinite(policy.fill) else str(policy.fill), "seed": spec_seed}), flush=True)
+    if regularised and rank == 0:
+        print(json.dumps({"event": "loss_regularisers", "label_smoothing": args.label_smoothing, "z_loss": args.z_loss}), flush=True)
     device_counts = args.train_error_counts == "device"
     if device_counts:
         from olmoasr_amd import metrics
@@ -520,7 +537,7 @@ def main(argv=None):
                                               segment_events=reducer.segment_events() if (reducer and last) else None,
                                               span=loader.last_span if use_span else None, mel_clip_max=clip_max,
                                               span_forward=use_span and bool(args.span_forward),
-                                              **({"pred_out": pred_buf[:ti.shape[0]]} if want_pred else {}))
+                                              **({"pred_out": pred_buf[:ti.shape[0]]} if want_pred else {}), **step_reg)
             if want_pred:
                 if i == 0:
                     counter.reset()
@@ -552,19 +569,21 @@ def main(argv=None):
         if global_step % args.train_log_freq == 0 or global_step == 1:
             scored = device_counts and global_step % args.train_log_freq == 0  # (global_step was advanced: this is log_now of the step just run)
             if scored:  # the counts ride with the loss: one all-reduce, one read (float64 holds both exactly enough: counts < 2^53)
-                t = torch.cat([loss_buf.double(), counter.total.double()])
+                t = torch.cat([loss_all.double(), counter.total.double()])
             else:
-                t = loss_buf.clone()
+                t = loss_all.clone()
             if world_size > 1:
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
-            if scored:
-                t, *sdih = t.cpu().tolist()  # the step's one read of the device: loss and counts together
-                sdih = [int(v) for v in sdih]
+            if scored or regularised:
+                t, *rest = t.cpu().tolist()  # the step's one read of the device: loss, its parts and the counts together
+                parts, sdih = rest[:loss_all.numel() - 1], [int(v) for v in rest[loss_all.numel() - 1:]]
             if rank == 0:
                 rec = {"global_step": global_step, "train_loss": float(t) / world_size, "lr": lr, "loss_scale": scaler.scale,
                        "time_per_step": round(time_per_step, 4), "audio_min_per_GPU_second": round(throughput, 3),
                        "audio_sec_per_sec_node": round(throughput * 60 * world_size, 1), "found_inf": found_inf,
                        "spec_masked_cells": spec_cells}
+                if regularised:
+                    rec.update(train_nll=parts[0] / world_size, train_lse_sq=parts[1] / world_size)
                 if preds:
                     rec["train_token_error_rate"] = round(token_error_rate(preds, tgts), 4)
                 if scored:
