@@ -16,8 +16,10 @@ extern "C" {
  * summed milliseconds, summed algorithmic flops (2*M*N*K, conv windows at their real width) and launch count; by_symbol
  * receives the same sums keyed by the kernel symbol rocprofv3 prints, so the two can be compared line by line. */
 int oasr_profile_gemm(int enable);
-/* experiments on the 256x256 kernel.  v < 0: defaults.  bits 0-3: schedule variant (8 = per-layout default); bits 4-5: 1 = plain
- * launches, 2 = persistent launches (next tile's prologue ahead of the epilogue); bit 6 / 7: non-temporal epilogue stores / side loads */
+/* tests / experiments on the 256x256 ping-pong kernel.  v < 0: defaults.  bits 0-3: K-tile schedule -- 2 = four phases of 8 MFMAs, 7 = two
+ * sections of 16 MFMAs, 8 = the per-layout default (7; 2 for the dgrad with fused column sums); any other value returns OASR_EINVAL and changes
+ * nothing.  bits 4-5: 1 = plain launches, 2 = persistent launches (next tile's prologue ahead of the epilogue); bit 6 / 7: non-temporal epilogue
+ * stores / side loads */
 int oasr_gemm_set_variant(int v);
 /* tests / A-B of the KV-cached step engine: -1 = default (ONE sequence on the bf16 engine: the chip-wide one-launch engine of
  * csrc/decode_wide.hip; 2-4: LayerNorm folded into the projections; more: separate kernels), 0 = separate LayerNorm kernels, 1 = LayerNorm

@@ -81,10 +81,9 @@ extern "C" int oasr_profile_gemm(int enable) {
   gemm_profile_enable(enable);
   return OASR_OK;
 }
-extern "C" int oasr_gemm_set_variant(int dma_in_mma) {
+extern "C" int oasr_gemm_set_variant(int v) {
   OASR_HOOK_GATE("oasr_gemm_set_variant");
-  gemm_set_variant(dma_in_mma);
-  return OASR_OK;
+  return gemm_set_variant(v);
 }
 extern "C" int oasr_gemm_set_stagger(int sleeps, int phases) {
   OASR_HOOK_GATE("oasr_gemm_set_stagger");

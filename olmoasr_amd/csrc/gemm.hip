@@ -60,12 +60,18 @@ struct GemmProfile {
   }
 };
 GemmProfile g_prof;
-bool g_force_general = false;
-int g_stagger = 0, g_stagger_phases = 2;  // experiment hook (oasr_gemm_set_stagger)
-int g_pp_dma_in_mma = -1;                 // ping-pong kernel variant (oasr_gemm_set_variant): -1 = default
-int g_pp_persistent = -1;                 // ping-pong kernel launched persistent: -1 = default rule, 0 / 1 forced
-int g_epi_flags = -1;                     // epilogue memory policy (GemmArgs::epi_flags): -1 = default
-int g_fast_geometry = 0;  // 0 = heuristic, 1 = force 256x128 (4 waves), 2 = force 256x256 (8 waves, 2 stages)  // tests: run the register-staged general kernel even where the fast path applies
+
+// Process-wide kernel selection set through include/oasr_testing.h (tests and A/B scripts); the defaults are what production runs.
+enum class ForcedPath { Auto = 0, General, Fast256x128, Fast256x256Stage2, PingPong };  // the codes of oasr_gemm_force_general
+struct GemmHooks {
+  ForcedPath path = ForcedPath::Auto;   // oasr_gemm_force_general
+  int stagger = 0, stagger_phases = 2;  // oasr_gemm_set_stagger: 0 = the automatic rule, > 0 = forced on every call, < 0 = off everywhere
+  // oasr_gemm_set_variant; -1 = default everywhere
+  int pp_schedule = -1;    // ping-pong K-tile schedule (2 or 7) instead of the per-layout choice
+  int pp_persistent = -1;  // ping-pong kernel launched persistent: 0 never, 1 whenever possible
+  int epi_flags = -1;      // epilogue memory policy (GemmArgs::epi_flags) instead of the caller's
+};
+GemmHooks g_hooks;
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = 128 * 64 * 2;
@@ -840,19 +846,31 @@ __global__ __launch_bounds__(128 * NWN, (NWN == 2 && !SWAP) ? 3 : 2) void oasr_g
 // four 16 KiB half-tile images (A rows 0-127 / 128-255, B columns 0-127 / 128-255; each image is laid out exactly like
 // a 128-row operand tile of the kernel above, so the fragment readers are shared).
 //
-// A K-tile is consumed in four phases, one 64 x 32 output quadrant (8 MFMAs) each:
+// The waves of the upper M half run one barrier behind the lower half, so on every SIMD one wave is in its MFMA section
+// while the other issues LDS reads and DMA: the matrix pipe never waits for a barrier-drained staging step (the
+// 1-workgroup-per-CU failure mode of the kernel above).  The DMA queue is never drained inside the loop: one counted
+// wait per K-tile leaves the newest pieces (tile t+2's B) in flight across the barriers.  Every MFMA section is pinned
+// between its two barriers by empty asm statements on its accumulators: without them hipcc sinks most of a section's
+// MFMAs below the closing s_barrier (the asm-volatile barrier orders memory, not register-only instructions; round 1's
+// ISA had 1 + 7 MFMAs around the first barrier pair instead of 8 inside it).
+//
+// Two schedules of a K-tile exist (VAR, part of the kernel symbol):
+//   VAR = 7, two sections of 16 MFMAs (4 barriers per K-tile), four of a wave's eight DMA pieces issued between the MFMAs.
+//            Every layout without the fused column sum.  Against the four-phase schedule: +8 % on the NT forward shapes
+//            at K = 1024, +16..19 % on the NN dgrads whose B fragments come through ds_read_b64_tr_b16
+//            (profiles/r02_gemm_variants_ab.txt, r02_step_gemm_variants_same_box.txt).  NT at K = 4096 is 2 % faster on
+//            four phases; not worth a shape-dependent choice between the two.
+//   VAR = 2, four phases of 8 MFMAs (8 barriers per K-tile), one 64 x 32 output quadrant each, all DMA pieces issued in
+//            the fragment-read sections.  The fused-colsum dgrad (CSUM), for which it won the whole-step A/B:
 //     phase  LDS -> VGPR          MFMA        direct-to-LDS staging issued (2 x 1 KiB pieces per wave)
 //       0    B0 (4), A0 (8)       A0 x B0     A rows   0-127 of tile t+1 -> other buffer
 //       1    B1 (4)               A0 x B1     A rows 128-255 of tile t+1 -> other buffer
 //       2    A1 (8)               A1 x B1     B cols   0-127 of tile t+2 -> THIS buffer (its B images are dead)
 //       3    -                    A1 x B0     B cols 128-255 of tile t+2 -> THIS buffer;  s_waitcnt vmcnt(4)
-// Every phase is  { ds_reads; staging; s_barrier; MFMAs; s_barrier }.  The waves of the upper M half run one barrier
-// behind the lower half, so on every SIMD one wave is in its MFMA section while the other issues LDS reads and DMA:
-// the matrix pipe never waits for a barrier-drained staging step (the 1-workgroup-per-CU failure mode of the
-// kernel above).  The DMA queue is never drained inside the loop: the single counted wait per K-tile (phase 3) leaves
-// the two newest half-tiles (tile t+2's B) in flight across the barriers.
-// Hazards (DMA writes are ordered with LDS reads only by the issuing wave's vmcnt wait followed by a barrier):
-//   RAW  tile t+1 is complete after phase 3's wait of tile t + the barriers up to the first read in phase 0 of t+1
+//            Every phase is  { ds_reads; staging; s_barrier; MFMAs; s_barrier }.
+// Hazards (DMA writes are ordered with LDS reads only by the issuing wave's vmcnt wait followed by a barrier; "phase"
+// reads "section" in the two-section schedule, whose staging plan is written above its loop):
+//   RAW  tile t+1 is complete after the counted wait of tile t + the barriers up to the first read in phase 0 of t+1
 //        (two barrier events later even for the trailing wave group);
 //   WAR  an image is re-staged >= 2 phases after its last ds_read, or in the next phase when the reading phase
 //        retired its reads (lgkmcnt(0)) before its first barrier (B1 in phase 1 -> B restaged in phase 2).
@@ -860,12 +878,8 @@ __global__ __launch_bounds__(128 * NWN, (NWN == 2 && !SWAP) ? 3 : 2) void oasr_g
 
 template <bool TA, bool TB, bool SWAP, bool CSUM, int VAR>
 __global__ __launch_bounds__(512, 2) void oasr_gemm_pp_kernel(GemmArgs p) {
-  // VAR bit 0: the direct-to-LDS pieces are issued between the MFMAs (else in the fragment-read section);
-  //     bit 1: every MFMA section is pinned between its two barriers.  Without the pin hipcc sinks most of a section's MFMAs
-  //            below the closing s_barrier (the asm-volatile barrier orders memory, not register-only instructions, and the
-  //            conditional DMA issue splits the basic block the sched_barrier fences act in): the ISA of round 1's kernel has
-  //            1 + 7 MFMAs around the first barrier pair instead of 8 inside it.
-  constexpr bool DMA_IN_MMA = (VAR & 1) != 0, PIN = (VAR & 2) != 0;
+  static_assert(VAR == 2 || VAR == 7, "ping-pong schedules: 2 = four phases, 7 = two sections");
+  constexpr bool TWO_SECTION = VAR == 7;
   constexpr int HALF = 128 * 64 * 2, BUF = 4 * HALF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -966,7 +980,7 @@ for (;;) {  // output tiles of this workgroup (one iteration unless the launch i
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   }
   OASR_PP_BARRIER();
-  if (wm == 1 && !(VAR & 8)) OASR_PP_BARRIER();  // the upper half trails by one barrier from here on (VAR bit 3: lockstep experiment)
+  if (wm == 1) OASR_PP_BARRIER();  // the upper half trails by one barrier from here on
 
   const int aoff = wm * HALF, boff = (2 + (wn >> 1)) * HALF, bsub = (wn & 1) * 64;
   bf16x8_t fa[2][4], fb0[4], fb1[4];
@@ -977,47 +991,36 @@ for (;;) {  // output tiles of this workgroup (one iteration unless the launch i
     else                                                                                                     \
       acc[MT0 + T][NT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[T][KS], FB[KS], acc[MT0 + T][NT], 0, 0, 0); \
   } while (0)
-  // 8 MFMAs at priority 1.  DMA: the phase's two direct-to-LDS pieces are issued from INSIDE the section (after the 2nd and
-  // the 4th MFMA) when OASR_PP_DMA_IN_MMA: a piece costs ~60 cycles of issue among bare MFMAs, which the 256 cycles of
-  // matrix-pipe time cover, against 100-185 cycles in a read section already carrying 8-12 ds_read_b128
-  // (MI355X_MICROARCH.md, "LDS-DMA piece issue cost") -- there it made the read section longer than the partner's MFMAs.
-#define OASR_PP_MMA(MT0, NT, FB, DO_STAGE, IMG, T, BUFP)                                                     \
+  // one phase of the four-phase schedule: 8 MFMAs at priority 1, pinned between the barriers around them
+#define OASR_PP_MMA(MT0, NT, FB)                                                                             \
   do {                                                                                                       \
     __builtin_amdgcn_sched_barrier(0);                                                                       \
     __builtin_amdgcn_s_setprio(1);                                                                           \
-    if (PIN) asm volatile("" : "+v"(acc[MT0][NT]), "+v"(acc[MT0 + 1][NT]));                                  \
+    asm volatile("" : "+v"(acc[MT0][NT]), "+v"(acc[MT0 + 1][NT]));                                           \
     OASR_PP_MFMA1(MT0, NT, FB, 0, 0);                                                                        \
     OASR_PP_MFMA1(MT0, NT, FB, 0, 1);                                                                        \
-    if (DMA_IN_MMA && (DO_STAGE)) {                                                                          \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-      const __amdgpu_buffer_rsrc_t rs_ = make_rsrc((IMG) < 2 ? baseA + (T) * stepA : baseB + (T) * stepB);   \
-      glds16(rs_, (BUFP) + (IMG) * HALF + wave * 1024, off[IMG][0]);                                         \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-    }                                                                                                        \
     OASR_PP_MFMA1(MT0, NT, FB, 1, 0);                                                                        \
     OASR_PP_MFMA1(MT0, NT, FB, 1, 1);                                                                        \
-    if (DMA_IN_MMA && (DO_STAGE)) {                                                                          \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-      const __amdgpu_buffer_rsrc_t rs_ = make_rsrc((IMG) < 2 ? baseA + (T) * stepA : baseB + (T) * stepB);   \
-      glds16(rs_, (BUFP) + (IMG) * HALF + wave * 1024 + 8192, off[IMG][1]);                                  \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-    }                                                                                                        \
     OASR_PP_MFMA1(MT0, NT, FB, 2, 0);                                                                        \
     OASR_PP_MFMA1(MT0, NT, FB, 2, 1);                                                                        \
     OASR_PP_MFMA1(MT0, NT, FB, 3, 0);                                                                        \
     OASR_PP_MFMA1(MT0, NT, FB, 3, 1);                                                                        \
-    if (PIN) asm volatile("" : "+v"(acc[MT0][NT]), "+v"(acc[MT0 + 1][NT]));                                  \
+    asm volatile("" : "+v"(acc[MT0][NT]), "+v"(acc[MT0 + 1][NT]));                                           \
     __builtin_amdgcn_s_setprio(0);                                                                           \
     __builtin_amdgcn_sched_barrier(0);                                                                       \
   } while (0)
 
-  if (VAR & 4) {
+  if (TWO_SECTION) {
     // Two sections of 16 MFMAs per K-tile (4 barriers instead of 8): S0 = rows 0-63 of this wave's 128 x 64 block against
     // both column halves, S1 = rows 64-127.  Staging (hazards as in the header, with "phase" = section):
     //   S0 read : A image 0 of tile t+1 -> oth (its last reader, the leading group, is past its own S1 MFMAs);
     //             lgkmcnt(0) BEFORE the barrier, so the B images of `cur` are dead once both groups passed it
     //   S0 MFMA : A image 1 of tile t+1 -> oth, between the MFMAs (the trailing group finished reading it one barrier ago)
-    //   S1 read : B images of tile t+2 -> cur; vmcnt(4): everything of tile t+1 has landed, only those 4 pieces are in flight
+    //   S1 read : B image 0 of tile t+2 -> cur; vmcnt(2): everything of tile t+1 has landed, only those 2 pieces are in flight
+    //   S1 MFMA : B image 1 of tile t+2 -> cur, between the MFMAs
+    // A piece issued between bare MFMAs costs ~60 cycles of issue, which the section's matrix-pipe time covers, against
+    // 100-185 cycles in a read section already carrying 8-12 ds_read_b128 (MI355X_MICROARCH.md, "LDS-DMA piece issue cost")
+    // -- there it made the read section longer than the partner's MFMAs.
     for (int t = 0; t < nt; ++t) {
       char* cur = smem + ((t & 1) ^ parity) * BUF;
       char* oth = smem + ((t & 1) ^ parity ^ 1) * BUF;
@@ -1075,12 +1078,7 @@ for (;;) {  // output tiles of this workgroup (one iteration unless the launch i
         for (int i = 0; i < 2; ++i) fa[i][ks] = fast_frag<TA, 256>(cur + aoff, 64 + i * 32, ks, lane);
       if (next2) {
         OASR_PP_STAGE(2, t + 2, cur);
-        if (DMA_IN_MMA) {  // B image 1 of tile t+2 goes out between this section's MFMAs: only B image 0's 2 pieces are newer
-          asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        } else {
-          OASR_PP_STAGE(3, t + 2, cur);
-          asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        }
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // B image 1 goes out between this section's MFMAs: only these 2 pieces are newer
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
@@ -1094,7 +1092,7 @@ for (;;) {  // output tiles of this workgroup (one iteration unless the launch i
         OASR_PP_MFMA1(2, 0, fb0, ks, 1);
         OASR_PP_MFMA1(2, 1, fb1, ks, 0);
         OASR_PP_MFMA1(2, 1, fb1, ks, 1);
-        if (DMA_IN_MMA && next2 && ks < 2) {
+        if (next2 && ks < 2) {
           __builtin_amdgcn_sched_barrier(0);
           const __amdgpu_buffer_rsrc_t rs_ = make_rsrc(baseB + (t + 2) * stepB);
           glds16(rs_, cur + 3 * HALF + wave * 1024 + ks * 8192, off[3][ks]);
@@ -1118,43 +1116,39 @@ for (;;) {  // output tiles of this workgroup (one iteration unless the launch i
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int i = 0; i < 2; ++i) fa[i][ks] = fast_frag<TA, 256>(cur + aoff, i * 32, ks, lane);
-    if (!DMA_IN_MMA && next1) OASR_PP_STAGE(0, t + 1, oth);
+    if (next1) OASR_PP_STAGE(0, t + 1, oth);
     OASR_PP_BARRIER();
-    OASR_PP_MMA(0, 0, fb0, next1, 0, t + 1, oth);
+    OASR_PP_MMA(0, 0, fb0);
     OASR_PP_BARRIER();
     // ---- phase 1
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) fb1[ks] = fast_frag<TB, 256>(cur + boff, bsub + 32, ks, lane);
-    if (!DMA_IN_MMA && next1) OASR_PP_STAGE(1, t + 1, oth);
+    if (next1) OASR_PP_STAGE(1, t + 1, oth);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // B images of `cur` are dead before this phase's barrier
     OASR_PP_BARRIER();
-    OASR_PP_MMA(0, 1, fb1, next1, 1, t + 1, oth);
+    OASR_PP_MMA(0, 1, fb1);
     OASR_PP_BARRIER();
     // ---- phase 2
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int i = 0; i < 2; ++i) fa[i][ks] = fast_frag<TA, 256>(cur + aoff, 64 + i * 32, ks, lane);
-    if (!DMA_IN_MMA && next2) OASR_PP_STAGE(2, t + 2, cur);
+    if (next2) OASR_PP_STAGE(2, t + 2, cur);
     OASR_PP_BARRIER();
-    OASR_PP_MMA(2, 1, fb1, next2, 2, t + 2, cur);
+    OASR_PP_MMA(2, 1, fb1);
     OASR_PP_BARRIER();
     // ---- phase 3: everything of tile t+1 (this wave's pieces) must have landed before the barrier that ends the tile
-    if (DMA_IN_MMA) {
-      // outstanding, oldest first: [B0 B1](t+1) [A0 A1](t+1) B0(t+2) -> all but the last two pieces
-      if (next2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (next2) {
+    if (next2) {
       OASR_PP_STAGE(3, t + 2, cur);
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // everything but tile t+2's B has landed (this wave's pieces)
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     OASR_PP_BARRIER();
-    OASR_PP_MMA(2, 0, fb0, next2, 3, t + 2, cur);
+    OASR_PP_MMA(2, 0, fb0);
     OASR_PP_BARRIER();
   }
-  if (wm == 0 && !(VAR & 8)) OASR_PP_BARRIER();  // re-join: the trailing half has finished its LDS reads after this
+  if (wm == 0) OASR_PP_BARRIER();  // re-join: the trailing half has finished its LDS reads after this
   // Persistent launch: the NEXT output tile's prologue is issued before this tile's epilogue, into the buffer the epilogue does
   // not stage through (K-tile 0 -> buffer parity ^ 1, K-tile 1's B images -> the upper half of buffer `parity`; the epilogue's
   // wave-private staging tiles live in the lower half of buffer `parity`, the bias rows behind both buffers).  The operand fetch
@@ -1261,6 +1255,30 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p) {
 }
 
 
+// One kernel launch on `stream`.  With profiling on (gemm_profile_enable) the launch's record is pushed and the launch runs between
+// a pair of pooled events; with it off this makes no HIP call beyond the launch and its check.
+template <class F>
+int timed_launch(const GemmArgs& a, double flops, const char* symbol, bool persistent, hipStream_t stream, F&& launch) {
+  hipEvent_t e1 = nullptr;
+  if (g_prof.on) {
+    const size_t idx = g_prof.recs.size();
+    while (g_prof.events.size() < 2 * (idx + 1)) {
+      hipEvent_t e;
+      OASR_CHECK_HIP(hipEventCreate(&e));
+      g_prof.events.push_back(e);
+    }
+    e1 = g_prof.events[2 * idx + 1];
+    g_prof.push(gemm_rec(a, flops, symbol, persistent));
+    OASR_CHECK_HIP(hipEventRecord(g_prof.events[2 * idx], stream));
+  }
+  launch();
+  OASR_LAUNCH_CHECK();
+  if (e1) OASR_CHECK_HIP(hipEventRecord(e1, stream));
+  return OASR_OK;
+}
+double gemm_flops(const GemmArgs& a) { return 2.0 * (double)a.M * (double)a.N * (double)a.K; }
+const char* tf(bool b) { return b ? "true" : "false"; }  // template arguments in a kernel symbol, as rocprofv3 prints them
+
 template <bool TA, bool TB, int FBN, int NWN, int NSTAGE, bool SWAP, bool CSUM = false>
 int launch_fast_cfg(const GemmArgs& a, hipStream_t stream) {
   static LdsAttrOnce attr;
@@ -1269,33 +1287,18 @@ int launch_fast_cfg(const GemmArgs& a, hipStream_t stream) {
   const int tiles = cdiv(a.M, FBM) * cdiv(a.N, FBN);
   dim3 grid(tiles, a.split_k);
   if (!SWAP && (a.split_k & 7) == 0) grid = dim3(tiles * a.split_k, 1);  // split index tied to the XCD (see kernel)
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof.on) {
-    const size_t idx = g_prof.recs.size();
-    while (g_prof.events.size() < 2 * (idx + 1)) {
-      hipEvent_t e;
-      OASR_CHECK_HIP(hipEventCreate(&e));
-      g_prof.events.push_back(e);
-    }
-    e0 = g_prof.events[2 * idx];
-    e1 = g_prof.events[2 * idx + 1];
-    auto tf = [](bool b) { return b ? "true" : "false"; };
-    static const std::string name = std::string("oasr_gemm_fast_kernel<") + tf(TA) + ", " + tf(TB) + ", " + std::to_string(FBN) + ", " +
-                                    std::to_string(NWN) + ", " + std::to_string(NSTAGE) + ", " + tf(SWAP) + ", " + tf(CSUM) + ">";
-    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * (double)a.N * (double)a.K, name.c_str()));
-    OASR_CHECK_HIP(hipEventRecord(e0, stream));
-  }
-  hipLaunchKernelGGL((oasr_gemm_fast_kernel<TA, TB, FBN, NWN, NSTAGE, SWAP, CSUM>), grid, dim3(128 * NWN), lds, stream, a);
-  OASR_LAUNCH_CHECK();
-  if (e1) OASR_CHECK_HIP(hipEventRecord(e1, stream));
-  return OASR_OK;
+  static const std::string name = std::string("oasr_gemm_fast_kernel<") + tf(TA) + ", " + tf(TB) + ", " + std::to_string(FBN) + ", " +
+                                  std::to_string(NWN) + ", " + std::to_string(NSTAGE) + ", " + tf(SWAP) + ", " + tf(CSUM) + ">";
+  return timed_launch(a, gemm_flops(a), name.c_str(), false, stream, [&] {
+    hipLaunchKernelGGL((oasr_gemm_fast_kernel<TA, TB, FBN, NWN, NSTAGE, SWAP, CSUM>), grid, dim3(128 * NWN), lds, stream, a);
+  });
 }
 
-template <bool TA, bool TB, bool SWAP, bool CSUM, int DMA>
+template <bool TA, bool TB, bool SWAP, bool CSUM, int VAR>
 int launch_pp_variant(const GemmArgs& a, hipStream_t stream) {
   static LdsAttrOnce attr;
   const int lds = 2 * 4 * 128 * 64 * 2 + 8 * 256;  // two K-tile buffers + the epilogue's per-wave bias rows
-  { const int rc_ = ensure_dynamic_lds(attr, (const void*)oasr_gemm_pp_kernel<TA, TB, SWAP, CSUM, DMA>, lds); if (rc_) return rc_; }
+  { const int rc_ = ensure_dynamic_lds(attr, (const void*)oasr_gemm_pp_kernel<TA, TB, SWAP, CSUM, VAR>, lds); if (rc_) return rc_; }
   const int tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
   dim3 grid(tiles, a.split_k);
   if (!SWAP && (a.split_k & 7) == 0) grid = dim3(tiles * a.split_k, 1);
@@ -1303,7 +1306,8 @@ int launch_pp_variant(const GemmArgs& a, hipStream_t stream) {
   // opt-in (OASR_PP_PERSISTENT=1 or oasr_gemm_set_variant() bits 4-5).  Measured level with plain launches on every layer shape
   // (profiles/r02_gemm_tile_cost_model.txt): the chip is at its power budget in these kernels (effective clock 1.53 GHz of 2.4,
   // profiles/r02_gemm_effective_clock.txt), so cycles saved between tiles come back as a lower clock, and plain launches keep the
-  // hardware's dynamic tile dispatch (robust when RCCL kernels hold CUs).
+  // hardware's dynamic tile dispatch (robust when RCCL kernels hold CUs).  Launching only the GELU-epilogue shapes persistent was
+  // level too (profiles/r05_gelu_gemm_persistent_ab.txt).
   static const int n_cu = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
@@ -1316,62 +1320,20 @@ int launch_pp_variant(const GemmArgs& a, hipStream_t stream) {
   }();
   GemmArgs pa = a;
   pa.vgrid = (int)grid.x;
-  // (experiment: OASR_PP_PERSIST_GELU=1 launches only the GELU-epilogue shapes persistent -- mlp.0 forward and the dgrad through GELU',
-  // whose 12.7 k-cycle epilogues are the largest fixed cost per tile, profiles/r03_gemm_tile_stamps.txt)
-  static const int env_persist_gelu = [] {
-    const char* e = oasr_experiment_env("OASR_PP_PERSIST_GELU");
-    return e ? atoi(e) : 0;
-  }();
-  int want = g_pp_persistent >= 0 ? g_pp_persistent : env_persist;
-  if (want < 0 && env_persist_gelu && (a.act != 0 || a.dgelu_u)) want = 1;
-  const bool can_persist = grid.y == 1 && (int)grid.x > n_cu && ((a.K / BK) % a.split_k) == 0;
-  if (can_persist && want == 1) grid = dim3(n_cu, 1);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof.on) {
-    const size_t idx = g_prof.recs.size();
-    while (g_prof.events.size() < 2 * (idx + 1)) {
-      hipEvent_t e;
-      OASR_CHECK_HIP(hipEventCreate(&e));
-      g_prof.events.push_back(e);
-    }
-    e0 = g_prof.events[2 * idx];
-    e1 = g_prof.events[2 * idx + 1];
-    auto tf = [](bool b) { return b ? "true" : "false"; };
-    static const std::string name = std::string("oasr_gemm_pp_kernel<") + tf(TA) + ", " + tf(TB) + ", " + tf(SWAP) + ", " + tf(CSUM) +
-                                    ", " + std::to_string(DMA) + ">";
-    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * (double)a.N * (double)a.K, name.c_str(), can_persist && want == 1));
-    OASR_CHECK_HIP(hipEventRecord(e0, stream));
-  }
-  hipLaunchKernelGGL((oasr_gemm_pp_kernel<TA, TB, SWAP, CSUM, DMA>), grid, dim3(512), lds, stream, pa);
-  OASR_LAUNCH_CHECK();
-  if (e1) OASR_CHECK_HIP(hipEventRecord(e1, stream));
-  return OASR_OK;
+  const int want = g_hooks.pp_persistent >= 0 ? g_hooks.pp_persistent : env_persist;
+  const bool persistent = want == 1 && grid.y == 1 && (int)grid.x > n_cu && ((a.K / BK) % a.split_k) == 0;
+  if (persistent) grid = dim3(n_cu, 1);
+  static const std::string name = std::string("oasr_gemm_pp_kernel<") + tf(TA) + ", " + tf(TB) + ", " + tf(SWAP) + ", " + tf(CSUM) + ", " +
+                                  std::to_string(VAR) + ">";
+  return timed_launch(a, gemm_flops(a), name.c_str(), persistent, stream,
+                      [&] { hipLaunchKernelGGL((oasr_gemm_pp_kernel<TA, TB, SWAP, CSUM, VAR>), grid, dim3(512), lds, stream, pa); });
 }
+// Which schedule a layout gets, and why, is written above the kernel.
 template <bool TA, bool TB, bool SWAP, bool CSUM = false>
 int launch_pp_cfg(const GemmArgs& a, hipStream_t stream) {
-  // Where the direct-to-LDS pieces are issued: between the MFMAs (+3..5 % on the NT forward shapes at M = 192000,
-  // profiles/r02_gemm_variants_ab.txt) or in the fragment-read section (level or better when an operand is read
-  // through ds_read_b64_tr_b16: those read sections are longer and hide the issue).  g_pp_dma_in_mma: -1 = this rule,
-  // 0 / 1 = forced (scripts/gemm_stagger_ab.py variant).
-  // Default (profiles/r02_gemm_variants_ab.txt, r02_step_gemm_variants_same_box.txt): two pinned 16-MFMA sections per K-tile with
-  // the DMA pieces spread over read and MFMA sections (7): +8 % on the NT forward shapes at K = 1024, +16..19 % on the NN dgrads
-  // whose B fragments come through ds_read_b64_tr_b16.  The fused-colsum dgrad keeps four pinned 8-MFMA sections (2), which won
-  // the whole-step A/B for it.  (NT at K = 4096 is 2 % faster on 2; not worth a second instantiation per layout.)
-  static const int env_var = [] {
-    const char* e = oasr_experiment_env("OASR_PP_VARIANT");  // experiments: force one variant for a whole process
-    return e ? atoi(e) : -1;
-  }();
-  const int forced = g_pp_dma_in_mma >= 0 ? g_pp_dma_in_mma : env_var;
-  const int var = forced >= 0 ? forced : (CSUM ? 2 : 7);
-  switch (var & 15) {
-    case 1: return launch_pp_variant<TA, TB, SWAP, CSUM, 1>(a, stream);
-    case 2: return launch_pp_variant<TA, TB, SWAP, CSUM, 2>(a, stream);
-    case 3: return launch_pp_variant<TA, TB, SWAP, CSUM, 3>(a, stream);
-    case 6: return launch_pp_variant<TA, TB, SWAP, CSUM, 6>(a, stream);
-    case 7: return launch_pp_variant<TA, TB, SWAP, CSUM, 7>(a, stream);
-    case 15: return launch_pp_variant<TA, TB, SWAP, CSUM, 15>(a, stream);
-    default: return launch_pp_variant<TA, TB, SWAP, CSUM, 0>(a, stream);
-  }
+  const int var = g_hooks.pp_schedule >= 0 ? g_hooks.pp_schedule : (CSUM ? 2 : 7);
+  if (var == 2) return launch_pp_variant<TA, TB, SWAP, CSUM, 2>(a, stream);
+  return launch_pp_variant<TA, TB, SWAP, CSUM, 7>(a, stream);
 }
 
 // Geometry choice for bf16-output GEMMs, from interleaved A/B runs on the OLMoASR-medium shapes (scripts/gemm_ab.py,
@@ -1384,26 +1346,12 @@ bool prefer_pingpong(const GemmArgs& a) {
 
 int launch_skinny(const GemmArgs& a, hipStream_t stream) {
   const dim3 grid(cdiv(a.N, 32));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof.on) {
-    const size_t idx = g_prof.recs.size();
-    while (g_prof.events.size() < 2 * (idx + 1)) {
-      hipEvent_t e;
-      OASR_CHECK_HIP(hipEventCreate(&e));
-      g_prof.events.push_back(e);
-    }
-    e0 = g_prof.events[2 * idx];
-    e1 = g_prof.events[2 * idx + 1];
-    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * (double)a.N * (double)a.K, a.M <= 32 ? "gemm_skinny_kernel<1>" : "gemm_skinny_kernel<2>"));
-    OASR_CHECK_HIP(hipEventRecord(e0, stream));
-  }
-  if (a.M <= 32)
-    hipLaunchKernelGGL(gemm_skinny_kernel<1>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(gemm_skinny_kernel<2>, grid, dim3(256), 0, stream, a);
-  OASR_LAUNCH_CHECK();
-  if (e1) OASR_CHECK_HIP(hipEventRecord(e1, stream));
-  return OASR_OK;
+  return timed_launch(a, gemm_flops(a), a.M <= 32 ? "gemm_skinny_kernel<1>" : "gemm_skinny_kernel<2>", false, stream, [&] {
+    if (a.M <= 32)
+      hipLaunchKernelGGL(gemm_skinny_kernel<1>, grid, dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL(gemm_skinny_kernel<2>, grid, dim3(256), 0, stream, a);
+  });
 }
 
 template <bool TA, bool TB>
@@ -1416,7 +1364,8 @@ int launch_fast_t(const GemmArgs& a, hipStream_t stream) {
     const char* e = oasr_experiment_env("OASR_GEMM_GEOM");
     return e ? atoi(e) : 0;
   }();
-  const int geom = g_fast_geometry ? g_fast_geometry : env_geom;
+  // 1 = 256x128, 2 = 256x256 / 2 stages, 3 = ping-pong (ForcedPath::General never gets here)
+  const int geom = g_hooks.path != ForcedPath::Auto ? (int)g_hooks.path - 1 : env_geom;
   const bool big = geom == 2;  // (the 256x256 / 2-stage geometry lost to 256x128 on every measured shape incl. small split-K outputs: scripts/wgrad_sweep.py)
   if (geom == 3 || (geom == 0 && !atomic_only && prefer_pingpong(a)) ||
       (geom == 0 && atomic_only && a.atomic_on_pp && (a.M % 256) == 0 && (a.N % 256) == 0)) {  // 256x256 ping-pong kernel
@@ -1455,64 +1404,46 @@ int launch_t(const GemmArgs& a, hipStream_t stream) {
   const int lds = 4 * TILE_BYTES;
   { const int rc_ = ensure_dynamic_lds(attr, (const void*)gemm_kernel<TA, TB>, lds); if (rc_) return rc_; }
   const int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
-  dim3 grid(tiles, a.split_k);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof.on) {
-    const size_t idx = g_prof.recs.size();
-    while (g_prof.events.size() < 2 * (idx + 1)) {
-      hipEvent_t e;
-      OASR_CHECK_HIP(hipEventCreate(&e));
-      g_prof.events.push_back(e);
-    }
-    e0 = g_prof.events[2 * idx];
-    e1 = g_prof.events[2 * idx + 1];
-    // algorithmic flops: conv windows count their real kernel width, not the zero padding
-    const double kk = a.A.rpb ? (double)(a.ta ? a.K : a.A.kvalid) : (double)a.K;
-    const double nn = (a.B.rpb && a.tb) ? (double)a.B.kvalid : (double)a.N;
-    static const std::string name = std::string("gemm_kernel<") + (TA ? "true" : "false") + ", " + (TB ? "true" : "false") + ">";
-    g_prof.push(gemm_rec(a, 2.0 * (double)a.M * nn * kk, name.c_str()));
-    OASR_CHECK_HIP(hipEventRecord(e0, stream));
-  }
-  hipLaunchKernelGGL((gemm_kernel<TA, TB>), grid, dim3(256), lds, stream, a);
-  OASR_LAUNCH_CHECK();
-  if (e1) OASR_CHECK_HIP(hipEventRecord(e1, stream));
-  return OASR_OK;
+  const dim3 grid(tiles, a.split_k);
+  // algorithmic flops: conv windows count their real kernel width, not the zero padding
+  const double kk = a.A.rpb ? (double)(a.ta ? a.K : a.A.kvalid) : (double)a.K;
+  const double nn = (a.B.rpb && a.tb) ? (double)a.B.kvalid : (double)a.N;
+  static const std::string name = std::string("gemm_kernel<") + tf(TA) + ", " + tf(TB) + ">";
+  return timed_launch(a, 2.0 * (double)a.M * nn * kk, name.c_str(), false, stream,
+                      [&] { hipLaunchKernelGGL((gemm_kernel<TA, TB>), grid, dim3(256), lds, stream, a); });
 }
 
 }  // namespace
 
-// v < 0: defaults.  bits 0-3: kernel variant (8 = the per-layout default); bits 4-5: 0 = default launch rule, 1 = never
-// persistent, 2 = persistent whenever possible.  (24 = default kernels, plain launches; 40 = default kernels, persistent)
-void gemm_set_variant(int v) {
-  g_pp_dma_in_mma = (v < 0 || (v & 15) == 8) ? -1 : (v & 15);
-  g_pp_persistent = v < 0 ? -1 : (((v >> 4) & 3) == 0 ? -1 : ((v >> 4) & 3) - 1);
-  g_epi_flags = v < 0 ? -1 : ((v >> 6) & 3);  // bit 6: non-temporal output stores, bit 7: non-temporal side-input loads
+// v < 0: defaults.  bits 0-3: ping-pong schedule, 2 or 7 (the VAR of oasr_gemm_pp_kernel) or 8 = the per-layout default; bits 4-5:
+// 0 = default launch rule, 1 = never persistent, 2 = persistent whenever possible; bit 6: non-temporal output stores, bit 7:
+// non-temporal side-input loads.  (24 = default kernels, plain launches; 40 = default kernels, persistent)
+int gemm_set_variant(int v) {
+  const int sched = v & 15, launch = (v >> 4) & 3;
+  OASR_REQUIRE(v < 0 || sched == 2 || sched == 7 || sched == 8,
+               "gemm_set_variant: schedule %d (bits 0-3 of %d) does not exist: 2, 7 or 8 = per-layout default", sched, v);
+  g_hooks.pp_schedule = (v < 0 || sched == 8) ? -1 : sched;
+  g_hooks.pp_persistent = v < 0 ? -1 : launch - 1;
+  g_hooks.epi_flags = v < 0 ? -1 : ((v >> 6) & 3);
+  return OASR_OK;
 }
 void gemm_set_stagger(int sleeps, int phases) {  // sleeps < 0: stagger off everywhere (A/B baseline)
-  g_stagger = sleeps;
-  g_stagger_phases = phases < 2 ? 2 : phases;
+  g_hooks.stagger = sleeps;
+  g_hooks.stagger_phases = phases < 2 ? 2 : phases;
 }
 
-int launch_gemm(const GemmArgs& a, hipStream_t stream) {
-  OASR_REQUIRE(a.A.ptr && a.B.ptr, "gemm: null operand");
-  if (g_epi_flags >= 0 && a.epi_flags != g_epi_flags + 256) {
-    GemmArgs b = a;
-    b.epi_flags = g_epi_flags + 256;  // (+256: marks the override as applied)
-    return launch_gemm(b, stream);
-  }
-  if (g_stagger > 0 && a.stagger == 0) {
-    GemmArgs b = a;
-    b.stagger = g_stagger;
-    b.stagger_phases = g_stagger_phases;
-    return launch_gemm(b, stream);
-  }
-  // measured (scripts/gemm_stagger_ab.py, M = 192000): +14 % on N = 1024, K = 1024 (tiles of ~8 us whose epilogues collide),
-  // 0..-3 % on every longer tile -> only the short ones are staggered: 8 phases x one s_sleep(127)
-  if (g_stagger == 0 && a.stagger == 0 && a.N <= 1024 && a.K <= 1024 && a.M >= 16384 && a.out && !a.out_f32) {
-    GemmArgs b = a;
-    b.stagger = 1;
-    b.stagger_phases = 8;
-    return launch_gemm(b, stream);
+int launch_gemm(const GemmArgs& args, hipStream_t stream) {
+  OASR_REQUIRE(args.A.ptr && args.B.ptr, "gemm: null operand");
+  GemmArgs a = args;  // the call with the process-wide hooks and launch rules applied
+  if (g_hooks.epi_flags >= 0) a.epi_flags = g_hooks.epi_flags;
+  if (a.stagger == 0 && g_hooks.stagger > 0) {
+    a.stagger = g_hooks.stagger;
+    a.stagger_phases = g_hooks.stagger_phases;
+  } else if (a.stagger == 0 && g_hooks.stagger == 0 && a.N <= 1024 && a.K <= 1024 && a.M >= 16384 && a.out && !a.out_f32) {
+    // measured (scripts/gemm_stagger_ab.py, M = 192000): +14 % on N = 1024, K = 1024 (tiles of ~8 us whose epilogues collide),
+    // 0..-3 % on every longer tile -> only the short ones are staggered: 8 phases x one s_sleep(127)
+    a.stagger = 1;
+    a.stagger_phases = 8;
   }
   OASR_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: bad shape %d %d %d", a.M, a.N, a.K);
   OASR_REQUIRE((a.N % 4) == 0, "gemm: N (%d) must be a multiple of 4", a.N);
@@ -1521,7 +1452,6 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   // (a k-contiguous operand is fetched in 16-byte chunks that are bounds-checked at their first element: a last chunk that straddles K
   //  would bring in up to 7 elements past it, and NaN / Inf there survives the other operand's zero fill)
   OASR_REQUIRE(a.tb || (a.K % 8) == 0 || a.B.rpb, "gemm: K must be a multiple of 8 for k-contiguous B");
-  OASR_REQUIRE(!a.ta || (a.M % 8) == 0 || true, "gemm");
   OASR_REQUIRE(a.split_k >= 1, "gemm: split_k");
   OASR_REQUIRE(a.split_k == 1 || (a.atomic && a.out_f32 && !a.out && !a.out_pre), "gemm: split_k > 1 needs atomic fp32 output only");
   OASR_REQUIRE(a.out || a.out_f32 || a.out_pre, "gemm: no output");
@@ -1530,18 +1460,14 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
     const char* e = oasr_experiment_env("OASR_GEMM_GM");
     return e ? atoi(e) : 0;
   }();
-  if (a.raster_gm == 0 && env_gm > 0) {
-    GemmArgs b = a;
-    b.raster_gm = env_gm;
-    return launch_gemm(b, stream);
-  }
+  if (a.raster_gm == 0 && env_gm > 0) a.raster_gm = env_gm;
   // decode-sized problems: a few token rows against a whole weight matrix
   if (a.M <= 64 && !a.ta && !a.tb && !a.A.rpb && !a.B.rpb && (a.K % BK) == 0 && a.split_k == 1 && !a.atomic && !a.colsum &&
-      !g_force_general && g_fast_geometry == 0)
+      g_hooks.path == ForcedPath::Auto)
     return launch_skinny(a, stream);
   const bool atomic_only = a.atomic && a.out_f32 && !a.out && !a.out_pre;
   const bool fast = !a.A.rpb && !a.B.rpb && (a.K % BK) == 0 && (!a.ta || (a.M % 8) == 0) && (!a.tb || (a.N % 8) == 0) &&
-                    a.M >= 8 && a.N >= 8 && !g_force_general && (atomic_only || fast_rows_ok(a));
+                    a.M >= 8 && a.N >= 8 && g_hooks.path != ForcedPath::General && (atomic_only || fast_rows_ok(a));
   if (fast) {
     if (!a.ta && !a.tb) return launch_fast_t<false, false>(a, stream);
     if (!a.ta && a.tb) return launch_fast_t<false, true>(a, stream);
@@ -1633,7 +1559,4 @@ int gemm_profile_records(char* buf, int cap) {
   return (int)g_prof.recs.size();
 }
 
-void gemm_force_general(int on) {
-  g_force_general = (on == 1);
-  g_fast_geometry = on >= 2 ? on - 1 : 0;  // 2 -> force 256x128, 3 -> force 256x256 (2-stage), 4 -> force 256x256 ping-pong
-}
+void gemm_force_general(int on) { g_hooks.path = (on >= 1 && on <= 4) ? (ForcedPath)on : ForcedPath::Auto; }

@@ -76,8 +76,10 @@ int launch_gemm(const GemmArgsF& a, hipStream_t stream);  // fp32 validation ker
 // bench-only: time every GEMM launch with HIP events on its stream; collect() sums per variant (2*ta+tb)
 void gemm_profile_enable(int on);
 int gemm_profile_lane(int lane);  // tag the following launches' profile records (0 = main stream, 1 = side stream); returns the old tag
-void gemm_force_general(int on);  // tests: disable the direct-to-LDS fast path
-void gemm_set_variant(int dma_in_mma);  // experiments: ping-pong kernel issues its DMA pieces between the MFMAs
+void gemm_force_general(int on);  // tests: 0 = automatic choice, 1 = general kernel, 2 = 256x128, 3 = 256x256 two-stage, 4 = ping-pong
+// tests / experiments on the ping-pong kernel: v < 0 = defaults; bits 0-3 = K-tile schedule (2, 7, or 8 = per-layout default), bits 4-5 = plain /
+// persistent launch, bits 6-7 = non-temporal epilogue stores / side-input loads.  OASR_EINVAL, and no change, for a schedule that does not exist
+int gemm_set_variant(int v);
 void gemm_set_stagger(int sleeps, int phases);  // experiments: first-wave phase stagger of the ping-pong kernel
 int gemm_profile_collect(double ms[4], double flops[4], long count[4], char* by_symbol, int cap);
 int gemm_profile_records(char* buf, int cap);  // tests: one text line per recorded launch (kernel symbol, shape, layout, epilogue flags, launch options)

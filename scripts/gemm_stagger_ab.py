@@ -61,17 +61,6 @@ def main():
             print(row, flush=True)
         N.lib().oasr_gemm_set_variant(-1)
         return
-    if len(sys.argv) > 1 and sys.argv[1] == "variant":  # A/B of where the ping-pong kernel issues its DMA pieces
-        print(f"{'case':34s}  variants 7 15 7 15 (bit 3 = both wave groups in lockstep, no ping-pong offset) (bit 0 = DMA between the MFMAs, bit 1 = MFMA sections pinned, bit 2 = two 16-MFMA sections per K-tile): ms TF/s")
-        for name, fn, flops in cases:
-            row = f"{name:34s} "
-            for v in (7, 15, 7, 15):
-                N.lib().oasr_gemm_set_variant(v)
-                ms = timeit(fn)
-                row += f"{ms:7.3f} {flops / ms / 1e9:6.0f} | "
-            print(row, flush=True)
-        N.lib().oasr_gemm_set_variant(-1)
-        return
     settings = [(0, 2), (2, 2), (5, 2), (2, 4), (3, 4), (1, 8)]
     print(f"{'case':34s} " + " ".join(f"s{a}p{b}: ms TF/s " for a, b in settings))
     for name, fn, flops in cases:

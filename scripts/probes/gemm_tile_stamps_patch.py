@@ -2,13 +2,14 @@
 workgroup in a __device__ buffer + an exported reader).  The copy is compiled into a scratch library next to the product objects and
 loaded through OASR_LIB (scripts/probes/gemm_tile_stamps.py reads the records): profiles/r03_gemm_tile_stamps.txt.
 usage: python scripts/probes/gemm_tile_stamps_patch.py /tmp/gemm_dbg.hip"""
+import os
 import sys
-s=open('/root/repo/olmoasr_amd/csrc/gemm.hip').read()
+s=open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'olmoasr_amd', 'csrc', 'gemm.hip')).read()
 def rep(a,b):
     global s
     assert a in s, a[:60]
     s=s.replace(a,b,1)
-rep('int g_stagger = 0, g_stagger_phases = 2;','__device__ unsigned long long g_gemm_dbg[8 * 16384];\nextern "C" int oasr_gemm_dbg_read(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gemm_dbg), bytes); }\nint g_stagger = 0, g_stagger_phases = 2;')
+rep('GemmHooks g_hooks;','__device__ unsigned long long g_gemm_dbg[8 * 16384];\nextern "C" int oasr_gemm_dbg_read(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gemm_dbg), bytes); }\nGemmHooks g_hooks;')
 rep('''  int v = blockIdx.x;
   OASR_PP_TILE(v);
   if (nt <= 0) return;  // (uneven split-K; the host never launches those persistent)''','''  const unsigned long long dbg_r0 = __builtin_amdgcn_s_memrealtime(), dbg_t0 = __builtin_amdgcn_s_memtime();
@@ -17,11 +18,11 @@ rep('''  int v = blockIdx.x;
   OASR_PP_TILE(v);
   if (nt <= 0) return;  // (uneven split-K; the host never launches those persistent)''')
 rep('''  OASR_PP_BARRIER();
-  if (wm == 1 && !(VAR & 8)) OASR_PP_BARRIER();  // the upper half trails by one barrier from here on (VAR bit 3: lockstep experiment)''','''  OASR_PP_BARRIER();
+  if (wm == 1) OASR_PP_BARRIER();  // the upper half trails by one barrier from here on''','''  OASR_PP_BARRIER();
   dbg_t1 = __builtin_amdgcn_s_memtime();
-  if (wm == 1 && !(VAR & 8)) OASR_PP_BARRIER();  // the upper half trails by one barrier from here on (VAR bit 3: lockstep experiment)''')
-rep('''  if (wm == 0 && !(VAR & 8)) OASR_PP_BARRIER();  // re-join: the trailing half has finished its LDS reads after this
-''','''  if (wm == 0 && !(VAR & 8)) OASR_PP_BARRIER();  // re-join: the trailing half has finished its LDS reads after this
+  if (wm == 1) OASR_PP_BARRIER();  // the upper half trails by one barrier from here on''')
+rep('''  if (wm == 0) OASR_PP_BARRIER();  // re-join: the trailing half has finished its LDS reads after this
+''','''  if (wm == 0) OASR_PP_BARRIER();  // re-join: the trailing half has finished its LDS reads after this
   dbg_t2 = __builtin_amdgcn_s_memtime();
 ''')
 rep('''  fast_epilogue<SWAP, CSUM>(p, acc, stg, (float*)(smem + 2 * BUF + wave * 256), em0, en0, wm, wn, lane);

@@ -197,19 +197,20 @@ def test_gemm_pingpong_persistent_launch_matches_plain(layout):
         assert bool(((outs[1][0].float() - ref).abs() <= ulp + 1e-2 * ref.abs() + 1e-3).all()), "persistent " + layout
 
 
+@pytest.mark.parametrize("M,N_,K", [(2560, 1024, 1024), (520, 512, 320)])  # the second: ragged last row panel, an odd count (5) of K-tiles
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, True)])
-def test_gemm_pingpong_dma_placement_variants_are_bit_identical(ta, tb):
-    """The 256x256 kernel issues its direct-to-LDS pieces either in the fragment-read section or between the MFMAs
-    (per-layout default); both schedules must produce the same bits."""
+def test_gemm_pingpong_schedules_are_bit_identical(ta, tb, M, N_, K):
+    """The 256x256 kernel walks a K-tile in four phases of 8 MFMAs (schedule 2) or in two sections of 16 with part of the direct-to-LDS
+    pieces issued between the MFMAs (7, the default without fused column sums); every accumulator receives its K slices in the same
+    order in both, so they must produce the same bits."""
     from olmoasr_amd import _native as N
-    M, N_, K = 2560, 1024, 1024
     A = rnd(K, M, seed=1) if ta else rnd(M, K, seed=1)
     B = rnd(K, N_, seed=2, scale=0.05) if tb else rnd(N_, K, seed=2, scale=0.05)
     outs = []
     try:
         N.lib().oasr_gemm_force_general(4)  # force the ping-pong kernel
-        for v in (0, 1):
-            N.lib().oasr_gemm_set_variant(v)
+        for v in (2, 7):
+            N.check(N.lib().oasr_gemm_set_variant(v), "variant")
             if ta:  # wgrad layout: fp32 atomic output
                 o = torch.zeros(M, N_, device=DEV)
                 ops().gemm(A, B, M, N_, K, ta=ta, tb=tb, out_f32=o, atomic=True, split_k=1)
@@ -223,7 +224,7 @@ def test_gemm_pingpong_dma_placement_variants_are_bit_identical(ta, tb):
     assert torch.equal(outs[0], outs[1])
     Af = A.float().t() if ta else A.float()
     Bf = B.float().t() if tb else B.float()
-    close(outs[1], Af @ Bf.t(), name="dma-in-mma variant")
+    close(outs[1], Af @ Bf.t(), name="ping-pong schedule 7")
 
 
 def test_gemm_epilogues(gemm_path):

@@ -181,6 +181,24 @@ def test_testing_hooks_are_inert_without_the_opt_in(native, monkeypatch):
     assert lib.oasr_span_set_side_streams(-1) == 0 and 0 <= lib.oasr_span_side_streams() <= 15
 
 
+def test_gemm_set_variant_accepts_only_the_schedules_that_exist(native, monkeypatch):
+    """oasr_gemm_set_variant: bits 0-3 name a ping-pong schedule that is compiled (2, 7) or the per-layout default (8); anything else is
+    refused with a message and leaves the accepted setting as it was (host logic only: no GPU needed)."""
+    lib = native.lib()
+    monkeypatch.setenv("OASR_TESTING_HOOKS", "1")
+    try:
+        for v in (-1, 2, 7, 8, 24, 40, 24 | 64 | 128):
+            assert lib.oasr_gemm_set_variant(v) == 0, v
+        for v in (0, 1, 3, 6, 15):
+            assert lib.oasr_gemm_set_variant(40) == 0
+            assert lib.oasr_gemm_set_variant(v) != 0, v
+            msg = lib.oasr_last_error()
+            assert b"gemm_set_variant" in msg and b"schedule %d " % v in msg, msg
+            assert lib.oasr_gemm_set_variant(-1) == 0  # the state is still one the setter can leave
+    finally:
+        assert lib.oasr_gemm_set_variant(-1) == 0
+
+
 def test_a_library_of_another_abi_generation_is_refused_before_any_symbol_is_declared(native, tmp_path, monkeypatch):
     """a stale liboasr.so (older ABI: no oasr_sizeof_attn_args, fewer entry points) must be refused by the VERSION check --
     not die with an AttributeError inside the declarations -- and must not stay cached as a half-declared handle."""
