@@ -425,6 +425,70 @@ typedef struct oasr_edit_args {
 size_t oasr_sizeof_edit_args(void);
 int oasr_edit_counts(const oasr_edit_args*, void* stream);
 int oasr_edit_counts_host(const oasr_edit_args*);
+/* Speed perturbation (Ko et al. 2015; Kaldi's 0.9 / 1.0 / 1.1) of int16 PCM AHEAD of oasr_log_mel, with the transcript's timestamp tokens
+ * moved along (csrc/speed.hip; the rule itself: csrc/speed_core.h).  Entry points only: OASR_ABI_VERSION is unchanged, and a binding checks
+ * oasr_sizeof_speed and oasr_sizeof_speed_args like oasr_sizeof_specaug.  The operator is an integer function: int16 in, Q15 integer taps,
+ * an exact sum, int16 out; floating point enters only where the HOST builds a ratio's tap table, once.
+ *
+ * Policy: factor i plays a clip P[i] / Q[i] times FASTER -- output sample n sits at input position n P / Q.  1 <= n_factors <=
+ * OASR_SPEED_MAX_FACTORS; 1 <= P, Q <= 32; gcd(P, Q) = 1; Q <= 2 P and P <= 2 Q; else OASR_EINVAL.
+ *
+ * Choice per clip, with mix() and h = mix(mix(seed) ^ clip), clip = first_clip + row, as at oasr_spec_augment (the SAME h; kind 3 keeps the
+ * draw apart from the masks' kinds 1 and 2), n_valid the row's leading non-padding samples and N the row length:
+ *     i = mix(h ^ (3 << 16)) % n_factors        (P, Q) = (P[i], Q[i])        n_out = (n_valid * Q) / P   (integer division)
+ *     n_out > N (a slow-down would push audio the transcript covers past the end of the row): the identity, P = Q = 1, n_out = n_valid,
+ *     reported as factor -1
+ * Identity: P == Q is a copy of the whole row, bit for bit; it is not a filter.
+ *
+ * Table of a ratio P != Q (double precision, on the host):  fc = 0.95 min(1, Q / P),  Wd = 16 / fc,  H = floor(Wd) + 1,  2 H taps per phase;
+ *     for phase r < Q, tap j < 2 H:   k = j - H + 1,   u = k - r / Q
+ *         c = fc sinc(fc u) (0.5 + 0.5 cos(pi u / Wd))  where |u| < Wd, else 0         sinc(x) = sin(pi x) / (pi x), sinc(0) = 1
+ *         T[r][j] = floor(c * 32768 + 0.5)
+ *     then the phase's largest tap (the first of equal ones) takes + (32768 - sum_j T[r][j]): every phase sums to exactly 2^15.
+ * oasr_speed_table writes T as int32 [Q][2 H] (at most 32 x 68 entries) and H; HOST function; P == Q or a pair outside the policy's bounds
+ * is OASR_EINVAL.
+ *
+ * Sample n < n_out:   m = (n P) / Q,  r = (n P) % Q,   acc = sum_j x[m + j - H + 1] T[r][j]   with x = 0 outside [0, n_valid)
+ *                     y[n] = clamp((acc + 16384) >> 15, -32768, 32767)        (arithmetic shift; acc exact: it needs more than 32 bits,
+ *                     sum_j |T[r][j]| reaches 73920 at 9 / 10)
+ * and y[n] = 0 for n_out <= n < N.
+ *
+ * Timestamp tokens (optional): a token t in [ts_begin, ts_begin + ts_max], k = t - ts_begin, becomes
+ *     ts_begin + min(ts_max, (2 k Q + P) / (2 P))
+ * (the nearest timestamp of k Q / P, halves up), every other token stays; the map is monotone and the number of tokens unchanged.
+ *
+ * oasr_speed_perturb: device pointers, ONE launch on `stream`, never synchronises (the first call that meets a ratio on a device uploads
+ * its table, like the log-mel tables).  pcm_in / pcm_out int16 [B, N] with row strides ld_in / ld_out >= N (samples), out of place: the two
+ * must not overlap.  n_valid int32 [B].  n_out, factor_out: int32 [B] or NULL.  tokens_a, tokens_b: int64 [B, S] (row strides ld_tokens_a /
+ * ld_tokens_b >= S) rewritten in place, or NULL; S >= 1, ts_begin >= 0 and 0 <= ts_max <= 2^24 when either is given.  1 <= B <= 65535,
+ * 1 <= N <= 2^26.  The plan is evaluated on the device; lengths live there, so the host cannot refuse them: a row whose n_valid is outside
+ * [0, N] is copied unchanged, reports factor -1 and n_out = min(max(n_valid, 0), N), and its tokens are left alone.  Everything else that
+ * is wrong is OASR_EINVAL before a launch.
+ * oasr_speed_perturb_host: HOST function (no GPU call, host pointers), the same rule from the same text; an n_valid outside [0, N] is
+ * OASR_EINVAL before anything is written.
+ * oasr_speed_plan: HOST function: the (P, Q), n_out and factor of ONE clip (each output may be NULL); 0 <= n_valid <= N, else OASR_EINVAL. */
+#define OASR_SPEED_MAX_FACTORS 8
+typedef struct oasr_speed {
+  int32_t n_factors;
+  int32_t P[OASR_SPEED_MAX_FACTORS], Q[OASR_SPEED_MAX_FACTORS];
+} oasr_speed;
+typedef struct oasr_speed_args {
+  const int16_t* pcm_in;
+  int16_t* pcm_out;
+  const int32_t* n_valid;
+  int32_t *n_out, *factor_out;
+  int64_t *tokens_a, *tokens_b;
+  int64_t ld_in, ld_out, ld_tokens_a, ld_tokens_b;
+  uint64_t seed, first_clip;
+  int32_t B, N, S, ts_begin, ts_max;
+  oasr_speed policy;
+} oasr_speed_args;
+size_t oasr_sizeof_speed(void);
+size_t oasr_sizeof_speed_args(void);
+int oasr_speed_perturb(const oasr_speed_args*, void* stream);
+int oasr_speed_perturb_host(const oasr_speed_args*);
+int oasr_speed_plan(const oasr_speed* policy, uint64_t seed, uint64_t clip, int n_valid, int N, int* P, int* Q, int* n_out, int* factor);
+int oasr_speed_table(int P, int Q, int32_t* out, int* H);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 /* The same operator with the regularisers of oasr_train_step_args (label_smoothing, z_loss: the formula there; gscale takes the place of

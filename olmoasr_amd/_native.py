@@ -63,6 +63,19 @@ class EditArgs(C.Structure):  # include/oasr.h: oasr_edit_args
                 ("ld_hyp", C.c_int64), ("ld_ref", C.c_int64), ("B", C.c_int32), ("Lh", C.c_int32), ("Lr", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Speed(C.Structure):  # include/oasr.h: oasr_speed
+    MAX_FACTORS = 8  # OASR_SPEED_MAX_FACTORS
+    _fields_ = [("n_factors", C.c_int32), ("P", C.c_int32 * 8), ("Q", C.c_int32 * 8)]
+
+
+class SpeedArgs(C.Structure):  # include/oasr.h: oasr_speed_args
+    MAX_N = 1 << 26
+    _fields_ = [("pcm_in", C.c_void_p), ("pcm_out", C.c_void_p), ("n_valid", C.c_void_p), ("n_out", C.c_void_p), ("factor_out", C.c_void_p),
+                ("tokens_a", C.c_void_p), ("tokens_b", C.c_void_p), ("ld_in", C.c_int64), ("ld_out", C.c_int64), ("ld_tokens_a", C.c_int64),
+                ("ld_tokens_b", C.c_int64), ("seed", C.c_uint64), ("first_clip", C.c_uint64), ("B", C.c_int32), ("N", C.c_int32),
+                ("S", C.c_int32), ("ts_begin", C.c_int32), ("ts_max", C.c_int32), ("policy", Speed)]
+
+
 class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
     _fields_ = [(n, C.c_void_p) for n in ("mel", "xa", "tokens", "targets", "text_len", "span_host", "mel_clip_max", "loss_out", "logits_out",
                                           "pred_out", "seg_events")] + \
@@ -76,6 +89,7 @@ DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_
 # The query-block tables of oasr_attn_args (qblk128 / qblk256 / n128 / n256: compact grids of the span-limited attention launches) grow the struct at its end under the same version number: a library built without them is refused by the oasr_sizeof_attn_args check in lib().
 # Token error counts (oasr_edit_counts, oasr_edit_counts_host) and the prediction kernel's hook (oasr_test_argmax_rows) likewise: a stale library is refused by the oasr_sizeof_edit_args check in lib().
 # Label smoothing / z-loss (oasr_train_step_args.label_smoothing, z_loss, loss_parts_out, loss_parts_rows; oasr_cross_entropy_ex) grow the step's struct at its end and add one entry point under the same version number: a library built without them is refused by the oasr_sizeof_train_step_args check in lib().
+# Speed perturbation (oasr_speed_perturb, oasr_speed_perturb_host, oasr_speed_plan, oasr_speed_table) likewise: entry points only, a stale library refused by the oasr_sizeof_speed / oasr_sizeof_speed_args checks in lib().
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
@@ -170,6 +184,12 @@ def _declare(lib):
         "oasr_sizeof_edit_args": (sz, []),
         "oasr_edit_counts": (i32, [C.POINTER(EditArgs), vp]),
         "oasr_edit_counts_host": (i32, [C.POINTER(EditArgs)]),
+        "oasr_sizeof_speed": (sz, []),
+        "oasr_sizeof_speed_args": (sz, []),
+        "oasr_speed_perturb": (i32, [C.POINTER(SpeedArgs), vp]),
+        "oasr_speed_perturb_host": (i32, [C.POINTER(SpeedArgs)]),
+        "oasr_speed_plan": (i32, [C.POINTER(Speed), C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "oasr_speed_table": (i32, [i32, i32, vp, C.POINTER(i32)]),
         "oasr_test_argmax_rows": (i32, [vp, i32, i64, i32, i64, vp, vp, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cross_entropy_ex": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, f32, f32, vp, vp]),
@@ -239,6 +259,9 @@ def lib():
         if int(handle.oasr_sizeof_edit_args()) != C.sizeof(EditArgs):
             raise NativeError(f"{LIB_PATH}: oasr_edit_args of {int(handle.oasr_sizeof_edit_args())} bytes, this binding passes "
                               f"{C.sizeof(EditArgs)} -- rebuild (__graft_entry__.build())")
+        if int(handle.oasr_sizeof_speed()) != C.sizeof(Speed) or int(handle.oasr_sizeof_speed_args()) != C.sizeof(SpeedArgs):
+            raise NativeError(f"{LIB_PATH}: oasr_speed / oasr_speed_args of {int(handle.oasr_sizeof_speed())} / {int(handle.oasr_sizeof_speed_args())} "
+                              f"bytes, this binding passes {C.sizeof(Speed)} / {C.sizeof(SpeedArgs)} -- rebuild (__graft_entry__.build())")
         if int(handle.oasr_sizeof_train_step_args()) != C.sizeof(TrainStepArgs):
             raise NativeError(f"{LIB_PATH}: oasr_train_step_args of {int(handle.oasr_sizeof_train_step_args())} bytes, this binding passes "
                               f"{C.sizeof(TrainStepArgs)} -- rebuild (__graft_entry__.build())")

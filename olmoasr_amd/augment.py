@@ -7,7 +7,16 @@ applied by one native launch (``ops.spec_augment_``, csrc/specaug.hip) between `
 
 A clip's masks are a pure integer function of (seed, clip stream id, policy, shape) -- include/oasr.h states the rule -- so the library's
 host twin gives the same plan without a GPU (``plan``, ``masked_cells``), a resumed run draws what the uninterrupted run would have drawn,
-and the masks of a clip do not depend on the micro-batch it travels in."""
+and the masks of a clip do not depend on the micro-batch it travels in.
+
+Speed perturbation (Ko et al. 2015; Kaldi's 0.9 / 1.0 / 1.1) works one stage earlier, on the int16 clips ahead of ``ops.log_mel``, and moves
+the transcript's timestamp tokens with the audio (``ops.speed_perturb``, csrc/speed.hip):
+
+    speed = augment.SpeedPerturb.preset("3way")          # 9/10, 1/1, 11/10 times faster, one drawn per clip
+    pcm, n_out, factor = speed.apply(pcm, n_valid, seed, first_clip=stream_id_of_row_0, tokens=(text_input, text_y))
+
+It is an integer function of the samples, drawn from the same hash stream as the masks (kind 3): ``SpeedPerturb.plan`` gives a clip's ratio,
+new length and factor index without a GPU."""
 import math
 from dataclasses import dataclass
 
@@ -49,6 +58,49 @@ class SpecAugment:
         """In place on finalized log-mel fp32 [B, n_mels, T] / [n_mels, T] on the GPU; row b takes stream id first_clip + b.  Returns mel."""
         from . import ops
         return ops.spec_augment_(mel, **self.kwargs(int(mel.shape[-1])), fill=self.fill, seed=seed, first_clip=first_clip)
+
+
+SPEED_PRESETS = {"3way": ((9, 10), (1, 1), (11, 10))}  # Kaldi's speeds 0.9, 1.0, 1.1
+
+
+@dataclass(frozen=True)
+class SpeedPerturb:
+    factors: tuple = SPEED_PRESETS["3way"]  # (P, Q) pairs: P / Q times faster; coprime, inside [1, 32], ratio inside [1/2, 2], at most 8
+    ts_begin: int = 50363                   # <|0.00|> of the multilingual vocabulary the training script uses
+    ts_max: int = 1500                      # <|30.00|> = ts_begin + 1500
+
+    def __post_init__(self):
+        from . import ops
+        ops.speed_policy(self.factors)
+        object.__setattr__(self, "factors", tuple((int(p), int(q)) for p, q in self.factors))
+
+    @classmethod
+    def preset(cls, name, **overrides):
+        """"3way": each clip at 0.9, 1.0 or 1.1 times its speed, one third of the clips each."""
+        if name not in SPEED_PRESETS:
+            raise ValueError(f"SpeedPerturb.preset: unknown policy {name!r}; known: {sorted(SPEED_PRESETS)}")
+        return cls(**{"factors": SPEED_PRESETS[name], **overrides})
+
+    def apply(self, pcm, n_valid, seed, first_clip=0, tokens=(), out=None):
+        """int16 [B, N] on the GPU -> (pcm_out, n_out, factor), out of place; row b takes stream id first_clip + b; the timestamp ids of
+        ``tokens`` (up to two int64 [B, S]) move in place."""
+        from . import ops
+        return ops.speed_perturb(pcm, n_valid, factors=self.factors, seed=seed, first_clip=first_clip, tokens=tokens, ts_begin=self.ts_begin,
+                                 ts_max=self.ts_max, out=out)
+
+    def plan(self, seed, clip, n_valid, N):
+        """(P, Q, n_out, factor) of stream id ``clip``, from the library's host function: no GPU needed."""
+        from . import ops
+        return ops.speed_plan(self.factors, seed, clip, n_valid, N)
+
+    def factor_counts(self, seed, first_clip, n_valid, N):
+        """Per factor, how many clips of a batch at stream ids first_clip .. take it (host ``n_valid``), from the plan alone: a list of
+        len(factors) + 1 integers whose LAST entry counts the clips that fell back to the copy because the slow-down they drew would not
+        fit the row -- so the list always sums to the number of clips."""
+        counts = [0] * (len(self.factors) + 1)
+        for b, nv in enumerate(n_valid):
+            counts[self.plan(seed, (first_clip + b) & _U64, int(nv), N)[3]] += 1  # (-1, the fallback, indexes the last entry)
+        return counts
 
 
 def plan(policy: SpecAugment, seed: int, clip: int, n_mels: int = 80, T: int = 3000):

@@ -329,6 +329,11 @@ int launch_argmax_rows(const float* logits, long ld, int V, long n_rows, const i
 struct oasr_specaug;
 int launch_spec_augment(float* mel, int B, int n_mels, int T, const oasr_specaug* policy, uint64_t seed, uint64_t first_clip, hipStream_t s);
 
+// ---- speed perturbation (speed.hip; the contract: include/oasr.h at oasr_speed_perturb, the rule: speed_core.h) ---------------------------
+// pcm_out = each clip of pcm_in resampled by its seeded factor (or copied), timestamp tokens rescaled in place; one launch, plan on the device
+struct oasr_speed_args;
+int launch_speed_perturb(const oasr_speed_args* a, hipStream_t s);
+
 // ---- LoRA adapters in weight space (lora.hip) -----------------------------------------------------------------
 // out = W0 + scale * B . A  (W0 [rows][cols] fp32, A [r][cols], B [rows][r]; k sum in ascending order): exactly one of out32 (fp32, may be w0
 // itself) / out16 (bf16, the rounding of launch_cast_f32_bf16)

@@ -172,7 +172,7 @@ class ShardLoader:
         n_slot = self.depth + 2  # `depth` in flight + the one being consumed + the one just handed back
         pin = dict(pin_memory=True) if self.cuda else {}
         self.h = [dict(pcm=torch.zeros(self.B, N_SAMPLES, dtype=torch.int16, **pin), ti=torch.full((self.B, N_TEXT_CTX), PAD_ID, dtype=torch.int64, **pin),
-                       ty=torch.full((self.B, N_TEXT_CTX), PAD_ID, dtype=torch.int64, **pin), tl=torch.zeros(self.B, dtype=torch.int32, **pin))
+                       ty=torch.full((self.B, N_TEXT_CTX), PAD_ID, dtype=torch.int64, **pin), tl=torch.zeros(self.B, dtype=torch.int32, **pin), nv=torch.zeros(self.B, dtype=torch.int32, **pin))
                   for _ in range(n_slot)]
         self.d = [{k: torch.empty_like(v, device=self.device) for k, v in slot.items()} for slot in self.h] if self.cuda else self.h
         # (high priority: a default-priority stream may share the compute stream's hardware queue on ROCm and run behind it -- see ddp.GradReducer)
@@ -183,6 +183,8 @@ class ShardLoader:
         self.next_slot = 0
         self.last = None                  # slot handed out by the previous __next__
         self.last_span = None             # HOST int32 [b]: supervised span of the batch the last __next__ returned (synth.supervised_span_host)
+        self.last_n_valid = None          # DEVICE int32 [b]: leading non-padding samples of each clip of that batch (ops.speed_perturb's n_valid)
+        self.last_n_valid_host = None     # the same on the HOST (a copy: the pinned slot is recycled)
         self._fill()
 
     def _load_into(self, slot: int, row: int, index: int):
@@ -195,6 +197,7 @@ class ShardLoader:
         h["ti"][row] = ti
         h["ty"][row] = ty
         h["tl"][row] = tl
+        h["nv"][row] = n
 
     def _fill(self):
         while len(self.pending) < self.depth:
@@ -217,7 +220,7 @@ class ShardLoader:
             with torch.cuda.stream(self.copy_stream):
                 if self.consumed[slot] is not None:
                     self.copy_stream.wait_event(self.consumed[slot])
-                for k in ("pcm", "ti", "ty", "tl"):
+                for k in ("pcm", "ti", "ty", "tl", "nv"):
                     self.d[slot][k].copy_(self.h[slot][k], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.copy_stream)
@@ -248,6 +251,7 @@ class ShardLoader:
             self._upload(self.pending[0])  # the next batch's copy goes out now, under this batch's kernels
         self.last = slot
         d, b = self.d[slot], entry[3]
+        self.last_n_valid, self.last_n_valid_host = d["nv"][:b], self.h[slot]["nv"][:b].clone()
         return d["pcm"][:b], d["ti"][:b], d["ty"][:b], d["tl"][:b]
 
     def close(self):

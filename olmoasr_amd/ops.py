@@ -528,9 +528,9 @@ def specaug_policy(freq_masks, freq_width, time_masks, time_width, fill=0.0):
     return N.SpecAug(freq_masks, freq_width, time_masks, time_width, float(fill))
 
 
-def _u64(name, v):
+def _u64(name, v, who="spec_augment"):
     if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= _U64:
-        raise ValueError(f"spec_augment: {name} must be an integer in [0, 2^64), got {v!r}")
+        raise ValueError(f"{who}: {name} must be an integer in [0, 2^64), got {v!r}")
     return v
 
 
@@ -569,6 +569,146 @@ def spec_augment_plan(*, freq_masks, freq_width, time_masks, time_width, seed=0,
     f_iv, t_iv = (C.c_int32 * (2 * max(1, freq_masks)))(), (C.c_int32 * (2 * max(1, time_masks)))()
     N.check(N.lib().oasr_spec_augment_plan(C.byref(pol), _u64("seed", seed), _u64("clip", clip), n_mels, T, f_iv, t_iv), "oasr_spec_augment_plan")
     return ([(f_iv[2 * i], f_iv[2 * i + 1]) for i in range(freq_masks)], [(t_iv[2 * i], t_iv[2 * i + 1]) for i in range(time_masks)])
+
+
+def speed_policy(factors):
+    """The ``oasr_speed`` block of a list of (P, Q) factors -- P / Q times faster -- refused here (ValueError) for what the library would
+    refuse (OASR_EINVAL): 1 .. 8 pairs of coprime integers in [1, 32] with a ratio inside [1/2, 2]."""
+    try:
+        pairs = [tuple(f) for f in factors]
+    except TypeError:
+        raise ValueError(f"speed_perturb: factors must be a sequence of (P, Q) pairs, got {factors!r}")
+    if not 1 <= len(pairs) <= N.Speed.MAX_FACTORS:
+        raise ValueError(f"speed_perturb: between 1 and {N.Speed.MAX_FACTORS} factors, got {len(pairs)}")
+    pol = N.Speed()
+    pol.n_factors = len(pairs)
+    for i, pq in enumerate(pairs):
+        if len(pq) != 2 or any(not isinstance(v, int) or isinstance(v, bool) for v in pq):
+            raise ValueError(f"speed_perturb: factor {pq!r} is not a pair of integers (P, Q)")
+        p, q = pq
+        if not (1 <= p <= 32 and 1 <= q <= 32):
+            raise ValueError(f"speed_perturb: factor {p}/{q}: P and Q must lie in [1, 32]")
+        if math.gcd(p, q) != 1:
+            raise ValueError(f"speed_perturb: factor {p}/{q}: P and Q must be coprime")
+        if q > 2 * p or p > 2 * q:
+            raise ValueError(f"speed_perturb: factor {p}/{q}: the ratio must lie in [1/2, 2]")
+        pol.P[i], pol.Q[i] = p, q
+    return pol
+
+
+def _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_max, out, cuda):
+    """Checks and converts the operands of ``speed_perturb`` / ``speed_perturb_host``: (SpeedArgs, pcm_out, n_out, factor, keep-alive)."""
+    what = "speed_perturb" if cuda else "speed_perturb_host"
+    tokens = tuple(tokens)
+    if len(tokens) > 2:
+        raise ValueError(f"{what}: at most two token tensors, got {len(tokens)}")
+
+    def rows(t, nm, dtype, width=None):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == 2):
+            raise ValueError(f"{what}: {nm} must be a 2-D {dtype} tensor")
+        if t.is_cuda != cuda or t.device != pcm.device:
+            raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor on the device of pcm")
+        if width is not None and tuple(t.shape) != (pcm.shape[0], width):
+            raise ValueError(f"{what}: {nm} must be [{pcm.shape[0]}, {width}], got {tuple(t.shape)}")
+        if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"{what}: {nm} needs unit column stride and rows that do not overlap")
+        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+    if not isinstance(pcm, torch.Tensor):
+        raise ValueError(f"{what}: pcm must be a 2-D torch.int16 tensor")
+    ld_in = rows(pcm, "pcm", torch.int16)
+    B, n = pcm.shape
+    if not (isinstance(n_valid, torch.Tensor) and n_valid.dtype == torch.int32 and n_valid.dim() == 1 and n_valid.numel() == B
+            and n_valid.is_contiguous() and n_valid.device == pcm.device):
+        raise ValueError(f"{what}: n_valid must be a contiguous int32 [{B}] on the device of pcm")
+    if not 1 <= n <= N.SpeedArgs.MAX_N or B > 65535:
+        raise ValueError(f"{what}: pcm [B, N] with B <= 65535 and 1 <= N <= 2^26, got {tuple(pcm.shape)}")
+    a = N.SpeedArgs()
+    a.policy = speed_policy(factors)
+    a.seed, a.first_clip = _u64("seed", seed, what), _u64("first_clip", first_clip, what)
+    if tokens:
+        S = tokens[0].shape[1] if isinstance(tokens[0], torch.Tensor) and tokens[0].dim() == 2 else 0
+        lds = [rows(t, f"tokens[{i}]", torch.int64, S) for i, t in enumerate(tokens)]
+        if S < 1:
+            raise ValueError(f"{what}: tokens must be [B, S] with S >= 1")
+        for nm, v, hi in (("ts_begin", ts_begin, 2 ** 31 - 1), ("ts_max", ts_max, 1 << 24)):
+            if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= hi:
+                raise ValueError(f"{what}: {nm} must be an integer in [0, {hi}], got {v!r}")
+        a.S, a.ts_begin, a.ts_max = S, ts_begin, ts_max
+        a.tokens_a, a.ld_tokens_a = tokens[0].data_ptr(), lds[0]
+        if len(tokens) == 2:
+            a.tokens_b, a.ld_tokens_b = tokens[1].data_ptr(), lds[1]
+    if out is None:
+        out = torch.empty(B, n, dtype=torch.int16, device=pcm.device)
+    ld_out = rows(out, "out", torch.int16, n)
+    if B:
+        lo_i, lo_o = pcm.data_ptr(), out.data_ptr()
+        hi_i, hi_o = lo_i + 2 * ((B - 1) * ld_in + n), lo_o + 2 * ((B - 1) * ld_out + n)
+        if lo_i < hi_o and lo_o < hi_i:
+            raise ValueError(f"{what}: out overlaps pcm (the operator works out of place)")
+    n_out = torch.empty(B, dtype=torch.int32, device=pcm.device)
+    factor = torch.empty(B, dtype=torch.int32, device=pcm.device)
+    a.pcm_in, a.pcm_out, a.n_valid, a.n_out, a.factor_out = pcm.data_ptr(), out.data_ptr(), n_valid.data_ptr(), n_out.data_ptr(), factor.data_ptr()
+    a.ld_in, a.ld_out, a.B, a.N = ld_in, ld_out, B, n
+    return a, out, n_out, factor, (pcm, n_valid, tokens)
+
+
+def speed_perturb(pcm, n_valid, *, factors, seed=0, first_clip=0, tokens=(), ts_begin=50363, ts_max=1500, out=None):
+    """Speed perturbation of int16 PCM on the GPU (include/oasr.h: oasr_speed_perturb; the rule: csrc/speed_core.h): ``pcm`` int16 [B, N]
+    (unit column stride, any row stride >= N), ``n_valid`` int32 [B] = each row's leading non-padding samples.  Row ``b`` draws one of
+    ``factors`` -- (P, Q) pairs, P / Q times faster -- from stream id ``first_clip + b`` (mod 2^64) under ``seed`` (the hash stream of
+    ``spec_augment_``, kind 3) and is resampled by the integer polyphase filter of that ratio; (1, 1), a slow-down that would not fit the row,
+    and a row whose ``n_valid`` is outside [0, N] are copies of the row.  ``tokens``: up to two int64 [B, S] tensors whose timestamp ids
+    ``ts_begin .. ts_begin + ts_max`` are rescaled IN PLACE by the row's ratio.  Returns ``(pcm_out, n_out, factor)``: the new int16 [B, N]
+    (``out``, if given: int16 [B, N] that does not overlap ``pcm``), int32 [B] new lengths, int32 [B] the index taken (-1: fell back to the
+    copy).  One launch on the current stream, no host read; wrong dtypes, shapes or devices raise ValueError before anything is launched."""
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda):
+        raise ValueError("speed_perturb: pcm must be a GPU tensor (speed_perturb_host takes CPU tensors)")
+    a, out, n_out, factor, keep = _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_max, out, True)
+    if a.B:
+        with torch.cuda.device(pcm.device):
+            N.check(N.lib().oasr_speed_perturb(C.byref(a), N.stream_ptr(pcm.device)), "oasr_speed_perturb")
+    return out, n_out, factor
+
+
+def speed_perturb_host(pcm, n_valid, *, factors, seed=0, first_clip=0, tokens=(), ts_begin=50363, ts_max=1500, out=None):
+    """``speed_perturb`` on CPU tensors through the library's host twin (oasr_speed_perturb_host: the same rule from the same text, no GPU).
+    Here the lengths are readable, so an ``n_valid`` outside [0, N] raises ValueError."""
+    if not (isinstance(pcm, torch.Tensor) and not pcm.is_cuda):
+        raise ValueError("speed_perturb_host: pcm must be a CPU tensor")
+    a, out, n_out, factor, keep = _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_max, out, False)
+    if a.B:
+        if int(n_valid.min()) < 0 or int(n_valid.max()) > a.N:
+            raise ValueError(f"speed_perturb_host: n_valid outside [0, N = {a.N}]")
+        N.check(N.lib().oasr_speed_perturb_host(C.byref(a)), "oasr_speed_perturb_host")
+    return out, n_out, factor
+
+
+def speed_plan(factors, seed, clip, n_valid, n):
+    """What ``speed_perturb`` does to stream id ``clip`` with ``n_valid`` of ``n`` samples, from the library's host function
+    (oasr_speed_plan; no GPU): ``(P, Q, n_out, factor)``; factor -1 and P = Q = 1 where a slow-down would not fit the row."""
+    pol = speed_policy(factors)
+    for nm, v in (("n_valid", n_valid), ("N", n)):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise ValueError(f"speed_plan: {nm} must be an integer, got {v!r}")
+    if not (1 <= n <= N.SpeedArgs.MAX_N and 0 <= n_valid <= n):
+        raise ValueError(f"speed_plan: 1 <= N <= 2^26 and 0 <= n_valid <= N, got N = {n}, n_valid = {n_valid}")
+    P, Q, n_out, f = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    N.check(N.lib().oasr_speed_plan(C.byref(pol), _u64("seed", seed, "speed_plan"), _u64("clip", clip, "speed_plan"), n_valid, n, C.byref(P), C.byref(Q), C.byref(n_out),
+                                    C.byref(f)), "oasr_speed_plan")
+    return P.value, Q.value, n_out.value, f.value
+
+
+def speed_table(P, Q):
+    """The library's Q15 tap table of the ratio P / Q (oasr_speed_table; host): ``(T, H)`` with T int32 [Q, 2 H], every row summing to 32768."""
+    pol = speed_policy([(P, Q)])
+    if P == Q:
+        raise ValueError("speed_table: P == Q is the identity (a copy): it has no table")
+    H = C.c_int()
+    N.check(N.lib().oasr_speed_table(pol.P[0], pol.Q[0], None, C.byref(H)), "oasr_speed_table")
+    T = torch.empty(Q, 2 * H.value, dtype=torch.int32)
+    N.check(N.lib().oasr_speed_table(P, Q, N.ptr(T), C.byref(H)), "oasr_speed_table")
+    return T, H.value
 
 
 def pick_tokens(logits, mask=None, mask2=None, want_logprob=True):

@@ -80,6 +80,17 @@ def synth_samples(indices, device, timestamps: bool = False):
     return pcm, ti, ty, tl
 
 
+def n_valid_host(pcm: torch.Tensor) -> int:
+    """One past the last non-zero sample of a HOST int16 clip (0 for silence): its leading non-padding samples, ``ops.speed_perturb``'s n_valid."""
+    nz = pcm.numpy().nonzero()[0]
+    return int(nz[-1]) + 1 if nz.size else 0
+
+
+def _sample_with_length(i, timestamps):
+    it = synth_sample(i, timestamps)
+    return it + (n_valid_host(it[0]),)
+
+
 class SynthLoader:
     """Iterator over micro-batches of the synthetic dataset with background generation -- the role the reference's
     ``DataLoader(num_workers=..., pin_memory=True, prefetch_factor=...)`` plays (train_timestamps.py:640-660): ``workers``
@@ -95,10 +106,12 @@ class SynthLoader:
         self.depth = max(1, depth)
         self.pending = []
         self.last_span = None  # HOST int32 [B]: supervised span of the batch the last __next__ returned (supervised_span_host)
+        self.last_n_valid = None       # DEVICE int32 [B]: leading non-padding samples of each clip of that batch (ops.speed_perturb's n_valid)
+        self.last_n_valid_host = None  # the same on the HOST
         self._fill()
 
     def _submit(self, indices):
-        return [self.pool.submit(synth_sample, int(i), self.timestamps) for i in indices]
+        return [self.pool.submit(_sample_with_length, int(i), self.timestamps) for i in indices]
 
     def _fill(self):
         while len(self.pending) < self.depth:
@@ -127,6 +140,8 @@ class SynthLoader:
         ti = up(torch.stack([it[1] for it in items]))
         ty = up(ty_h)
         tl = up(tl_h)
+        self.last_n_valid_host = torch.tensor([it[4] for it in items], dtype=torch.int32)
+        self.last_n_valid = up(self.last_n_valid_host)
         return pcm, ti, ty, tl
 
     def close(self):

@@ -76,10 +76,15 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     # -- F.cross_entropy(label_smoothing=eps), the usual companion of SpecAugment -- and the z-loss coefficient z >= 0 -- + z * mean(logsumexp^2),
     # PaLM's auxiliary term.  Both 0 = the reference's objective, step and log records unchanged.  With either set, train_loss is the regularised
     # objective and a logging step's record gains train_nll (the plain cross-entropy) and train_lse_sq (mean logsumexp^2), read with the loss.
-    label_smoothing=0.0, z_loss=0.0)
+    label_smoothing=0.0, z_loss=0.0,
+    # Speed perturbation of the int16 clips of every TRAINING micro-batch, ahead of the log-mel (olmoasr_amd/augment.py, csrc/speed.hip): off |
+    # 3way (each clip 0.9, 1.0 or 1.1 times its speed; the transcript's timestamp tokens move along).  --speed_factors replaces the preset's list
+    # of (P, Q) pairs, P / Q times faster.  Drawn from --seed and the step counter (spec_offset), like the SpecAugment masks.
+    speed_perturb="off", speed_factors=None)
 ERROR_COUNTS = ("host", "device")
 SPEC_OVERRIDES = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_time_ratio", "spec_fill")
 SPEC_PRESETS = ("off", "LD", "LB")
+SPEED_PRESETS = ("off", "3way")
 
 
 class Args(dict):
@@ -117,6 +122,27 @@ def spec_policy(args):
         return augment.SpecAugment.preset(args.spec_augment, **over)
     except ValueError as e:
         raise SystemExit(f"--spec_augment={args.spec_augment}: {e}")
+
+
+def speed_policy(args):
+    """--speed_perturb and --speed_factors -> augment.SpeedPerturb, or None for "off"."""
+    if args.speed_perturb not in SPEED_PRESETS:
+        raise SystemExit(f"--speed_perturb must be one of {' | '.join(SPEED_PRESETS)}, got {args.speed_perturb!r}")
+    if args.speed_perturb == "off":
+        if args.speed_factors is not None:
+            raise SystemExit(f"--speed_factors given with --speed_perturb=off: name a policy ({' | '.join(SPEED_PRESETS[1:])}) to override")
+        return None
+    from olmoasr_amd import augment
+    over = {}
+    if args.speed_factors is not None:
+        f = args.speed_factors
+        if not (isinstance(f, (tuple, list)) and f and all(isinstance(pq, (tuple, list)) and len(pq) == 2 for pq in f)):
+            raise SystemExit(f"--speed_factors must be a list of (P, Q) pairs such as '((9,10),(1,1),(11,10))', got {f!r}")
+        over["factors"] = tuple(tuple(pq) for pq in f)
+    try:
+        return augment.SpeedPerturb.preset(args.speed_perturb, **over)
+    except ValueError as e:
+        raise SystemExit(f"--speed_perturb={args.speed_perturb}: {e}")
 
 
 def spec_offset(global_step, micro, accum, world_size, rank, train_batch_size):
@@ -174,6 +200,7 @@ def parse_args(argv=None):
         args.lora_targets = tuple(t.strip() for t in args.lora_targets.split(",") if t.strip())
     args.lora_targets = tuple(args.lora_targets)
     args.spec_policy = spec_policy(args)
+    args.speed_policy = speed_policy(args)
     if args.train_error_counts not in ERROR_COUNTS:
         raise SystemExit(f"--train_error_counts must be one of {' | '.join(ERROR_COUNTS)}, got {args.train_error_counts!r}")
     if args.train_error_counts == "device" and not args.span_backward:
@@ -502,6 +529,10 @@ def main(argv=None):
         print(json.dumps({"event": "spec_augment", "policy": args.spec_augment, "freq_masks": policy.freq_masks, "freq_width": policy.freq_width,
                           "time_masks": policy.time_masks, "time_width": policy.time_width, "time_ratio": policy.time_ratio,
                           "fill": policy.fill if math.isfinite(policy.fill) else str(policy.fill), "seed": spec_seed}), flush=True)
+    speed = args.speed_policy
+    if speed is not None and rank == 0:
+        print(json.dumps({"event": "speed_perturb", "policy": args.speed_perturb, "factors": [list(pq) for pq in speed.factors],
+                          "seed": spec_seed}), flush=True)
     if regularised and rank == 0:
         print(json.dumps({"event": "loss_regularisers", "label_smoothing": args.label_smoothing, "z_loss": args.z_loss}), flush=True)
     device_counts = args.train_error_counts == "device"
@@ -515,6 +546,7 @@ def main(argv=None):
         log_now = ((global_step + 1) % args.train_log_freq) == 0  # gen_pred condition of the reference (:1480)
         preds, tgts = [], []
         spec_cells = 0  # cells masked on this rank in this step: from the host plan, no device read-back
+        speed_counts = [0] * (len(speed.factors) + 1) if speed is not None else None  # this rank's clips per factor (last entry: fell back to the copy): from the host plan too
         for i in range(accum):
             pcm, ti, ty, tl = next(loader)
             cursor += args.train_batch_size  # (position in this rank's epoch order; a short last batch also ends the epoch)
@@ -525,6 +557,11 @@ def main(argv=None):
             # backward to the span and lets the encoder's transpose apply the log-mel floor / scale instead of a second pass over the tensor)
             use_span = bool(args.span_backward) and (device_counts or not log_now)
             want_pred = device_counts and log_now
+            if speed is not None:  # a new pcm tensor; the timestamp ids of ti / ty move in place (the token count, hence the span, stays)
+                first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
+                n_samples = int(pcm.shape[1])
+                pcm, _, _ = speed.apply(pcm, loader.last_n_valid, spec_seed, first, tokens=(ti, ty))
+                speed_counts = [c + d for c, d in zip(speed_counts, speed.factor_counts(spec_seed, first, loader.last_n_valid_host.tolist(), n_samples))]
             if policy is not None:  # masks go on the FINALIZED log-mel, so the span step takes it finalized as well (mel_clip_max=None)
                 mel, clip_max = ops.log_mel(pcm), None
                 first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
@@ -582,6 +619,8 @@ def main(argv=None):
                        "time_per_step": round(time_per_step, 4), "audio_min_per_GPU_second": round(throughput, 3),
                        "audio_sec_per_sec_node": round(throughput * 60 * world_size, 1), "found_inf": found_inf,
                        "spec_masked_cells": spec_cells}
+                if speed is not None:
+                    rec["speed_factor_counts"] = speed_counts
                 if regularised:
                     rec.update(train_nll=parts[0] / world_size, train_lse_sq=parts[1] / world_size)
                 if preds:
