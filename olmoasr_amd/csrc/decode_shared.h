@@ -1,4 +1,4 @@
-// Arithmetic shared by the KV-cached decoder step's engines (multi-launch: decode_proj.hip + attention.hip::attn_decode_kernel; one launch:
+// Arithmetic shared by the KV-cached decoder step's engines (multi-launch: decode_proj.hip + attention_fwd.hip::attn_decode_kernel; one launch:
 // decode_xcd.hip).  The engines must agree to the last bit (tests/test_gpu_decode_step.py), so every expression whose fp32 rounding
 // depends on how hipcc contracts it (a * b + c -> fma) lives HERE, once, and is inlined into each engine: same source expression,
 // same contraction, same result.  Reference semantics: TextDecoder.forward for one new token with the kv_cache hooks,

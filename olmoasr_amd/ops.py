@@ -243,7 +243,7 @@ def attention_fwd_rows(qc, kc, vc, B, H, Tq, Tk, q_rows, k_rows=None, kv_len=Non
 
 
 def attention_bwd_rows(qc, kc, vc, oc, lse, doc, B, H, Tq, Tk, q_rows, k_rows=None, q_span=None, kv_len=None, causal=False, o_lo=None,
-                       dq_colsum=None, dv_colsum=None, fill=None, q_blocks=None, scratch_fill=None):
+                       dq_colsum=None, dv_colsum=None, fill=None, q_blocks=None, scratch_fill=None, qtile_flags=None):
     """attention_bwd on chunked token rows.  Gradients are allocated with the operands' strides and pre-filled with ``fill`` (e.g. NaN)
     so that a test can see which rows the kernels left untouched.  q_blocks: ``span_block_tables`` of the spans in q_span (compact
     grids); scratch_fill: what the bias gradients' scratch rows hold on entry (nothing may depend on it)."""
@@ -261,6 +261,7 @@ def attention_bwd_rows(qc, kc, vc, oc, lse, doc, B, H, Tq, Tk, q_rows, k_rows=No
     a.q_span = q_span.data_ptr() if q_span is not None else None
     a.dq_colsum = dq_colsum.data_ptr() if dq_colsum is not None else None
     a.dv_colsum = dv_colsum.data_ptr() if dv_colsum is not None else None
+    a.qtile_flags = qtile_flags.data_ptr() if qtile_flags is not None else None  # (as in attention_bwd)
     scratch = None
     if dq_colsum is not None or dv_colsum is not None:
         scratch = torch.empty(B * ((Tq + 127) // 128 + (Tk + 127) // 128) * H * 64, device=qc.device, dtype=torch.float32)

@@ -41,7 +41,7 @@ BF = torch.bfloat16
 F64 = torch.float64
 SCALE = 0.125
 LOG2E = 1.4426950408889634
-RESCALE_THR = 8.0            # attention.hip: the forward's lazy-rescale threshold (log2 units)
+RESCALE_THR = 8.0            # attention_fwd.hip: the forward's lazy-rescale threshold (log2 units)
 EPS_BF = 2.0 ** -8           # unit roundoff of bf16: 8 significant bits, round to nearest (half an ulp of [1, 2) is 2^-8)
 EPS_F32 = 2.0 ** -24
 SCENARIOS = ("masked", "phantom", "plateau", "onehot", "uniform", "offset")
