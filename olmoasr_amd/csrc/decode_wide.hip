@@ -924,11 +924,13 @@ __global__ __launch_bounds__(WT) void decode_wide_kernel(WArgs a) {
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 size_t decode_wide_part_floats(int H) { return (size_t)H * WNS * 66; }
 
-bool decode_wide_supports(int d, int H, int Te, int S_max, int L, int M, int nwg) {
+// V: the rows of the tied logits projection as the last phase deals them out (the token embedding's rows, unpadded: logits_phase's RW)
+bool decode_wide_supports(int d, int H, int Te, int S_max, int L, int M, int nwg, int V) {
   if (!(M == 1 && L >= 1 && L <= WMAXL && d % 64 == 0 && d == H * 64 && d <= WMAXD && H <= 32 && S_max >= 1 && S_max <= WNG * WSK && Te >= 1 &&
         (Te + WNS - 1) / WNS <= WNG * WCK && nwg >= 64 && nwg <= WMAXWG && nwg % 4 == 0 && H * WNS <= nwg))
     return false;
   if (2 * ((d + 2 * nwg - 1) / (2 * nwg)) > WPKR) return false;  // an N = d projection's rows per workgroup fill one packet
+  if (V < 1 || (V + nwg - 1) / nwg > 64 * WC) return false;       // the logits phase parks a wave's rows of the workgroup's run in its 64 lanes
   {
     const int R0 = 2 * ((3 * d + 2 * nwg - 1) / (2 * nwg)), NP0 = (R0 + 5) / 6;  // the q | k | v row: <= 3 packets per workgroup, <= 16 packets per head and range
     if (NP0 > 3 || ((63 + R0 - 1) / R0 + 1) * NP0 > 16 || H * 11 > WPKS) return false;
@@ -950,7 +952,7 @@ bool decode_wide_supports(int d, int H, int Te, int S_max, int L, int M, int nwg
 }
 
 int launch_decode_wide(const DecodeXcdArgs& h, hipStream_t s) {
-  OASR_REQUIRE(decode_wide_supports(h.d, h.H, h.Te, h.S_max, h.L, h.M, h.team), "decode_wide: unsupported shape");
+  OASR_REQUIRE(decode_wide_supports(h.d, h.H, h.Te, h.S_max, h.L, h.M, h.team, h.logits_out ? h.V : 1), "decode_wide: unsupported shape");
   OASR_REQUIRE(h.pos >= 0 && h.pos < h.S_max && h.layer_offsets, "decode_wide: bad launch shape");
   WArgs a;
   a.wflat = h.wflat, a.params = h.params, a.aux = h.aux, a.cache = h.cache, a.cache_lstride = h.cache_lstride;
@@ -984,7 +986,9 @@ int launch_decode_wide(const DecodeXcdArgs& h, hipStream_t s) {
 // Test hooks (include/oasr_testing.h): the host-side view of the work split -- whether a shape runs on this engine, and which (row, K span) units compute
 // wave `wave` (1 .. 8) of workgroup `wg` is dealt for an [N x K] projection: out[2 i] = row (absolute), out[2 i + 1] = span; returns the count, or -1
 // past the instantiation's unrolled bound (wmu).  tests/test_native_abi.py checks that the units of all waves tile the matrix exactly once.
-extern "C" int oasr_wide_supports_debug(int d, int H, int Te, int S_max, int L, int M, int nwg) { return decode_wide_supports(d, H, Te, S_max, L, M, nwg) ? 1 : 0; }
+extern "C" int oasr_wide_supports_debug(int d, int H, int Te, int S_max, int L, int M, int nwg, int V) {
+  return decode_wide_supports(d, H, Te, S_max, L, M, nwg, V) ? 1 : 0;
+}
 extern "C" int oasr_wide_plan_debug(int d, int nwg, int N, int K, int wg, int wave, int* out, int max_units) {
   WGemv p{};
   p.N = N, p.K = K, p.R = 2 * ((N + 2 * nwg - 1) / (2 * nwg));

@@ -60,7 +60,7 @@ int pick_step_engine(oasr_ctx* c, int B, StepEngine& e) {
   }
   const int nwg = c->n_cu >= 256 ? 256 : (c->n_cu > 0 ? c->n_cu & ~3 : 0);
   const bool one_launch = !c->xcd_disabled && !c->xcd_offsets.empty();
-  e.wide = (mode == -1 || mode == 5) && B == 1 && one_launch && decode_wide_supports(d, c->H, c->Te, S_max, c->L_dec, B, nwg);
+  e.wide = (mode == -1 || mode == 5) && B == 1 && one_launch && decode_wide_supports(d, c->H, c->Te, S_max, c->L_dec, B, nwg, c->V);
   e.team = !e.wide && ((mode == -1 && B == 1) || mode >= 2) && one_launch && decode_xcd_supports(d, c->H, c->Te, S_max, c->L_dec, B) &&
            decode_xcd_offsets_ok(c->xcd_offsets.data(), c->xcd_lstride, (long)kv_layer_elems(c, B), d, c->Te, c->L_dec, B);
   e.nwg = e.wide ? nwg : (mode == 4 ? 64 : 32);

@@ -21,16 +21,19 @@ def _tail(state):
     return state["cache"][-N.KV_TAIL_BYTES:].view(torch.int32)
 
 
-def _steps(net, xa, toks, mode):
+def _steps(net, xa, toks, mode, info=None):
     """mode: 1 = LayerNorm folded into the projections; 0 = separate LayerNorm / logits-widening kernels; 2 / 3 / 4 = one launch for the
     whole decoder stack (one XCD / 32 / 64 workgroups spread), where the shape allows it (else the call falls back to the folded path);
-    5 = the chip-wide one-launch engine (one sequence; more sequences: as 2); -1 = the library's default."""
+    5 = the chip-wide one-launch engine (one sequence; more sequences: as 2); -1 = the library's default.
+    ``info``: a dict that receives the window's state (``state``: its cache carries the engines' control tail) and what kv_cache_check said (``ok``)."""
     from olmoasr_amd import _native as N
     N.lib().oasr_decode_set_ln_fold(mode)
     try:
         st = net.kv_cache_begin(xa)
         out = [net.kv_cache_step(st, toks[:, p]) for p in range(toks.shape[1])]
-        net.kv_cache_check(st)
+        ok = net.kv_cache_check(st)
+        if info is not None:
+            info.update(state=st, ok=ok)
         return torch.stack(out, 1)
     finally:
         N.lib().oasr_decode_set_ln_fold(-1)

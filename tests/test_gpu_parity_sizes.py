@@ -15,6 +15,8 @@ import os
 import pytest
 import torch
 
+from bf16_ulp import bf16_ulp_report
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF = torch.bfloat16
@@ -22,19 +24,6 @@ BF = torch.bfloat16
 # medium (the benchmarked configuration) is compared DIRECTLY with the CPU oracle at B = 4 -- a batch, not a single clip -- so the chain
 # "medium B = 128 == sum of 128 single-clip HIP steps" (test_gpu_bench_shapes.py) + "single clip == oracle" has a batched link of its own
 SIZES = [("base", 2), ("small", 2), ("medium", 4), ("large", 1)]  # large = BASELINE configs[3] (large-v2 shares its dims)
-
-
-def bf16_ulp_report(native, mirror, valid, tag):
-    """native (bf16 engine) vs the oracle's autocast MIRROR (same rounding points, CPU accumulation order), in bf16 ulps of the logit
-    scale: ulp = 2^(floor(log2 max|logit|) - 7), the spacing of bf16 at the largest logit.  Returns (fraction within 2 ulp, max in ulp)."""
-    import math
-    scale = float(mirror[valid].abs().max())
-    ulp = 2.0 ** (math.floor(math.log2(scale)) - 7)
-    d = (native - mirror).abs()[valid] / ulp
-    hist = [float((d <= k).float().mean()) for k in (0.5, 1, 2, 4)]
-    print(f"   [{tag}] bf16 engine vs autocast mirror, valid logits: scale {scale:.2f} -> ulp {ulp:.5f}; within 0.5/1/2/4 ulp: "
-          f"{hist[0]:.5f} {hist[1]:.5f} {hist[2]:.5f} {hist[3]:.5f}; max {float(d.max()):.2f} ulp; mean {float(d.mean()):.3f} ulp")
-    return hist[2], float(d.max())
 
 
 def _dims(mo_dims):

@@ -291,7 +291,7 @@ def test_chip_wide_step_engine_work_split(native):
     lib = native.lib()
     buf = (C.c_int * 64)()
     for name, d, H, L in (("tiny", 384, 6, 4), ("base", 512, 8, 6), ("small", 768, 12, 12), ("medium", 1024, 16, 24), ("large", 1280, 20, 32)):
-        assert lib.oasr_wide_supports_debug(d, H, 1500, 448, L, 1, 256) == 1, name
+        assert lib.oasr_wide_supports_debug(d, H, 1500, 448, L, 1, 256, 51865) == 1, name
         for N, K in ((3 * d, d), (d, d), (4 * d, d), (d, 4 * d)):
             seen = {}
             for wg in range(256):
@@ -305,8 +305,34 @@ def test_chip_wide_step_engine_work_split(native):
             spans = (K // 8 + 63) // 64
             assert len(seen) == N * spans and all(0 <= r < N and 0 <= j < spans for r, j in seen), (name, N, K, len(seen))
     # shapes the engine must decline: more than one sequence, a context past 448 positions, too few workgroups, a width whose rows do not fit a packet
-    assert lib.oasr_wide_supports_debug(1024, 16, 1500, 448, 24, 2, 256) == 0
-    assert lib.oasr_wide_supports_debug(1024, 16, 1500, 512, 24, 1, 256) == 0
-    assert lib.oasr_wide_supports_debug(1024, 16, 1500, 448, 24, 1, 32) == 0
-    assert lib.oasr_wide_supports_debug(2048, 32, 1500, 448, 24, 1, 256) == 0
-    assert lib.oasr_wide_supports_debug(1024, 16, 2000, 448, 24, 1, 256) == 0  # (an audio context past 8 x 216 keys)
+    assert lib.oasr_wide_supports_debug(1024, 16, 1500, 448, 24, 2, 256, 51865) == 0
+    assert lib.oasr_wide_supports_debug(1024, 16, 1500, 512, 24, 1, 256, 51865) == 0
+    assert lib.oasr_wide_supports_debug(1024, 16, 1500, 448, 24, 1, 32, 51865) == 0
+    assert lib.oasr_wide_supports_debug(2048, 32, 1500, 448, 24, 1, 256, 51865) == 0
+    assert lib.oasr_wide_supports_debug(1024, 16, 2000, 448, 24, 1, 256, 51865) == 0  # (an audio context past 8 x 216 keys)
+
+
+def test_chip_wide_step_engine_declines_a_vocabulary_its_logits_phase_cannot_hold(native):
+    """The chip-wide engine's last phase deals the V rows of the tied logits projection out in runs of ceil(V / nwg) per workgroup and parks a
+    compute wave's rows in its 64 lanes: at most 64 x 8 = 512 rows per workgroup (launch_decode_wide's guard).  decode_wide_supports must know
+    that -- on a device with fewer than 102 CUs (nwg = n_cu & ~3) it once said yes for V = 51865, the engine was picked and every one-sequence
+    step failed in the launcher instead of falling back to the team / multi-launch step."""
+    from oracle import model_oracle as mo
+    lib = native.lib()
+    V = 51865  # the training layout: n_vocab + the pad row
+    assert lib.oasr_wide_supports_debug(384, 6, 1500, 448, 4, 1, 64, V) == 0
+    assert -(-V // 512) == 102  # the boundary; nwg is a multiple of 4
+    assert lib.oasr_wide_supports_debug(384, 6, 1500, 448, 4, 1, 104, V) == 1
+    assert lib.oasr_wide_supports_debug(384, 6, 1500, 448, 4, 1, 100, V) == 0
+    assert lib.oasr_wide_supports_debug(384, 6, 1500, 448, 4, 1, 64, 512 * 64) == 1
+    assert lib.oasr_wide_supports_debug(384, 6, 1500, 448, 4, 1, 64, 512 * 64 + 1) == 0
+    assert lib.oasr_wide_supports_debug(384, 6, 1500, 448, 4, 1, 256, 0) == 0
+    # supports() == 1 implies the launcher's logits condition, for every workgroup count a device can give and both head layouts
+    said_yes = 0
+    for name, dims in mo.VARIANTS.items():
+        for rows in (dims.n_vocab, dims.n_vocab + 1):
+            for nwg in range(64, 257, 4):
+                if lib.oasr_wide_supports_debug(dims.n_text_state, dims.n_text_head, dims.n_audio_ctx, dims.n_text_ctx, dims.n_text_layer, 1, nwg, rows):
+                    said_yes += 1
+                    assert -(-rows // nwg) <= 64 * 8, (name, rows, nwg)
+    assert said_yes > 0
