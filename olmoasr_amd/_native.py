@@ -84,12 +84,17 @@ class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
 
 
 DTW_MAX_N, DTW_MAX_M = 448, 1500  # csrc/dtw_core.h: the model's n_text_ctx / n_audio_ctx
-# The word-timestamp operators (oasr_alignment_matrix, oasr_dtw, oasr_test_dtw_host) add entry points without a new ABI generation: a library built before them is refused by the oasr_sizeof_align_args check in lib().
-# SpecAugment (oasr_spec_augment, oasr_spec_augment_plan) came the same way: entry points only, a stale library refused by the oasr_sizeof_specaug check in lib().
-# The query-block tables of oasr_attn_args (qblk128 / qblk256 / n128 / n256: compact grids of the span-limited attention launches) grow the struct at its end under the same version number: a library built without them is refused by the oasr_sizeof_attn_args check in lib().
-# Token error counts (oasr_edit_counts, oasr_edit_counts_host) and the prediction kernel's hook (oasr_test_argmax_rows) likewise: a stale library is refused by the oasr_sizeof_edit_args check in lib().
-# Label smoothing / z-loss (oasr_train_step_args.label_smoothing, z_loss, loss_parts_out, loss_parts_rows; oasr_cross_entropy_ex) grow the step's struct at its end and add one entry point under the same version number: a library built without them is refused by the oasr_sizeof_train_step_args check in lib().
-# Speed perturbation (oasr_speed_perturb, oasr_speed_perturb_host, oasr_speed_plan, oasr_speed_table) likewise: entry points only, a stale library refused by the oasr_sizeof_speed / oasr_sizeof_speed_args checks in lib().
+# (sizeof entry, struct) that lib() holds a library to.  Features that only add entry points, or grow a struct at its end, keep
+# ABI_VERSION: a library built before them lacks the sizeof entry or answers another size, and is refused all the same.
+STRUCT_SIZES = [
+    ("oasr_sizeof_attn_args", AttnArgs),  # checked before anything is declared; last grown by the query-block tables (qblk128 .. n256)
+    ("oasr_sizeof_align_args", AlignArgs),  # came with the word-timestamp operators (oasr_alignment_matrix, oasr_dtw)
+    ("oasr_sizeof_specaug", SpecAug),  # came with oasr_spec_augment
+    ("oasr_sizeof_edit_args", EditArgs),  # came with oasr_edit_counts and oasr_test_argmax_rows
+    ("oasr_sizeof_speed", Speed),  # came with oasr_speed_perturb
+    ("oasr_sizeof_speed_args", SpeedArgs),
+    ("oasr_sizeof_train_step_args", TrainStepArgs),  # last grown by label_smoothing / z_loss / loss_parts_*
+]
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
@@ -225,6 +230,13 @@ def _declare(lib):
 EXPORTS = None
 
 
+def _check_struct_size(handle, entry, struct):
+    size = getattr(handle, entry, lambda: None)()  # (a library from before the struct was passed lacks the entry)
+    if size != C.sizeof(struct):
+        raise NativeError(f"{LIB_PATH}: {entry} answers {size} bytes, this binding's {struct.__name__} has {C.sizeof(struct)} "
+                          "-- rebuild (__graft_entry__.build())")
+
+
 def lib():
     """Loads liboasr.so (once).  Raises NativeError when it is missing -- build it with __graft_entry__.build()."""
     global _lib, EXPORTS
@@ -238,33 +250,17 @@ def lib():
             raise NativeError(f"cannot load {LIB_PATH}: {e}") from e
         handle, _lib = _lib, None  # published only once it has passed every check below (a failed load must not leave a half-declared CDLL behind)
         # a library of another ABI generation reads structs of a different size through the same pointers, and may lack symbols this
-        # binding declares: check the version FIRST (oasr_version exists in every generation), then the struct size, then declare
-        vfn = getattr(handle, "oasr_version", None)
-        ver = int(vfn()) if vfn is not None else None
-        sfn = getattr(handle, "oasr_sizeof_attn_args", None)
-        size = int(sfn()) if sfn is not None else None
-        if ver != ABI_VERSION or size != C.sizeof(AttnArgs):
-            raise NativeError(f"{LIB_PATH}: ABI version {ver} / oasr_attn_args of {size} bytes, this binding is written for version "
-                              f"{ABI_VERSION} / {C.sizeof(AttnArgs)} bytes -- rebuild (__graft_entry__.build())")
+        # binding declares: check the version FIRST (oasr_version exists in every generation), then the first struct size, then declare
+        ver = getattr(handle, "oasr_version", lambda: None)()
+        if ver != ABI_VERSION:
+            raise NativeError(f"{LIB_PATH}: ABI version {ver}, this binding is written for version {ABI_VERSION} -- rebuild (__graft_entry__.build())")
+        _check_struct_size(handle, *STRUCT_SIZES[0])
         try:
             exports = _declare(handle)
         except AttributeError as e:
             raise NativeError(f"{LIB_PATH} (ABI {ver}) lacks an entry point this binding declares: {e} -- rebuild (__graft_entry__.build())") from e
-        if int(handle.oasr_sizeof_align_args()) != C.sizeof(AlignArgs):
-            raise NativeError(f"{LIB_PATH}: oasr_align_args of {int(handle.oasr_sizeof_align_args())} bytes, this binding passes "
-                              f"{C.sizeof(AlignArgs)} -- rebuild (__graft_entry__.build())")
-        if int(handle.oasr_sizeof_specaug()) != C.sizeof(SpecAug):
-            raise NativeError(f"{LIB_PATH}: oasr_specaug of {int(handle.oasr_sizeof_specaug())} bytes, this binding passes "
-                              f"{C.sizeof(SpecAug)} -- rebuild (__graft_entry__.build())")
-        if int(handle.oasr_sizeof_edit_args()) != C.sizeof(EditArgs):
-            raise NativeError(f"{LIB_PATH}: oasr_edit_args of {int(handle.oasr_sizeof_edit_args())} bytes, this binding passes "
-                              f"{C.sizeof(EditArgs)} -- rebuild (__graft_entry__.build())")
-        if int(handle.oasr_sizeof_speed()) != C.sizeof(Speed) or int(handle.oasr_sizeof_speed_args()) != C.sizeof(SpeedArgs):
-            raise NativeError(f"{LIB_PATH}: oasr_speed / oasr_speed_args of {int(handle.oasr_sizeof_speed())} / {int(handle.oasr_sizeof_speed_args())} "
-                              f"bytes, this binding passes {C.sizeof(Speed)} / {C.sizeof(SpeedArgs)} -- rebuild (__graft_entry__.build())")
-        if int(handle.oasr_sizeof_train_step_args()) != C.sizeof(TrainStepArgs):
-            raise NativeError(f"{LIB_PATH}: oasr_train_step_args of {int(handle.oasr_sizeof_train_step_args())} bytes, this binding passes "
-                              f"{C.sizeof(TrainStepArgs)} -- rebuild (__graft_entry__.build())")
+        for row in STRUCT_SIZES[1:]:
+            _check_struct_size(handle, *row)
         _lib, EXPORTS = handle, exports
     return _lib
 
@@ -292,6 +288,42 @@ def ptr(t):
 
 def stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+STREAM = object()  # call(): stands for the current stream of the call's device
+_Tensor = torch.Tensor
+
+
+def call(name, *args, device=None):
+    """``lib().<name>(*args)`` for an entry that returns a status code, checked under the entry's own name.  A tensor argument becomes
+    its address (None stays NULL), ``STREAM`` the current stream of the call's device; everything else -- numbers, ctypes values,
+    ``C.byref(struct)`` -- passes through.  The call's device is ``device`` (a tensor's ``.device``: entries whose addresses travel inside
+    a struct give it) or else the device of the CUDA tensor arguments, which must agree; the entry runs with that device current.  CPU
+    tensors pass as addresses and name no device (the ``*_host`` entries, ``span_host``).  No synchronisation and no allocation."""
+    fn = getattr(_lib or lib(), name)
+    argv, stream_at = [], -1
+    for a in args:
+        if isinstance(a, _Tensor):
+            if a.is_cuda:
+                if device is None:
+                    device = a.device
+                elif a.device != device:
+                    raise NativeError(f"{name}: arguments on {device} and on {a.device} -- one call, one device (nothing was launched)")
+            a = a.data_ptr()
+        elif a is STREAM:
+            stream_at = len(argv)
+        argv.append(a)
+    if device is None:
+        if stream_at >= 0:
+            raise NativeError(f"{name}: a stream was asked for, but no argument names a device")
+        rc = fn(*argv)
+    else:
+        with torch.cuda.device(device):
+            if stream_at >= 0:
+                argv[stream_at] = torch.cuda.current_stream().cuda_stream
+            rc = fn(*argv)
+    if rc != 0:
+        check(rc, name)
 
 
 def require_gpu(t, name="tensor"):

@@ -84,7 +84,7 @@ def mel_filters(device=None, n_mels: int = 80) -> torch.Tensor:
     if n_mels != 80:
         raise N.NativeError("only n_mels=80 is supported (every OLMoASR variant, olmoasr/config/model_dims.py:28-89)")
     out = np.empty((80, 201), dtype=np.float32)
-    N.check(N.lib().oasr_mel_filterbank(out.ctypes.data), "oasr_mel_filterbank")
+    N.call("oasr_mel_filterbank", out.ctypes.data)
     t = torch.from_numpy(out)
     return t.to(device) if device is not None else t
 

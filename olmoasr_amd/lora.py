@@ -140,8 +140,7 @@ def merge_lora(model) -> None:
     if not lora_modules(model):
         raise N.NativeError("merge_lora: the model has no LoRA adapters")
     names = lora_modules(model)
-    with torch.cuda.device(model.device):
-        N.check(N.lib().oasr_lora_merge(model._ctx, N.stream_ptr()), "oasr_lora_merge")
+    N.call("oasr_lora_merge", model._ctx, N.STREAM, device=model.device)
     with torch.no_grad():
         model._swap_context((), 0, 0.0, None)
     for t in names:

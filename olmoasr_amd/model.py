@@ -143,6 +143,37 @@ def _text_len_or_full(text_len: Optional[Tensor], B: int, S: int, device) -> Ten
     return torch.full((B,), S, dtype=torch.int32, device=device) if text_len is None else text_len.to(torch.int32).contiguous()
 
 
+class _Slot:
+    """One uint8 workspace and the generation of what it holds.  Every plan of the engine starts at the workspace's base, so whoever takes
+    the buffer overwrites what the last taker left there -- saved activations and index tables alike.  A forward that leaves activations
+    behind for its backward keeps ``gen`` as its lease; any later ``take``, ``drop`` or ``redeem`` voids it."""
+
+    def __init__(self):
+        self.buf, self.gen = None, 0
+
+    def take(self, need, device):
+        """A buffer of at least ``need`` bytes, grown if it is too small (the old one is released first: the two never coexist)."""
+        self.gen += 1
+        if self.buf is None or self.buf.numel() < need:
+            self.buf = None
+            self.buf = torch.empty(need, dtype=torch.uint8, device=device)
+        return self.buf
+
+    def redeem(self, gen, what):
+        """The buffer as the forward with lease ``gen`` left it, for that forward's backward -- once."""
+        if gen != self.gen or self.buf is None:
+            raise RuntimeError(f"{what} backward: the activations of this forward are gone -- the engine keeps ONE forward's activations per "
+                               "workspace, and a later call that uses the same workspace, a previous backward through this graph, or "
+                               "freeing / moving the workspace took them; run forward and backward in pairs (gradient accumulation: "
+                               "forward/backward per micro-batch)")
+        self.gen += 1
+        return self.buf
+
+    def drop(self):
+        self.gen += 1
+        self.buf = None
+
+
 class _TrainStep(torch.autograd.Function):
     """OLMoASR.forward with a grad_fn: oasr_train_fwd keeps the saved activations in the model's workspace, backward hands
     d(loss)/d(logits) to oasr_train_bwd, which accumulates into the flat gradient arena (= every ``p.grad``).  Gradients do not
@@ -160,38 +191,25 @@ class _TrainStep(torch.autograd.Function):
         mel = mel.float().contiguous()
         tokens = tokens.to(torch.int64).contiguous()
         text_len = _text_len_or_full(text_len, B, S, mel.device)
-        ws = model._ws(B, S, 1)
+        ws = model._ws(B, S, N.MODE_TRAIN)
         logits = torch.empty(B, S, model._n_rows, device=mel.device, dtype=torch.float32)
-        with torch.cuda.device(mel.device):
-            N.check(N.lib().oasr_train_fwd(model._ctx, N.ptr(mel), N.ptr(tokens), N.ptr(text_len), B, S, N.ptr(logits), N.ptr(ws), ws.numel(),
-                                           N.stream_ptr()), "oasr_train_fwd")
-        model._autograd_gen = getattr(model, "_autograd_gen", 0) + 1
-        ctx.model, ctx.gen = model, model._autograd_gen
+        N.call("oasr_train_fwd", model._ctx, mel, tokens, text_len, B, S, logits, ws, ws.numel(), N.STREAM)
+        ctx.model, ctx.gen = model, model._slots["main"].gen
         ctx.save_for_backward(tokens, text_len)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         model = ctx.model
-        if ctx.gen != model._autograd_gen:
-            raise RuntimeError("OLMoASR.backward: the activations of this forward are gone -- the engine keeps ONE forward's activations "
-                               "(in the model's workspace) and a later training-mode forward or a previous backward through this graph "
-                               "used them; run forward and backward in pairs (gradient accumulation: forward/backward per micro-batch)")
+        ws = model._slots["main"].redeem(ctx.gen, "OLMoASR.forward")
         tokens, text_len = ctx.saved_tensors
         B, S = tokens.shape
         dlogits = dlogits.float().contiguous()
-        ws = model._ws(B, S, 1)
-        seg = getattr(model, "_autograd_segment_events", None)
-        ev = None
-        if seg is not None:
-            ev = (C.c_void_p * len(seg))(*[e.cuda_event for e in seg])
-        with torch.cuda.device(dlogits.device):
-            N.check(N.lib().oasr_train_bwd(model._ctx, N.ptr(tokens), N.ptr(text_len), N.ptr(dlogits), B, S, ev, N.ptr(ws), ws.numel(),
-                                           N.stream_ptr()), "oasr_train_bwd")
-        model._autograd_gen += 1  # consumed
-        post = getattr(model, "_autograd_post_backward", None)
-        if post is not None:
-            post()  # ddp.DistributedDataParallel: bucketed all-reduce of the arena, overlapped through the segment events
+        seg = model._autograd_segment_events
+        ev = None if seg is None else (C.c_void_p * len(seg))(*[e.cuda_event for e in seg])
+        N.call("oasr_train_bwd", model._ctx, tokens, text_len, dlogits, B, S, ev, ws, ws.numel(), N.STREAM)
+        if model._autograd_post_backward is not None:
+            model._autograd_post_backward()  # ddp.DistributedDataParallel: bucketed all-reduce of the arena, overlapped through the segment events
         return None, None, None, None, None
 
 
@@ -206,22 +224,18 @@ class _EncoderStage(torch.autograd.Function):
         mel_c = mel.detach().float().contiguous()
         ws = model._stage_ws("enc", B, 1)
         xa = torch.empty(B, model.dims.n_audio_ctx, model.dims.n_audio_state, device=mel.device, dtype=model._act_dtype)
-        with torch.cuda.device(mel.device):
-            N.check(N.lib().oasr_train_encode(model._ctx, N.ptr(mel_c), B, N.ptr(xa), N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_train_encode")
-        ctx.model, ctx.gen, ctx.B = model, model._stage_forward("enc"), B
+        N.call("oasr_train_encode", model._ctx, mel_c, B, xa, ws, ws.numel(), N.STREAM)
+        ctx.model, ctx.gen, ctx.B = model, model._slots["enc"].gen, B
         return xa
 
     @staticmethod
     def backward(ctx, dxa):
         model, B = ctx.model, ctx.B
-        ws = model._stage_backward_ws("enc", ctx.gen, "model.encoder")
+        ws = model._slots["enc"].redeem(ctx.gen, "model.encoder")
         dxa = dxa.to(model._act_dtype).contiguous()
         dmel = (torch.empty(B, model.dims.n_mels, 2 * model.dims.n_audio_ctx, device=dxa.device, dtype=torch.float32)
                 if ctx.needs_input_grad[2] else None)
-        with torch.cuda.device(dxa.device):
-            N.check(N.lib().oasr_train_encode_bwd(model._ctx, N.ptr(dxa), B, N.ptr(dmel), N.ptr(ws), ws.numel(), N.stream_ptr()),
-                    "oasr_train_encode_bwd")
-        model._stage_gen["enc"] += 1  # consumed
+        N.call("oasr_train_encode_bwd", model._ctx, dxa, B, dmel, ws, ws.numel(), N.STREAM)
         return None, None, dmel
 
 
@@ -238,26 +252,21 @@ class _DecoderStage(torch.autograd.Function):
         text_len = _text_len_or_full(text_len, B, S, tokens.device)
         ws = model._stage_ws("dec", B, S)
         logits = torch.empty(B, S, model._n_rows, device=tokens.device, dtype=torch.float32)
-        with torch.cuda.device(tokens.device):
-            N.check(N.lib().oasr_train_decode(model._ctx, N.ptr(tokens), N.ptr(xa_c), N.ptr(text_len), B, S, N.ptr(logits), N.ptr(ws),
-                                              ws.numel(), N.stream_ptr()), "oasr_train_decode")
-        ctx.model, ctx.gen = model, model._stage_forward("dec")
+        N.call("oasr_train_decode", model._ctx, tokens, xa_c, text_len, B, S, logits, ws, ws.numel(), N.STREAM)
+        ctx.model, ctx.gen = model, model._slots["dec"].gen
         ctx.save_for_backward(tokens, text_len)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         model = ctx.model
-        ws = model._stage_backward_ws("dec", ctx.gen, "model.decoder")
+        ws = model._slots["dec"].redeem(ctx.gen, "model.decoder")
         tokens, text_len = ctx.saved_tensors
         B, S = tokens.shape
         dlogits = dlogits.float().contiguous()
         dxa = (torch.empty(B, model.dims.n_audio_ctx, model.dims.n_audio_state, device=dlogits.device, dtype=model._act_dtype)
                if ctx.needs_input_grad[3] else None)
-        with torch.cuda.device(dlogits.device):
-            N.check(N.lib().oasr_train_decode_bwd(model._ctx, N.ptr(tokens), N.ptr(text_len), N.ptr(dlogits), B, S, N.ptr(dxa), N.ptr(ws),
-                                                  ws.numel(), N.stream_ptr()), "oasr_train_decode_bwd")
-        model._stage_gen["dec"] += 1  # consumed
+        N.call("oasr_train_decode_bwd", model._ctx, tokens, text_len, dlogits, B, S, dxa, ws, ws.numel(), N.STREAM)
         return None, None, None, dxa, None
 
 
@@ -293,10 +302,8 @@ class Linear(_ParamModule):
         a = _rows_bf16(x)
         if "lora_A" in self._parameters:  # a LoRA-adapted Linear computes with W0 + s * B . A (olmoasr_amd.lora), merged as the engine merges it
             w = torch.empty(self.out_features, self.in_features, device=a.device, dtype=torch.bfloat16)
-            with torch.cuda.device(a.device):
-                N.check(N.lib().oasr_lora_merge_op(N.ptr(self.weight.detach()), N.ptr(self.lora_A.detach()), N.ptr(self.lora_B.detach()),
-                                                   self.out_features, self.in_features, self.lora_A.shape[0], float(self.lora_scale), 0,
-                                                   N.ptr(w), N.stream_ptr()), "oasr_lora_merge_op")
+            N.call("oasr_lora_merge_op", self.weight, self.lora_A, self.lora_B, self.out_features, self.in_features, self.lora_A.shape[0],
+                   float(self.lora_scale), 0, w, N.STREAM)
         else:
             w = ops.cast_bf16(self.weight.detach())
         out = torch.empty(a.shape[0], self.out_features, device=a.device, dtype=torch.bfloat16)
@@ -554,9 +561,13 @@ class OLMoASR(nn.Module):
         self._flat = flat.to(device)
         self._gflat = None
         self._shadow = torch.zeros(lib.oasr_shadow_bytes(self._ctx), dtype=torch.uint8, device=device)
-        self._workspace = None
-        self._stage_workspace = {}  # "enc" / "dec": the staged autograd entries' own workspaces (allocated on first use)
-        self._stage_gen = {"enc": 0, "dec": 0}
+        # workspaces: "main" (``_workspace``) of forward / embed_audio / logits / loss_and_backward, "enc" / "dec" of the staged autograd entries
+        self._slots = {"main": _Slot(), "enc": _Slot(), "dec": _Slot()}
+        self._opt_state = None  # (exp_avg, exp_avg_sq) arenas with _opt_stats / _opt_scratch: init_optimizer_state
+        self._opt_stats = self._opt_scratch = None
+        self._autograd_segment_events = None  # ddp.DistributedDataParallel: the events oasr_train_bwd records per gradient segment
+        self._autograd_post_backward = None  # ddp.DistributedDataParallel: runs after _TrainStep's backward
+        self._reset_derived()
         import weakref
         for sub in (self.encoder, self.decoder):  # stack-level forward()s call back into the engine (no module cycle)
             sub.__dict__["_owner"] = weakref.ref(self)
@@ -585,19 +596,19 @@ class OLMoASR(nn.Module):
             name = C.create_string_buffer(128)
             off, numel, ndim = C.c_int64(), C.c_int64(), C.c_int()
             shape = (C.c_int64 * 4)()
-            N.check(lib.oasr_param_info(self._ctx, i, name, 128, C.byref(off), C.byref(numel), C.byref(ndim), shape), "param_info")
+            N.call("oasr_param_info", self._ctx, i, name, 128, C.byref(off), C.byref(numel), C.byref(ndim), shape)
             self._table.append((name.value.decode(), off.value, numel.value, tuple(shape[j] for j in range(ndim.value))))
         self._segments = []
         for i in range(lib.oasr_segment_count(self._ctx)):
             o, m = C.c_int64(), C.c_int64()
-            N.check(lib.oasr_segment_info(self._ctx, i, C.byref(o), C.byref(m)), "segment_info")
+            N.call("oasr_segment_info", self._ctx, i, C.byref(o), C.byref(m))
             self._segments.append((o.value, m.value))
 
     def _swap_context(self, targets, rank, scale, init_new):
         """Re-creates the context with another adapter set (``olmoasr_amd.lora``): a new arena in the new table's layout, every tensor
         both tables hold copied over by name, ``init_new(name, tensor)`` filling the new ones; parameters the new table lacks are removed
         from their modules.  Gradient arena, optimizer state and data-parallel wrappers are tied to the old layout: they must not exist yet."""
-        if getattr(self, "_opt_state", None) is not None or self._gflat is not None or getattr(self, "_autograd_post_backward", None) is not None:
+        if self._opt_state is not None or self._gflat is not None or self._autograd_post_backward is not None:
             raise N.NativeError("LoRA adapters must be added / merged before the gradient arena, the optimizer state or a data-parallel "
                                 "wrapper exists (they are laid out for the current parameter table): call add_lora / merge_lora first")
         old_ctx, old = self._ctx, {name: self._flat[off:off + numel] for name, off, numel, _ in self._table}
@@ -616,10 +627,7 @@ class OLMoASR(nn.Module):
                 del mod._parameters[attr]
         self._flat = flat
         self._shadow = torch.zeros(N.lib().oasr_shadow_bytes(self._ctx), dtype=torch.uint8, device=flat.device)
-        self._workspace = None
-        self._stage_workspace = {}
-        self._trainable_mask = None
-        self._param_version = None
+        self._reset_derived()
         self._attach_views()
         self._bind()
         N.lib().oasr_destroy(old_ctx)
@@ -658,9 +666,8 @@ class OLMoASR(nn.Module):
         if self._gflat is not None:
             self._gflat = fn(self._gflat).contiguous()
         self._shadow = self._shadow.to(self._flat.device)
-        self._workspace = None
-        self._stage_workspace = {}
-        if getattr(self, "_opt_state", None) is not None:  # optimizer arenas follow the parameters
+        self._reset_derived(context_changed=False)
+        if self._opt_state is not None:  # optimizer arenas follow the parameters
             self._opt_state = tuple(fn(t).contiguous() for t in self._opt_state)
             self._opt_stats = self._opt_stats.to(self._flat.device)
             self._opt_scratch = self._opt_scratch.to(self._flat.device)
@@ -674,20 +681,17 @@ class OLMoASR(nn.Module):
         return self
 
     def _bind(self):
-        lib = N.lib()
         pos = self.encoder.positional_embedding
         if pos.dtype != torch.float32 or not pos.is_contiguous():
             self.encoder._buffers["positional_embedding"] = pos.float().contiguous()
             pos = self.encoder.positional_embedding
-        opt = getattr(self, "_opt_state", None)
-        N.check(lib.oasr_bind(self._ctx, N.ptr(self._flat), N.ptr(self._gflat), N.ptr(opt[0]) if opt else None,
-                              N.ptr(opt[1]) if opt else None, N.ptr(pos)), "oasr_bind")
-        N.check(lib.oasr_bind_shadow(self._ctx, N.ptr(self._shadow)), "oasr_bind_shadow")
+        m, v = self._opt_state or (None, None)
+        N.call("oasr_bind", self._ctx, self._flat, self._gflat, m, v, pos)
+        N.call("oasr_bind_shadow", self._ctx, self._shadow)
 
     def refresh_shadow(self):
         """Re-derive the bf16 compute copies after the fp32 parameters changed outside ``optim_step``."""
-        with torch.cuda.device(self._flat.device):
-            N.check(N.lib().oasr_refresh_shadow(self._ctx, N.stream_ptr()), "oasr_refresh_shadow")
+        N.call("oasr_refresh_shadow", self._ctx, N.STREAM, device=self._flat.device)
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
@@ -731,12 +735,28 @@ class OLMoASR(nn.Module):
         """[(offset, numel)] arena ranges in the order their gradients become final during backward."""
         return list(self._segments)
 
-    def _ws(self, B, S, mode):
-        need = N.lib().oasr_workspace_bytes(self._ctx, B, S, mode)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
-        return self._workspace
+    def _reset_derived(self, context_changed=True):
+        """Forgets what hangs on the arenas' device (``.to()``) and, with ``context_changed``, on the engine context (``_swap_context``)."""
+        for slot in self._slots.values():
+            slot.drop()
+        self._anchor = None  # the leaf every autograd bridge hangs its graph on (_autograd_anchor)
+        self._loss_parts_rows = None  # f32 [2, B * S] row scratch of loss_and_backward(loss_parts_out=...)
+        if context_changed:
+            self._trainable_mask = None  # the requires_grad mask last pushed with oasr_set_trainable
+            self._param_version = None  # sum of the parameters' version counters at the last shadow refresh (_sync_for_autograd)
+
+    def _ws(self, B, S, mode, slot="main"):
+        return self._slots[slot].take(N.lib().oasr_workspace_bytes(self._ctx, B, S, mode), self._flat.device)
+
+    @property
+    def _workspace(self):
+        """The main workspace (None: not allocated).  Assigning None frees it."""
+        return self._slots["main"].buf
+
+    @_workspace.setter
+    def _workspace(self, value):
+        assert value is None, "the workspace is allocated by the calls that need it"
+        self._slots["main"].drop()
 
     # ---- staged autograd (model.encoder / model.decoder with a grad_fn) -------------------------------------------------------
     def _stage_wants_grad(self, stage_module, inp) -> bool:
@@ -746,32 +766,14 @@ class OLMoASR(nn.Module):
         return bool(getattr(inp, "requires_grad", False)) or any(p.requires_grad for p in stage_module.parameters())
 
     def _stage_begin(self, input_grad: bool):
-        if getattr(self, "_autograd_post_backward", None) is not None:
+        if self._autograd_post_backward is not None:
             raise N.NativeError("model.encoder / model.decoder with autograd under olmoasr_amd.ddp.DistributedDataParallel: the wrapper reduces "
                                 "gradients after the backward of model(mel, tokens, mask) only -- train through model(mel, tokens, mask) (or "
                                 "loss_and_backward + GradReducer), or call the stages under torch.no_grad()")
         self._sync_for_autograd(allow_none=input_grad)
 
     def _stage_ws(self, stage, B, S):
-        mode = N.MODE_TRAIN_ENC if stage == "enc" else N.MODE_TRAIN_DEC
-        need = N.lib().oasr_workspace_bytes(self._ctx, B, S, mode)
-        ws = self._stage_workspace.get(stage)
-        if ws is None or ws.numel() < need:
-            self._stage_workspace[stage] = None
-            ws = self._stage_workspace[stage] = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
-        return ws
-
-    def _stage_forward(self, stage) -> int:
-        self._stage_gen[stage] += 1
-        return self._stage_gen[stage]
-
-    def _stage_backward_ws(self, stage, gen, what):
-        ws = self._stage_workspace.get(stage)
-        if gen != self._stage_gen[stage] or ws is None:
-            raise RuntimeError(f"{what} backward: the activations of this forward are gone -- the engine keeps ONE forward's activations per "
-                               "stage (in the stage's workspace) and a later forward of the same stage or a previous backward through this "
-                               "graph used them; run forward and backward in pairs (gradient accumulation: forward/backward per micro-batch)")
-        return ws
+        return self._ws(B, S, N.MODE_TRAIN_ENC if stage == "enc" else N.MODE_TRAIN_DEC, stage)
 
     # ---- reference API ---------------------------------------------------------------------------------------
     @staticmethod
@@ -798,9 +800,7 @@ class OLMoASR(nn.Module):
         ws = self._ws(B, S, 0)
         logits = torch.empty(B, S, self._n_rows, device=mel.device, dtype=torch.float32) if want_logits else None
         xa = torch.empty(B, self.dims.n_audio_ctx, self.dims.n_audio_state, device=mel.device, dtype=self._act_dtype) if want_xa else None
-        with torch.cuda.device(mel.device):
-            N.check(N.lib().oasr_forward(self._ctx, N.ptr(mel), N.ptr(tokens), N.ptr(text_len), B, S, N.ptr(logits), N.ptr(xa),
-                                         N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_forward")
+        N.call("oasr_forward", self._ctx, mel, tokens, text_len, B, S, logits, xa, ws, ws.numel(), N.STREAM)
         return logits, xa
 
     def forward(self, mel: Tensor, tokens: Tensor, padding_mask: Optional[Tensor] = None, verbose: bool = False) -> Tensor:
@@ -819,8 +819,8 @@ class OLMoASR(nn.Module):
 
     # ---- torch.autograd bridge -------------------------------------------------------------------------------------------
     def _autograd_anchor(self) -> Tensor:
-        a = getattr(self, "_anchor", None)
-        if a is None or a.device != self._flat.device:
+        a = self._anchor
+        if a is None:
             a = self._anchor = torch.zeros((), device=self._flat.device, requires_grad=True)
         return a
 
@@ -833,11 +833,10 @@ class OLMoASR(nn.Module):
         mask = tuple(bool(p.requires_grad) for p, *_ in self._param_views)
         if not any(mask) and not allow_none:
             raise N.NativeError("every parameter has requires_grad=False: nothing to train")
-        if mask != getattr(self, "_trainable_mask", None):
+        if mask != self._trainable_mask:
             buf = (C.c_uint8 * len(mask))(*mask)
-            with torch.cuda.device(self._flat.device):
-                N.check(N.lib().oasr_set_trainable(self._ctx, buf, len(mask)), "oasr_set_trainable")
-            old = getattr(self, "_trainable_mask", None)
+            N.call("oasr_set_trainable", self._ctx, buf, len(mask), device=self._flat.device)
+            old = self._trainable_mask
             self._trainable_mask = mask
             if self._gflat is not None:
                 for (p, off, numel, shape), t, was in zip(self._param_views, mask, old or (True,) * len(mask)):
@@ -868,8 +867,8 @@ class OLMoASR(nn.Module):
                     g = self._gflat[off:off + numel].view(shape)
                     g.zero_()
                     p.grad = g
-        if ver != getattr(self, "_param_version", None):
-            if getattr(self, "_param_version", None) is not None:
+        if ver != self._param_version:
+            if self._param_version is not None:
                 self.refresh_shadow()
             self._param_version = ver
 
@@ -882,8 +881,7 @@ class OLMoASR(nn.Module):
         mel = mel.float().contiguous()
         ws = self._ws(B, 1, 0)
         xa = torch.empty(B, self.dims.n_audio_ctx, self.dims.n_audio_state, device=mel.device, dtype=self._act_dtype)
-        with torch.cuda.device(mel.device):
-            N.check(N.lib().oasr_encode(self._ctx, N.ptr(mel), B, N.ptr(xa), N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_encode")
+        N.call("oasr_encode", self._ctx, mel, B, xa, ws, ws.numel(), N.STREAM)
         return xa
 
     @torch.no_grad()
@@ -900,9 +898,7 @@ class OLMoASR(nn.Module):
         ws = self._ws(B, S, 0)
         shape = (B, self._n_rows) if last_only else (B, S, self._n_rows)
         out = torch.empty(*shape, device=tokens.device, dtype=torch.float32)
-        with torch.cuda.device(tokens.device):
-            N.check(N.lib().oasr_decode_logits(self._ctx, N.ptr(tokens), N.ptr(xa), N.ptr(text_len), B, S, int(last_only), N.ptr(out),
-                                               N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_decode_logits")
+        N.call("oasr_decode_logits", self._ctx, tokens, xa, text_len, B, S, int(last_only), out, ws, ws.numel(), N.STREAM)
         return out
 
     # ---- cached decoding (the reference's install_kv_cache_hooks + one decoder step per token) ------------------------
@@ -924,8 +920,7 @@ class OLMoASR(nn.Module):
                 raise ValueError(f"kv_cache_begin: {name} must be a contiguous uint8 tensor of {nbytes} bytes on {xa.device}")
             bufs[name] = buf
         cache, ws = bufs["cache"], bufs["ws"]
-        with torch.cuda.device(xa.device):
-            N.check(lib.oasr_decode_begin(self._ctx, N.ptr(xa), B, N.ptr(cache), N.stream_ptr()), "oasr_decode_begin")
+        N.call("oasr_decode_begin", self._ctx, xa, B, cache, N.STREAM)
         return {"cache": cache, "ws": ws, "B": B, "pos": 0}
 
     @torch.no_grad()
@@ -935,9 +930,8 @@ class OLMoASR(nn.Module):
         tokens_last = tokens_last.to(torch.int64).contiguous()
         assert tokens_last.shape == (B,)
         out = torch.empty(B, self._n_rows, device=tokens_last.device, dtype=torch.float32)
-        with torch.cuda.device(tokens_last.device):
-            N.check(N.lib().oasr_decode_step(self._ctx, N.ptr(tokens_last), B, state["pos"], N.ptr(state["cache"]), N.ptr(out),
-                                             N.ptr(state["ws"]), state["ws"].numel(), N.stream_ptr()), "oasr_decode_step")
+        ws = state["ws"]
+        N.call("oasr_decode_step", self._ctx, tokens_last, B, state["pos"], state["cache"], out, ws, ws.numel(), N.STREAM)
         state["pos"] += 1
         return out
 
@@ -1038,8 +1032,7 @@ class OLMoASR(nn.Module):
     # ---- fused training micro-step ---------------------------------------------------------------------------
     def zero_grad(self, set_to_none: bool = False):
         g = self.enable_grad_arena()
-        with torch.cuda.device(g.device):
-            N.check(N.lib().oasr_zero_grad(self._ctx, N.stream_ptr()), "oasr_zero_grad")
+        N.call("oasr_zero_grad", self._ctx, N.STREAM, device=g.device)
 
     def loss_and_backward(self, mel: Tensor, tokens: Tensor, targets: Tensor, text_len: Tensor, *, loss_scale: float = 1.0,
                           accumulation_steps: int = 1, loss_out: Optional[Tensor] = None, accumulate_loss: bool = False,
@@ -1165,7 +1158,7 @@ class OLMoASR(nn.Module):
             assert span_h.numel() == B and not span_h.is_cuda
         parts_rows = None
         if loss_parts_out is not None:  # f32 [2, B * S]: the caller-owned row scratch of oasr_train_step_args.loss_parts_rows
-            parts_rows = getattr(self, "_loss_parts_rows", None)
+            parts_rows = self._loss_parts_rows
             if parts_rows is None or parts_rows.numel() < 2 * B * S or parts_rows.device != dev:
                 parts_rows = self._loss_parts_rows = torch.empty(2 * B * S, device=dev, dtype=torch.float32)
         args = N.TrainStepArgs(mel=N.ptr(None if xa is not None else mel), xa=N.ptr(xa), tokens=N.ptr(tokens), targets=N.ptr(targets),
@@ -1174,8 +1167,7 @@ class OLMoASR(nn.Module):
                                B=B, S=S, span_forward=int(span_forward is None or bool(span_forward)), accumulate_loss=int(accumulate_loss),
                                loss_scale=float(loss_scale), inv_accum=1.0 / accumulation_steps, label_smoothing=eps, z_loss=zc,
                                loss_parts_out=N.ptr(loss_parts_out), loss_parts_rows=N.ptr(parts_rows))
-        with torch.cuda.device(dev):
-            N.check(N.lib().oasr_train_step(self._ctx, C.byref(args), N.ptr(ws), ws.numel(), N.stream_ptr()), "oasr_train_step")
+        N.call("oasr_train_step", self._ctx, C.byref(args), ws, ws.numel(), N.STREAM, device=dev)
         return loss_out, logits
 
     @staticmethod
@@ -1188,7 +1180,7 @@ class OLMoASR(nn.Module):
         return torch.maximum(last, text_len.to(torch.int32).clamp(max=S)).cpu()
 
     def init_optimizer_state(self):
-        if getattr(self, "_opt_state", None) is None:
+        if self._opt_state is None:
             self._opt_state = (torch.zeros_like(self._flat), torch.zeros_like(self._flat))
             self._opt_stats = torch.zeros(2, device=self._flat.device, dtype=torch.float32)
             self._opt_scratch = torch.zeros(8192, device=self._flat.device, dtype=torch.uint8)
@@ -1243,10 +1235,8 @@ class OLMoASR(nn.Module):
         ``optimizer_state_dict`` is unchanged: it lists every tensor)."""
         self.init_optimizer_state()
         self._sync_trainable()
-        with torch.cuda.device(self._flat.device):
-            N.check(N.lib().oasr_optim_step(self._ctx, float(inv_loss_scale), float(max_grad_norm), float(lr), float(betas[0]),
-                                            float(betas[1]), float(eps), float(weight_decay), int(step), N.ptr(self._opt_stats),
-                                            N.ptr(self._opt_scratch), N.stream_ptr()), "oasr_optim_step")
+        N.call("oasr_optim_step", self._ctx, float(inv_loss_scale), float(max_grad_norm), float(lr), float(betas[0]), float(betas[1]),
+               float(eps), float(weight_decay), int(step), self._opt_stats, self._opt_scratch, N.STREAM)
         return self._opt_stats
 
     def __del__(self):

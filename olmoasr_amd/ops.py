@@ -1,5 +1,5 @@
 """Thin tensor-level wrappers over the unit operators of liboasr (used by the op-level parity tests and by the
-host-side mirrors).  bf16 tensors are torch.bfloat16; everything runs on the current HIP stream."""
+host-side mirrors).  bf16 tensors are torch.bfloat16; everything runs on the current HIP stream of the tensors' device."""
 import ctypes as C
 import math
 
@@ -40,12 +40,13 @@ def gemm(A, B, M, N_, K, *, ta=False, tb=False, a_view=None, b_view=None, bias=N
     g.beta, g.atomic, g.split_k = beta, int(atomic), split_k
     g.colsum = colsum.data_ptr() if colsum is not None else None
     g.dgelu_deriv = int(dgelu_deriv)
+    dev = next((t.device for t in (out, out_f32, out_pre) if t is not None), None)
     engine_only = (colsum_scratch, atomic_on_pp, raster_gm, stagger, stagger_phases)
     if all(x is None for x in engine_only):
-        N.check(N.lib().oasr_gemm(C.byref(g), N.stream_ptr()), "oasr_gemm")
+        N.call("oasr_gemm", C.byref(g), N.STREAM, device=dev)
     else:
-        N.check(N.lib().oasr_test_gemm(C.byref(g), N.ptr(colsum_scratch), int(atomic_on_pp or 0), int(raster_gm or 0), int(stagger or 0),
-                                       int(stagger_phases or 0), N.stream_ptr()), "oasr_test_gemm")
+        N.call("oasr_test_gemm", C.byref(g), colsum_scratch, int(atomic_on_pp or 0), int(raster_gm or 0), int(stagger or 0),
+               int(stagger_phases or 0), N.STREAM, device=dev)
 
 
 def gemm_launch_records():
@@ -67,8 +68,7 @@ def layernorm_fwd(x, gamma, beta):
     y = torch.empty_like(x)
     mean = torch.empty(rows, device=x.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
-    N.check(N.lib().oasr_layernorm_fwd(N.ptr(x), N.ptr(gamma), N.ptr(beta), N.ptr(y), N.ptr(mean), N.ptr(rstd), rows, d,
-                                       N.stream_ptr()), "layernorm_fwd")
+    N.call("oasr_layernorm_fwd", x, gamma, beta, y, mean, rstd, rows, d, N.STREAM)
     return y, mean, rstd
 
 
@@ -77,8 +77,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None):
     dx = torch.empty_like(x)
     dg = torch.zeros(d, device=x.device, dtype=torch.float32)
     db = torch.zeros_like(dg)
-    N.check(N.lib().oasr_layernorm_bwd(N.ptr(dy), N.ptr(x), N.ptr(gamma), N.ptr(mean), N.ptr(rstd), N.ptr(dres), N.ptr(dx),
-                                       N.ptr(dg), N.ptr(db), rows, d, N.stream_ptr()), "layernorm_bwd")
+    N.call("oasr_layernorm_bwd", dy, x, gamma, mean, rstd, dres, dx, dg, db, rows, d, N.STREAM)
     return dx, dg, db
 
 
@@ -105,7 +104,7 @@ def attention_fwd(q, k, v, kv_len=None, causal=False, want_o_lo=False):
     a = _attn_args(q, k, v, o.view(B, Tq, H, 64), lse, kv_len, causal)
     o_lo = torch.empty(B, Tq, H * 64, device=q.device, dtype=torch.bfloat16) if want_o_lo else None
     a.o_lo = o_lo.data_ptr() if want_o_lo else None
-    N.check(N.lib().oasr_attention_fwd(C.byref(a), N.stream_ptr()), "attention_fwd")
+    N.call("oasr_attention_fwd", C.byref(a), N.STREAM, device=q.device)
     return (o, lse, o_lo) if want_o_lo else (o, lse)
 
 
@@ -122,7 +121,7 @@ def attention_scores(q, k, kv_len=None, causal=False):
     a.ldq, a.ldk, a.bsq, a.bsk = q.stride(1), k.stride(1), q.stride(0), k.stride(0)
     a.kv_len = kv_len.data_ptr() if kv_len is not None else None
     a.B, a.H, a.Tq, a.Tk, a.causal = B, H, Tq, Tk, int(causal)
-    N.check(N.lib().oasr_attention_scores(C.byref(a), 0 if q.dtype == BF else 1, N.ptr(out), N.stream_ptr()), "attention_scores")
+    N.call("oasr_attention_scores", C.byref(a), 0 if q.dtype == BF else 1, out, N.STREAM)
     return out
 
 
@@ -144,7 +143,7 @@ def attention_bwd(q, k, v, o, lse, d_o, kv_len=None, causal=False, o_lo=None, dq
         Tk = k.shape[1]
         scratch = torch.empty(B * ((Tq + 127) // 128 + (Tk + 127) // 128) * H * 64, device=q.device, dtype=torch.float32)
         a.colsum_scratch = scratch.data_ptr()
-    N.check(N.lib().oasr_attention_bwd(C.byref(a), N.stream_ptr()), "attention_bwd")
+    N.call("oasr_attention_bwd", C.byref(a), N.STREAM, device=q.device)
     return dq, dk, dv
 
 
@@ -193,8 +192,7 @@ def span_block_tables(span, B, S, H, device="cuda", with_rows=False):
     span_d = torch.empty(B, dtype=torch.int32, device=device)
     tphys = torch.empty(B * S, dtype=torch.int64, device=device)
     counts = (C.c_int32 * 2)()
-    N.check(N.lib().oasr_test_span_block_tables(C.c_void_p(span.data_ptr()), B, S, H, N.ptr(targets), N.ptr(rows), N.ptr(span_d), N.ptr(tphys),
-                                                N.ptr(blk128), N.ptr(blk256), counts, N.stream_ptr(device)), "span_block_tables")
+    N.call("oasr_test_span_block_tables", span, B, S, H, targets, rows, span_d, tphys, blk128, blk256, counts, N.STREAM)
     blocks = (blk128, blk256, int(counts[0]), int(counts[1]))
     return (blocks, rows, span_d) if with_rows else blocks
 
@@ -238,7 +236,7 @@ def attention_fwd_rows(qc, kc, vc, B, H, Tq, Tk, q_rows, k_rows=None, kv_len=Non
     a.o_lo = o_lo.data_ptr() if want_o_lo else None
     a.q_span = q_span.data_ptr() if q_span is not None else None
     _set_blocks(a, q_blocks)
-    N.check(N.lib().oasr_attention_fwd(C.byref(a), N.stream_ptr()), "attention_fwd(rows)")
+    N.call("oasr_attention_fwd", C.byref(a), N.STREAM, device=qc.device)
     return (oc, lse, o_lo) if want_o_lo else (oc, lse)
 
 
@@ -269,7 +267,7 @@ def attention_bwd_rows(qc, kc, vc, oc, lse, doc, B, H, Tq, Tk, q_rows, k_rows=No
             scratch.fill_(scratch_fill)
         a.colsum_scratch = scratch.data_ptr()
     _set_blocks(a, q_blocks)
-    N.check(N.lib().oasr_attention_bwd(C.byref(a), N.stream_ptr()), "attention_bwd(rows)")
+    N.call("oasr_attention_bwd", C.byref(a), N.STREAM, device=qc.device)
     return dq, dk, dv
 
 
@@ -338,9 +336,8 @@ def alignment_matrix(qk_layers, heads_per_layer, n_frames, medfilt_width=7, qk_s
     a.n_layers, a.H, a.n_tok, a.Tk, a.n_frames, a.medfilt_width, a.qk_scale = len(qk_layers), H, n_tok, Tk, n_frames, medfilt_width, float(qk_scale)
     a.out, a.ldo = out.data_ptr(), out.stride(0)
     nsel = sum(len(hs) for hs in heads_per_layer)
-    with torch.cuda.device(dev):
-        ws = _workspace("alignment_matrix", dev, N.lib().oasr_alignment_workspace_bytes(nsel, n_tok, n_frames))
-        N.check(N.lib().oasr_alignment_matrix(C.byref(a), N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "oasr_alignment_matrix")
+    ws = _workspace("alignment_matrix", dev, N.lib().oasr_alignment_workspace_bytes(nsel, n_tok, n_frames))
+    N.call("oasr_alignment_matrix", C.byref(a), ws, ws.numel(), N.STREAM)
     return out
 
 
@@ -364,15 +361,13 @@ def dtw_device(cost, negate=False, path=None, workspace=None):
     N.require_gpu(cost, "dtw: cost")
     P = n + m - 1
     need = N.lib().oasr_dtw_workspace_bytes(n, m)
-    with torch.cuda.device(cost.device):
-        if path is None:
-            path = torch.empty(2 * P + 1, device=cost.device, dtype=torch.int32)
-        if workspace is None:
-            workspace = _workspace("dtw", cost.device, need)
-        assert path.dtype == torch.int32 and path.numel() == 2 * P + 1 and path.is_contiguous() and workspace.dtype == torch.uint8
-        ld = cost.stride(0) if n > 1 else max(m, cost.stride(0))
-        N.check(N.lib().oasr_dtw(N.ptr(cost), ld, n, m, int(bool(negate)), N.ptr(path), N.ptr(path[P:]), N.ptr(path[2 * P:]), N.ptr(workspace),
-                                 workspace.numel(), N.stream_ptr(cost.device)), "oasr_dtw")
+    if path is None:
+        path = torch.empty(2 * P + 1, device=cost.device, dtype=torch.int32)
+    if workspace is None:
+        workspace = _workspace("dtw", cost.device, need)
+    assert path.dtype == torch.int32 and path.numel() == 2 * P + 1 and path.is_contiguous() and workspace.dtype == torch.uint8
+    ld = cost.stride(0) if n > 1 else max(m, cost.stride(0))
+    N.call("oasr_dtw", cost, ld, n, m, int(bool(negate)), path, path[P:], path[2 * P:], workspace, workspace.numel(), N.STREAM)
     return path, workspace
 
 
@@ -395,8 +390,7 @@ def dtw_host(cost, negate=False):
     path = torch.full((2 * P + 1,), -1, dtype=torch.int32)
     ws = torch.empty(N.lib().oasr_dtw_workspace_bytes(n, m), dtype=torch.uint8)
     ld = cost.stride(0) if n > 1 else max(m, cost.stride(0))
-    N.check(N.lib().oasr_test_dtw_host(N.ptr(cost), ld, n, m, int(bool(negate)), N.ptr(path), N.ptr(path[P:]), N.ptr(path[2 * P:]), N.ptr(ws)),
-            "oasr_test_dtw_host")
+    N.call("oasr_test_dtw_host", cost, ld, n, m, int(bool(negate)), path, path[P:], path[2 * P:], ws)
     ln = int(path[-1])
     return path[:ln].to(torch.int64), path[P:P + ln].to(torch.int64)
 
@@ -445,8 +439,7 @@ def edit_counts(hyp, hyp_len, ref, ref_len, out=None):
                 and out.device == keep[0].device):
             raise ValueError("edit_counts: out must be a contiguous int32 [B, 4] on the operands' device")
         res, a.out = out, out.data_ptr()
-    with torch.cuda.device(res.device):
-        N.check(N.lib().oasr_edit_counts(C.byref(a), N.stream_ptr(res.device)), "oasr_edit_counts")
+    N.call("oasr_edit_counts", C.byref(a), N.STREAM, device=res.device)
     return res
 
 
@@ -457,7 +450,7 @@ def edit_counts_host(hyp, hyp_len, ref, ref_len):
     for nm, ln, w in (("hyp_len", keep[2], a.Lh), ("ref_len", keep[3], a.Lr)):
         if int(ln.min()) < 0 or int(ln.max()) > min(N.EditArgs.MAX_LEN, w):
             raise ValueError(f"edit_counts_host: {nm} outside [0, min({N.EditArgs.MAX_LEN}, row width {w})]")
-    N.check(N.lib().oasr_edit_counts_host(C.byref(a)), "oasr_edit_counts_host")
+    N.call("oasr_edit_counts_host", C.byref(a))
     return out
 
 
@@ -482,15 +475,14 @@ def cross_entropy_(logits, V, targets, ignore, gscale=1.0, write_grad=True, labe
     row_loss = torch.empty(rows, device=logits.device, dtype=torch.float32)
     loss = torch.zeros(1, device=logits.device, dtype=torch.float32)
     parts = torch.empty(2, rows, device=logits.device, dtype=torch.float32) if return_parts else None
-    N.check(N.lib().oasr_cross_entropy_ex(N.ptr(logits), logits.stride(0), V, N.ptr(targets), rows, ignore, gscale, N.ptr(nv),
-                                          N.ptr(row_loss), N.ptr(loss), int(write_grad), eps, z, N.ptr(parts), N.stream_ptr()),
-            "cross_entropy")
+    N.call("oasr_cross_entropy_ex", logits, logits.stride(0), V, targets, rows, ignore, gscale, nv, row_loss, loss, int(write_grad), eps, z,
+           parts, N.STREAM)
     return (loss, row_loss, parts) if return_parts else (loss, row_loss)
 
 
 def cast_bf16(x):
     out = torch.empty(x.shape, device=x.device, dtype=BF)
-    N.check(N.lib().oasr_cast_f32_bf16(N.ptr(x), N.ptr(out), x.numel(), N.stream_ptr()), "cast")
+    N.call("oasr_cast_f32_bf16", x, out, x.numel(), N.STREAM)
     return out
 
 
@@ -510,9 +502,9 @@ def log_mel(pcm, finalize: bool = True):
     ws = torch.empty(N.lib().oasr_log_mel_workspace_bytes(B), device=pcm.device, dtype=torch.uint8)
     if not finalize:
         cm = torch.empty(B, device=pcm.device, dtype=torch.float32)
-        N.check(N.lib().oasr_log_mel_raw(N.ptr(pcm), dt, B, n, N.ptr(mel), N.ptr(cm), N.ptr(ws), N.stream_ptr()), "oasr_log_mel_raw")
+        N.call("oasr_log_mel_raw", pcm, dt, B, n, mel, cm, ws, N.STREAM)
         return mel, cm
-    N.check(N.lib().oasr_log_mel(N.ptr(pcm), dt, B, n, N.ptr(mel), N.ptr(ws), N.stream_ptr()), "oasr_log_mel")
+    N.call("oasr_log_mel", pcm, dt, B, n, mel, ws, N.STREAM)
     return mel
 
 
@@ -556,8 +548,7 @@ def spec_augment_(mel, *, freq_masks, freq_width, time_masks, time_width, fill=0
         return mel
     if n_mels < 1 or T < 1:
         raise ValueError(f"spec_augment: n_mels = {n_mels} and T = {T} must be >= 1")
-    with torch.cuda.device(mel.device):
-        N.check(N.lib().oasr_spec_augment(N.ptr(mel), B, n_mels, T, C.byref(pol), seed, first_clip, N.stream_ptr(mel.device)), "oasr_spec_augment")
+    N.call("oasr_spec_augment", mel, B, n_mels, T, C.byref(pol), seed, first_clip, N.STREAM)
     return mel
 
 
@@ -568,7 +559,7 @@ def spec_augment_plan(*, freq_masks, freq_width, time_masks, time_width, seed=0,
     if not (isinstance(n_mels, int) and isinstance(T, int) and 1 <= n_mels < 2 ** 31 and 1 <= T < 2 ** 31):
         raise ValueError(f"spec_augment: n_mels = {n_mels!r} and T = {T!r} must be integers in [1, 2^31)")
     f_iv, t_iv = (C.c_int32 * (2 * max(1, freq_masks)))(), (C.c_int32 * (2 * max(1, time_masks)))()
-    N.check(N.lib().oasr_spec_augment_plan(C.byref(pol), _u64("seed", seed), _u64("clip", clip), n_mels, T, f_iv, t_iv), "oasr_spec_augment_plan")
+    N.call("oasr_spec_augment_plan", C.byref(pol), _u64("seed", seed), _u64("clip", clip), n_mels, T, f_iv, t_iv)
     return ([(f_iv[2 * i], f_iv[2 * i + 1]) for i in range(freq_masks)], [(t_iv[2 * i], t_iv[2 * i + 1]) for i in range(time_masks)])
 
 
@@ -667,8 +658,7 @@ def speed_perturb(pcm, n_valid, *, factors, seed=0, first_clip=0, tokens=(), ts_
         raise ValueError("speed_perturb: pcm must be a GPU tensor (speed_perturb_host takes CPU tensors)")
     a, out, n_out, factor, keep = _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_max, out, True)
     if a.B:
-        with torch.cuda.device(pcm.device):
-            N.check(N.lib().oasr_speed_perturb(C.byref(a), N.stream_ptr(pcm.device)), "oasr_speed_perturb")
+        N.call("oasr_speed_perturb", C.byref(a), N.STREAM, device=pcm.device)
     return out, n_out, factor
 
 
@@ -681,7 +671,7 @@ def speed_perturb_host(pcm, n_valid, *, factors, seed=0, first_clip=0, tokens=()
     if a.B:
         if int(n_valid.min()) < 0 or int(n_valid.max()) > a.N:
             raise ValueError(f"speed_perturb_host: n_valid outside [0, N = {a.N}]")
-        N.check(N.lib().oasr_speed_perturb_host(C.byref(a)), "oasr_speed_perturb_host")
+        N.call("oasr_speed_perturb_host", C.byref(a))
     return out, n_out, factor
 
 
@@ -695,8 +685,8 @@ def speed_plan(factors, seed, clip, n_valid, n):
     if not (1 <= n <= N.SpeedArgs.MAX_N and 0 <= n_valid <= n):
         raise ValueError(f"speed_plan: 1 <= N <= 2^26 and 0 <= n_valid <= N, got N = {n}, n_valid = {n_valid}")
     P, Q, n_out, f = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    N.check(N.lib().oasr_speed_plan(C.byref(pol), _u64("seed", seed, "speed_plan"), _u64("clip", clip, "speed_plan"), n_valid, n, C.byref(P), C.byref(Q), C.byref(n_out),
-                                    C.byref(f)), "oasr_speed_plan")
+    N.call("oasr_speed_plan", C.byref(pol), _u64("seed", seed, "speed_plan"), _u64("clip", clip, "speed_plan"), n_valid, n, C.byref(P),
+           C.byref(Q), C.byref(n_out), C.byref(f))
     return P.value, Q.value, n_out.value, f.value
 
 
@@ -706,9 +696,9 @@ def speed_table(P, Q):
     if P == Q:
         raise ValueError("speed_table: P == Q is the identity (a copy): it has no table")
     H = C.c_int()
-    N.check(N.lib().oasr_speed_table(pol.P[0], pol.Q[0], None, C.byref(H)), "oasr_speed_table")
+    N.call("oasr_speed_table", pol.P[0], pol.Q[0], None, C.byref(H))
     T = torch.empty(Q, 2 * H.value, dtype=torch.int32)
-    N.check(N.lib().oasr_speed_table(P, Q, N.ptr(T), C.byref(H)), "oasr_speed_table")
+    N.call("oasr_speed_table", P, Q, T, C.byref(H))
     return T, H.value
 
 
@@ -722,8 +712,7 @@ def pick_tokens(logits, mask=None, mask2=None, want_logprob=True):
     lp = torch.empty(rows, device=logits.device, dtype=torch.float32) if want_logprob else None
     for m in (mask, mask2):
         assert m is None or (m.dtype == torch.float32 and m.numel() == V and m.is_contiguous())
-    N.check(N.lib().oasr_pick_tokens(N.ptr(logits), logits.stride(0), V, rows, N.ptr(mask), N.ptr(mask2), N.ptr(tok), N.ptr(lp),
-                                     N.stream_ptr()), "oasr_pick_tokens")
+    N.call("oasr_pick_tokens", logits, logits.stride(0), V, rows, mask, mask2, tok, lp, N.STREAM)
     return tok, lp
 
 
@@ -739,11 +728,9 @@ def pick_tokens_ts(logits, history, n_history, *, timestamp_begin, eot, no_times
     lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
     for m in (mask, mask2):
         assert m is None or (m.dtype == torch.float32 and m.numel() == V and m.is_contiguous())
-    N.check(N.lib().oasr_pick_tokens_ts(N.ptr(logits), logits.stride(0), V, rows, N.ptr(mask), N.ptr(mask2),
-                                        N.ptr(history) if n_history else None, history.stride(0) if n_history else 0, int(n_history),
-                                        int(timestamp_begin), int(eot), int(no_timestamps),
-                                        -1 if max_initial_index is None else int(max_initial_index), N.ptr(tok), N.ptr(lp), N.stream_ptr()),
-            "oasr_pick_tokens_ts")
+    N.call("oasr_pick_tokens_ts", logits, logits.stride(0), V, rows, mask, mask2, history if n_history else None,
+           history.stride(0) if n_history else 0, int(n_history), int(timestamp_begin), int(eot), int(no_timestamps),
+           -1 if max_initial_index is None else int(max_initial_index), tok, lp, N.STREAM)
     return tok, lp
 
 
@@ -757,7 +744,7 @@ def _ts_args(logits, history, n_history, mask, mask2):
     for m in (mask, mask2):
         assert m is None or (m.dtype == torch.float32 and m.numel() == V and m.is_contiguous())
     nh = -1 if n_history is None else int(n_history)
-    return rows, V, (N.ptr(history) if nh > 0 else None), (history.stride(0) if nh > 0 else 0), nh
+    return rows, V, (history if nh > 0 else None), (history.stride(0) if nh > 0 else 0), nh
 
 
 def topk_tokens(logits, k, *, history=None, n_history=None, timestamp_begin=50363, eot=50256, no_timestamps=50362, max_initial_index=None,
@@ -768,9 +755,8 @@ def topk_tokens(logits, k, *, history=None, n_history=None, timestamp_begin=5036
     rows, V, hp, hld, nh = _ts_args(logits, history, n_history, mask, mask2)
     tok = torch.empty(rows, k, device=logits.device, dtype=torch.int64)
     lp = torch.empty(rows, k, device=logits.device, dtype=torch.float32)
-    N.check(N.lib().oasr_topk_tokens(N.ptr(logits), logits.stride(0), V, rows, N.ptr(mask), N.ptr(mask2), hp, hld, nh, int(timestamp_begin),
-                                     int(eot), int(no_timestamps), -1 if max_initial_index is None else int(max_initial_index), int(k),
-                                     N.ptr(tok), N.ptr(lp), N.stream_ptr()), "oasr_topk_tokens")
+    N.call("oasr_topk_tokens", logits, logits.stride(0), V, rows, mask, mask2, hp, hld, nh, int(timestamp_begin), int(eot), int(no_timestamps),
+           -1 if max_initial_index is None else int(max_initial_index), int(k), tok, lp, N.STREAM)
     return lp, tok
 
 
@@ -782,9 +768,8 @@ def sample_tokens(logits, temperature, uniforms, *, history=None, n_history=None
     assert uniforms.dtype == torch.float32 and uniforms.numel() == rows and uniforms.device == logits.device
     tok = torch.empty(rows, device=logits.device, dtype=torch.int64)
     lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
-    N.check(N.lib().oasr_sample_tokens(N.ptr(logits), logits.stride(0), V, rows, N.ptr(mask), N.ptr(mask2), hp, hld, nh, int(timestamp_begin),
-                                       int(eot), int(no_timestamps), -1 if max_initial_index is None else int(max_initial_index),
-                                       float(temperature), N.ptr(uniforms), N.ptr(tok), N.ptr(lp), N.stream_ptr()), "oasr_sample_tokens")
+    N.call("oasr_sample_tokens", logits, logits.stride(0), V, rows, mask, mask2, hp, hld, nh, int(timestamp_begin), int(eot), int(no_timestamps),
+           -1 if max_initial_index is None else int(max_initial_index), float(temperature), uniforms, tok, lp, N.STREAM)
     return tok, lp
 
 
@@ -799,72 +784,66 @@ def _dt(t):
 def embedding_fwd_(tok, E, pos, x, n_embed, rows=None):
     """x[row(b, s)] = E[tok[b, s]] + pos[s]; tok int64 [B, S]; x: the output allocation (bf16 or fp32), rows: chunk-row table or None."""
     B, S = tok.shape
-    N.check(N.lib().oasr_test_embedding_fwd(N.ptr(tok), N.ptr(E), N.ptr(pos), N.ptr(x), _dt(x), B, S, E.shape[1], int(n_embed), N.ptr(rows),
-                                            N.stream_ptr()), "oasr_test_embedding_fwd")
+    N.call("oasr_test_embedding_fwd", tok, E, pos, x, _dt(x), B, S, E.shape[1], int(n_embed), rows, N.STREAM)
 
 
 def embedding_bwd_(tok, dx, dE, dpos, pad_id, n_embed, d, rows=None, span=None):
     """dE[tok] += dx, dpos[s] += sum_b dx (either may be None); dx: activation rows [*, d]."""
     B, S = tok.shape
-    N.check(N.lib().oasr_test_embedding_bwd(N.ptr(tok), N.ptr(dx), _dt(dx), N.ptr(dE), N.ptr(dpos), B, S, d, int(pad_id), int(n_embed),
-                                            N.ptr(rows), N.ptr(span), N.stream_ptr()), "oasr_test_embedding_bwd")
+    N.call("oasr_test_embedding_bwd", tok, dx, _dt(dx), dE, dpos, B, S, d, int(pad_id), int(n_embed), rows, span, N.STREAM)
 
 
 def colsum_(x, ld, M, ncols, out):
-    N.check(N.lib().oasr_test_colsum(N.ptr(x), _dt(x), ld, M, ncols, N.ptr(out), N.stream_ptr()), "oasr_test_colsum")
+    N.call("oasr_test_colsum", x, _dt(x), ld, M, ncols, out, N.STREAM)
 
 
 def conv2_col2im_dgelu_(dA, u1, dpre1, B, T1, d):
     assert dA.dtype == u1.dtype == dpre1.dtype
-    N.check(N.lib().oasr_test_conv2_col2im_dgelu(N.ptr(dA), N.ptr(u1), N.ptr(dpre1), _dt(dA), B, T1, d, N.stream_ptr()),
-            "oasr_test_conv2_col2im_dgelu")
+    N.call("oasr_test_conv2_col2im_dgelu", dA, u1, dpre1, _dt(dA), B, T1, d, N.STREAM)
 
 
 def conv1_col2im_mel_(dcol, dmel, B, T1, n_mels):
-    N.check(N.lib().oasr_test_conv1_col2im_mel(N.ptr(dcol), _dt(dcol), N.ptr(dmel), B, T1, n_mels, N.stream_ptr()), "oasr_test_conv1_col2im_mel")
+    N.call("oasr_test_conv1_col2im_mel", dcol, _dt(dcol), dmel, B, T1, n_mels, N.STREAM)
 
 
 def mel_to_time_major_(mel, out, B, n_mels, T, clip_max=None):
-    N.check(N.lib().oasr_test_mel_to_time_major(N.ptr(mel), N.ptr(out), _dt(out), B, n_mels, T, N.ptr(clip_max), N.stream_ptr()),
-            "oasr_test_mel_to_time_major")
+    N.call("oasr_test_mel_to_time_major", mel, out, _dt(out), B, n_mels, T, clip_max, N.STREAM)
 
 
 def pack_conv_weight_(w, dst, co, ci, ldk):
-    N.check(N.lib().oasr_test_pack_conv_weight(N.ptr(w), N.ptr(dst), _dt(dst), co, ci, ldk, N.stream_ptr()), "oasr_test_pack_conv_weight")
+    N.call("oasr_test_pack_conv_weight", w, dst, _dt(dst), co, ci, ldk, N.STREAM)
 
 
 def unpack_conv_grad_(g, dw, co, ci, ldk):
-    N.check(N.lib().oasr_test_unpack_conv_grad(N.ptr(g), N.ptr(dw), co, ci, ldk, N.stream_ptr()), "oasr_test_unpack_conv_grad")
+    N.call("oasr_test_unpack_conv_grad", g, dw, co, ci, ldk, N.STREAM)
 
 
 def pack_embedding_(e, dst, rows, rows_pad, d):
-    N.check(N.lib().oasr_test_pack_embedding(N.ptr(e), N.ptr(dst), rows, rows_pad, d, N.stream_ptr()), "oasr_test_pack_embedding")
+    N.call("oasr_test_pack_embedding", e, dst, rows, rows_pad, d, N.STREAM)
 
 
 def dgelu_mul_(dy, u, out, n):
     assert dy.dtype == u.dtype == out.dtype
-    N.check(N.lib().oasr_test_dgelu_mul(N.ptr(dy), N.ptr(u), N.ptr(out), _dt(dy), n, N.stream_ptr()), "oasr_test_dgelu_mul")
+    N.call("oasr_test_dgelu_mul", dy, u, out, _dt(dy), n, N.STREAM)
 
 
 def dlogits_from_f32_(src, V, rows, ld, dst):
-    N.check(N.lib().oasr_test_dlogits_from_f32(N.ptr(src), V, rows, ld, N.ptr(dst), _dt(dst), N.stream_ptr()), "oasr_test_dlogits_from_f32")
+    N.call("oasr_test_dlogits_from_f32", src, V, rows, ld, dst, _dt(dst), N.STREAM)
 
 
 def logits_to_f32_(logits, ld, rows, V, out):
-    N.check(N.lib().oasr_test_logits_to_f32(N.ptr(logits), _dt(logits), ld, rows, V, N.ptr(out), N.stream_ptr()), "oasr_test_logits_to_f32")
+    N.call("oasr_test_logits_to_f32", logits, _dt(logits), ld, rows, V, out, N.STREAM)
 
 
 def layernorm_bwd_(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum):
     """launch_layernorm_bwd as the engine calls it: dx written, dgamma / dbeta / dsum (each may be None) ACCUMULATED into the caller's tensors."""
     rows, d = x.shape
-    N.check(N.lib().oasr_test_layernorm_bwd(N.ptr(dy), N.ptr(x), N.ptr(gamma), N.ptr(mean), N.ptr(rstd), N.ptr(dres), N.ptr(dx), N.ptr(dgamma),
-                                            N.ptr(dbeta), N.ptr(dsum), _dt(x), rows, d, N.stream_ptr()), "oasr_test_layernorm_bwd")
+    N.call("oasr_test_layernorm_bwd", dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, dsum, _dt(x), rows, d, N.STREAM)
 
 
 def argmax_rows_(logits, V, rows, span, pred_out):
     """include/oasr_testing.h: oasr_test_argmax_rows -- the prediction kernel of ``loss_and_backward(pred_out=...)`` on a caller's matrix:
     ``logits`` bf16 / fp32 [n_rows, ld], ``rows`` int32 [B, 16] chunk-row table, ``span`` int32 [B] (multiples of 64), ``pred_out`` int32 [B, S]."""
     B, S = pred_out.shape
-    N.check(N.lib().oasr_test_argmax_rows(N.ptr(logits), _dt(logits), logits.stride(0), V, logits.shape[0], N.ptr(rows), N.ptr(span), B, S,
-                                          N.ptr(pred_out), N.stream_ptr()), "oasr_test_argmax_rows")
+    N.call("oasr_test_argmax_rows", logits, _dt(logits), logits.stride(0), V, logits.shape[0], rows, span, B, S, pred_out, N.STREAM)
     return pred_out

@@ -47,15 +47,12 @@ class NativeBackend:
         return torch.zeros(n, device=self.net.flat_params.device, dtype=torch.float32)
 
     def sumsq(self, off, n):
-        with torch.cuda.device(self.stats.device):
-            N.check(N.lib().oasr_grad_sumsq_range(self.net._ctx, off, n, N.ptr(self.stats), N.ptr(self.scratch), N.stream_ptr()), "sumsq_range")
+        N.call("oasr_grad_sumsq_range", self.net._ctx, off, n, self.stats, self.scratch, N.STREAM)
         return self.stats
 
     def step(self, off, n, m, v, stats, **h):
-        with torch.cuda.device(self.stats.device):
-            N.check(N.lib().oasr_optim_step_range(self.net._ctx, off, n, N.ptr(m), N.ptr(v), N.ptr(stats), float(h["inv_loss_scale"]),
-                                                  float(h["max_grad_norm"]), float(h["lr"]), float(h["betas"][0]), float(h["betas"][1]),
-                                                  float(h["eps"]), float(h["weight_decay"]), int(h["step"]), N.stream_ptr()), "optim_step_range")
+        N.call("oasr_optim_step_range", self.net._ctx, off, n, m, v, stats, float(h["inv_loss_scale"]), float(h["max_grad_norm"]), float(h["lr"]),
+               float(h["betas"][0]), float(h["betas"][1]), float(h["eps"]), float(h["weight_decay"]), int(h["step"]), N.STREAM)
 
     def after_gather(self):
         self.net.refresh_shadow()

@@ -577,3 +577,12 @@ def test_attention_decode_step_kernel(Tk, kv):
     ro, rlse = ref_attention(q, k, v, kv_len, False)
     close(o, ro, atol=2e-3 + 1e-2 * float(ro.abs().mean()), name=f"decode attn o Tk={Tk}")
     close(lse, rlse, rtol=1e-3, atol=2e-3, name="decode attn lse")
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_operands_on_different_devices_are_refused_before_the_launch():
+    from olmoasr_amd import _native as N
+    x = rnd(8, 64)
+    gamma, beta = torch.ones(64, device="cuda:1"), torch.zeros(64, device="cuda:1")
+    with pytest.raises(N.NativeError, match="oasr_layernorm_fwd: arguments on cuda:0 and on cuda:1"):
+        ops().layernorm_fwd(x, gamma, beta)

@@ -229,7 +229,7 @@ def test_frozen_and_all_frozen(tiny_case, enc_oracle, dtype):
     net = _net(c, dtype)
     net.encoder.requires_grad_(False)
     xa = net.encoder(c["mel"].to(DEV))
-    assert not xa.requires_grad and net._stage_workspace == {}  # the inference forward: no graph, no saved activations
+    assert not xa.requires_grad and net._slots["enc"].buf is None and net._slots["dec"].buf is None  # the inference forward: no graph, no saved activations
     assert torch.equal(xa, net.embed_audio(c["mel"].to(DEV)))
     # every parameter frozen, mel requires grad: saliency -- d(mel) as above, no p.grad, the gradient arena not written
     net = _net(c, dtype)
@@ -360,6 +360,51 @@ def test_other_calls_between_stage_forward_and_backward(tiny_case, dtype):
     _fused_rule(_grads(net), g0, g1)
 
 
+@pytest.fixture(scope="module")
+def fused_graph_grads(tiny_case):
+    """Per compute dtype: the gradients of model(mel, tokens, mask) + backward on two fresh models (_fused_rule's ref0 / ref1)."""
+    return {dtype: [_fused_graph_step(_net(tiny_case, dtype), tiny_case)[1] for _ in range(2)] for dtype in DTYPES}
+
+
+def _interpose(net, c, what):
+    mel_d, tok, tgt, tl = _args(c)
+    if what == "embed_audio":
+        net.embed_audio(mel_d)
+    elif what == "logits":
+        xa = torch.zeros(2, c["dims"].n_audio_ctx, c["dims"].n_audio_state, device=DEV)
+        net.logits(tok, xa, _mask(c["text_len"]))
+    elif what == "no_grad_forward":
+        with torch.no_grad():
+            net(mel_d, tok, _mask(c["text_len"]))
+    elif what == "loss_and_backward":
+        net.loss_and_backward(mel_d, tok, tgt, tl)
+    elif what == "drop_workspace":
+        net._workspace = None
+    elif what == "to_device":
+        net.to(net.device)
+    else:
+        raise AssertionError(what)
+
+
+@pytest.mark.parametrize("what", ["embed_audio", "logits", "no_grad_forward", "loss_and_backward", "drop_workspace", "to_device"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fused_backward_after_the_workspace_was_reused_or_dropped_raises(tiny_case, fused_graph_grads, dtype, what):
+    """model(mel, tokens, mask) leaves its activations (and the plan's index tables) in the workspace every other entry of the model plans
+    over from offset 0: after any of them, or after the buffer was freed or moved, the backward must refuse in Python -- not run over what
+    the later call left there.  The model stays usable: the next forward / backward pair gives a fresh model's gradients."""
+    c = tiny_case
+    mel_d, tok, tgt, _ = _args(c)
+    net = _net(c, dtype)
+    loss = _ce(net(mel_d, tok, _mask(c["text_len"])), tgt)
+    _interpose(net, c, what)
+    with pytest.raises(RuntimeError, match=r"OLMoASR\.forward backward: .*activations of this forward are gone"):
+        loss.backward()
+    net.zero_grad()  # (loss_and_backward accumulated its own gradients)
+    _, gs = _fused_graph_step(net, c)
+    g0, g1 = fused_graph_grads[dtype]
+    _fused_rule(gs, g0, g1)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_dirty_stage_workspaces(tiny_case, dtype):
     c = tiny_case
@@ -367,8 +412,8 @@ def test_dirty_stage_workspaces(tiny_case, dtype):
     l1, g1 = _staged_step(_net(c, dtype), c)
     net = _net(c, dtype)
     _staged_step(net, c)
-    for ws in net._stage_workspace.values():
-        ws.view(torch.int16).fill_(0x7FC0)  # bf16 NaN bytes
+    for stage in ("enc", "dec"):
+        net._slots[stage].buf.view(torch.int16).fill_(0x7FC0)  # bf16 NaN bytes (both stage buffers exist after a staged step)
     net.zero_grad()
     ls, gs = _staged_step(net, c)
     assert torch.equal(ls, l0)
