@@ -128,6 +128,14 @@ int oasr_test_dtw_host(const float* cost, int64_t ld, int N, int M, int negate, 
 int oasr_test_argmax_rows(const void* logits, int dtype, int64_t ld, int V, int64_t n_rows, const int32_t* rows, const int32_t* span, int B, int S,
                           int32_t* pred_out, void* stream);
 
+/* tests (tests/test_gpu_vocab_planted.py): oasr_cross_entropy_ex -- count_valid, the cross-entropy kernel, loss_reduce -- on logits of either
+ * type, argument for argument: dtype = OASR_DTYPE_BF16 runs the production kernel (what oasr_cross_entropy_ex runs), OASR_DTYPE_F32 the fp32
+ * validation kernel of the fp32 engine (logits fp32 [rows][ld], any ld >= V), which has no entry of its own in the product ABI.  No process state,
+ * no opt-in. */
+int oasr_test_cross_entropy(void* logits, int dtype, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
+                            int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, float label_smoothing, float z_loss,
+                            float* row_parts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

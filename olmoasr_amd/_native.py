@@ -198,6 +198,7 @@ def _declare(lib):
         "oasr_test_argmax_rows": (i32, [vp, i32, i64, i32, i64, vp, vp, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cross_entropy_ex": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, f32, f32, vp, vp]),
+        "oasr_test_cross_entropy": (i32, [vp, i32, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, f32, f32, vp, vp]),
         "oasr_cast_f32_bf16": (i32, [vp, vp, i64, vp]),
         "oasr_pick_tokens": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, vp]),
         "oasr_pick_tokens_ts": (i32, [vp, i64, i32, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -324,11 +324,12 @@ extern "C" int oasr_test_argmax_rows(const void* logits, int dtype, int64_t ld, 
   return launch_argmax_rows((const float*)logits, (long)ld, V, (long)n_rows, rows, span, B, S, pred_out, (hipStream_t)stream);
 }
 
-extern "C" int oasr_cross_entropy_ex(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
-                                     int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, float label_smoothing, float z_loss,
-                                     float* row_parts, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  int rc = check_ce_reg("oasr_cross_entropy_ex", label_smoothing, z_loss);
+// count_valid -> cross-entropy kernel of the logits' type -> loss_reduce: the body of oasr_cross_entropy_ex and of its test twin below
+template <typename T>
+static int cross_entropy_chain(const char* who, T* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
+                               int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, float label_smoothing, float z_loss,
+                               float* row_parts, hipStream_t st) {
+  int rc = check_ce_reg(who, label_smoothing, z_loss);
   if (rc) return rc;
   CeReg reg;
   reg.eps = label_smoothing;
@@ -337,10 +338,26 @@ extern "C" int oasr_cross_entropy_ex(void* logits, int64_t ld, int V, const int6
   reg.parts_stride = (long)rows;
   rc = launch_count_valid(targets, rows, ignore, V, n_valid_dev, st);
   if (rc) return rc;
-  rc = launch_cross_entropy((bf16_t*)logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, write_grad, st, reg);
+  rc = launch_cross_entropy(logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, write_grad, st, reg);
   if (rc) return rc;
   if (loss_out) rc = launch_loss_reduce(row_loss, rows, n_valid_dev, 1.0f, loss_out, 0, st);
   return rc;
+}
+extern "C" int oasr_cross_entropy_ex(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
+                                     int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, float label_smoothing, float z_loss,
+                                     float* row_parts, void* stream) {
+  return cross_entropy_chain("oasr_cross_entropy_ex", (bf16_t*)logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, loss_out,
+                             write_grad, label_smoothing, z_loss, row_parts, (hipStream_t)stream);
+}
+extern "C" int oasr_test_cross_entropy(void* logits, int dtype, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
+                                       int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, float label_smoothing,
+                                       float z_loss, float* row_parts, void* stream) {
+  OASR_TEST_DTYPE("oasr_test_cross_entropy");
+  if (dtype == OASR_DTYPE_BF16)
+    return cross_entropy_chain("oasr_test_cross_entropy", (bf16_t*)logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, loss_out,
+                               write_grad, label_smoothing, z_loss, row_parts, (hipStream_t)stream);
+  return cross_entropy_chain("oasr_test_cross_entropy", (float*)logits, ld, V, targets, rows, ignore, gscale, n_valid_dev, row_loss, loss_out,
+                             write_grad, label_smoothing, z_loss, row_parts, (hipStream_t)stream);
 }
 extern "C" int oasr_cross_entropy(void* logits, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                                   int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream) {

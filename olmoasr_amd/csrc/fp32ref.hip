@@ -467,9 +467,16 @@ __global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits,
   }
   mx = block_reduce_f(mx, red, true);
   if (REG) xs = block_reduce_f(xs, red, false);
-  float sum = 0.f;
-  for (int c = threadIdx.x; c < V; c += 256) sum += expf(lr[c] - mx);
-  sum = block_reduce_f(sum, red, false);
+  // sum exp in double: a thread that holds the row maximum adds ~V / 256 small terms to 1.0, each add rounding at 2^-24 of the total; at a
+  // confident target (p - 1) g keeps that error whole, 2^-24 g per add (tests/test_gpu_vocab_planted.py, the peaked and offset rows)
+  __shared__ double redd[4];
+  double ds = 0.0;
+  for (int c = threadIdx.x; c < V; c += 256) ds += (double)expf(lr[c] - mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ds += __shfl_xor(ds, o, 64);
+  if ((threadIdx.x & 63) == 0) redd[threadIdx.x >> 6] = ds;
+  __syncthreads();
+  const float sum = (float)((redd[0] + redd[1]) + (redd[2] + redd[3]));
   const float lse = mx + logf(sum);
   const float ev = REG ? eps / (float)V : 0.f;
   if (threadIdx.x == 0) {
@@ -486,12 +493,15 @@ __global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits,
   }
   if (!write_grad) return;
   __syncthreads();
+  // softmax as exp(x - max) / sum, the bf16 kernel's form: exp(x - lse) carries the rounding of lse, |lse| 2^-24 relative, into every column,
+  // and at a confident target, where (p - 1) g cancels, that alone is 2^-24 |lse| g (tests/test_gpu_vocab_planted.py, the peaked rows)
   const float g = gscale / (float)max(1, *n_valid_dev);
   if (REG) {
-    const float k = 1.f + 2.f * zc * lse;
-    for (int c = threadIdx.x; c < ld; c += 256) lr[c] = c < V ? (k * expf(lr[c] - lse) - (c == tgt ? 1.f - eps : 0.f) - ev) * g : 0.f;
+    const float sg = g * (1.f + 2.f * zc * lse) / sum, gt = g * (1.f - eps), ge = g * ev;
+    for (int c = threadIdx.x; c < ld; c += 256) lr[c] = c < V ? expf(lr[c] - mx) * sg - ge - (c == tgt ? gt : 0.f) : 0.f;
   } else {
-    for (int c = threadIdx.x; c < ld; c += 256) lr[c] = c < V ? (expf(lr[c] - lse) - (c == tgt ? 1.f : 0.f)) * g : 0.f;
+    const float sg = g / sum;
+    for (int c = threadIdx.x; c < ld; c += 256) lr[c] = c < V ? expf(lr[c] - mx) * sg - (c == tgt ? g : 0.f) : 0.f;
   }
 }
 

@@ -267,7 +267,8 @@ int launch_dlogits_from_f32(const float* src, int V, long rows, long ld, float* 
 // ---- loss -------------------------------------------------------------------------------------------------
 // logits bf16 [rows][ld] (first V entries valid).  Writes, in place, dlogits = (softmax - onehot) * gscale / n_valid
 // (zeros for ignored rows and pad columns), row_loss[r] = lse - logit[target] (0 for ignored rows).
-// n_valid_dev: device int32 (count of targets != ignore).  loss_out += sum(row_loss)/n_valid * loss_mul.
+// n_valid_dev: device int32 (count of targets != ignore inside [0, V): an id outside that range is an ignored row, not an error).
+// loss_out += sum(row_loss)/n_valid * loss_mul.  Columns [V, ld) may hold anything on entry, NaN included; write_grad = 0 leaves the logits untouched.
 int launch_count_valid(const int64_t* targets, long rows, long ignore, int V, int32_t* n_valid_dev, hipStream_t s);
 // CeReg: the regularisers of the objective (include/oasr.h at oasr_train_step_args.label_smoothing); all zero = the plain kernel, launch for
 // launch.  Otherwise row_loss[r] = lse - (1 - eps) x_t - eps / V sum_{c<V} x_c + z lse^2, dlogits = g [(1 + 2 z lse) softmax - (1 - eps) onehot
@@ -288,6 +289,8 @@ int launch_loss_reduce(const float* row_loss, long rows, const int32_t* n_valid_
                        hipStream_t s);
 
 // tok[r] = argmax_c (logits[r][c] + mask[c] + mask2[c]) (lowest index on ties), logprob[r] = log_softmax of that entry (optional)
+// The empty row, for this launcher and the three below: a row in which no column survives (every entry -inf after the masks and the rules) gives
+// token 0 and log-probability -inf -- never NaN -- and top-k entries past the last survivor are (0, -inf) likewise.  Columns [V, ld) are never read.
 int launch_pick_tokens(const float* logits, long ld, int V, long rows, const float* mask, const float* mask2, int64_t* tok, float* logprob,
                        hipStream_t s);
 // + whisper's ApplyTimestampRules evaluated from the device-resident sampled history (loss.hip::pick_ts_kernel)

@@ -135,10 +135,25 @@ __global__ __launch_bounds__(CE_THREADS, REG ? 8 : 1) void ce_kernel(bf16_t* __r
     const int ch = threadIdx.x + CE_THREADS * c;
     if (ch < nchunk) {
       float e[8];
+      float tmin = 0.f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        e[2 * i] = __builtin_amdgcn_exp2f(fmaf(bf_lo(v[c][i]), L2E, nm2)) * sg;
-        e[2 * i + 1] = __builtin_amdgcn_exp2f(fmaf(bf_hi(v[c][i]), L2E, nm2)) * sg;
+        const float t0 = fmaf(bf_lo(v[c][i]), L2E, nm2), t1 = fmaf(bf_hi(v[c][i]), L2E, nm2);
+        tmin = fminf(tmin, fminf(t0, t1));
+        e[2 * i] = __builtin_amdgcn_exp2f(t0) * sg;
+        e[2 * i + 1] = __builtin_amdgcn_exp2f(t1) * sg;
+      }
+      // v_exp_f32 flushes a softmax below 2^-126 to zero, but its gradient is sg (up to ~gscale) times larger and can be a normal number:
+      // a chunk that holds a logit more than 87 below the row maximum redoes those columns scaled by 2^64 (t + 64 is exact there).  Every
+      // other chunk computes what it did before; the sum pass needs no such care (a flushed term is below 2^-126 of a sum >= 1).
+      if (tmin < -126.f) {
+        const float sgs = sg * 0x1p-64f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float t0 = fmaf(bf_lo(v[c][i]), L2E, nm2), t1 = fmaf(bf_hi(v[c][i]), L2E, nm2);
+          if (t0 < -126.f) e[2 * i] = __builtin_amdgcn_exp2f(t0 + 64.f) * sgs;
+          if (t1 < -126.f) e[2 * i + 1] = __builtin_amdgcn_exp2f(t1 + 64.f) * sgs;
+        }
       }
       if (REG) {
 #pragma unroll
@@ -248,7 +263,8 @@ __global__ __launch_bounds__(256) void pick_kernel(const float* __restrict__ log
   }
   if (threadIdx.x == 0) {
     tok[blockIdx.x] = besti == 0x7fffffff ? 0 : besti;
-    if (logprob) logprob[blockIdx.x] = -__logf(sum);
+    // a row without a survivor (every x = -inf): exp(-inf - -inf) above is NaN; the contract is (0, -inf) (kernels.h at launch_pick_tokens)
+    if (logprob) logprob[blockIdx.x] = best > -INFINITY ? -__logf(sum) : -INFINITY;
   }
 }
 

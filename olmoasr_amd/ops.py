@@ -847,3 +847,15 @@ def argmax_rows_(logits, V, rows, span, pred_out):
     B, S = pred_out.shape
     N.call("oasr_test_argmax_rows", logits, _dt(logits), logits.stride(0), V, logits.shape[0], rows, span, B, S, pred_out, N.STREAM)
     return pred_out
+
+
+def cross_entropy_test_(logits, V, targets, ignore, gscale=1.0, write_grad=True, label_smoothing=0.0, z_loss=0.0):
+    """include/oasr_testing.h: oasr_test_cross_entropy -- ``cross_entropy_`` on bf16 (the production kernel) or fp32 (the fp32 engine's kernel)
+    logits [rows, ld], in place.  Returns (loss f32 [1], row_loss f32 [rows], n_valid int32 [1])."""
+    rows = logits.shape[0]
+    nv = torch.zeros(1, device=logits.device, dtype=torch.int32)
+    row_loss = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    loss = torch.zeros(1, device=logits.device, dtype=torch.float32)
+    N.call("oasr_test_cross_entropy", logits, _dt(logits), logits.stride(0), V, targets, rows, ignore, gscale, nv, row_loss, loss,
+           int(write_grad), float(label_smoothing), float(z_loss), None, N.STREAM)
+    return loss, row_loss, nv
