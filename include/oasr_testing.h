@@ -62,10 +62,23 @@ int oasr_gemm_force_general(int on); /* tests: route every GEMM through the regi
 int oasr_test_gemm(const oasr_gemm_args* a, float* colsum_scratch, int atomic_on_pp, int raster_gm, int stagger, int stagger_phases, void* stream);
 /* tests: which kernels ran.  One text line per GEMM launch since oasr_profile_gemm(1), in launch order (oasr_profile_gemm_collect clears them):
  * "symbol\tM\tN\tK\tta\ttb\tflags\tsplit_k\tatomic\tatomic_on_pp\tscratch\tstagger\tstagger_phases\tpersistent\tlane\n" -- flags: the epilogue flag word
- * of csrc/gemm.hip (EPI_BIAS = 1, RESID 2, U 4, UDERIV 8, PRE 16, OUT 32, GELU 64, DERIV 128, POS 256, SCALE 512, NT_ST 1024, NT_LD 2048); scratch: a
+ * of csrc/gemm_common.h (EPI_BIAS = 1, RESID 2, U 4, UDERIV 8, PRE 16, OUT 32, GELU 64, DERIV 128, POS 256, SCALE 512, NT_ST 1024, NT_LD 2048); scratch: a
  * colsum_scratch came with colsum (the fused kernels then write partial rows instead of atomics); stagger: as the launch carried it (automatic rule applied); persistent: ping-pong kernel launched with
  * one workgroup per CU.  Returns the number of records (< 0: `cap` bytes do not hold them).  Does not synchronise. */
 int oasr_profile_gemm_records(char* buf, int cap);
+/* tests (CPU, tests/test_gemm_route_cpu.py): the kernel choice of oasr_gemm (csrc/gemm.hip: gemm_route) for a call described by plain integers --
+ * no device pointer, nothing launched, and the process-wide hooks above are NOT read: the forced path and the schedule override are parameters.
+ * The call is taken to pass oasr_gemm's argument checks (N % 4 == 0, K % 8 == 0 for a k-contiguous operand, ...).
+ *   M, N, K, ta, tb, split_k, atomic, atomic_on_pp: as in oasr_gemm_args / oasr_test_gemm; a_view, b_view: the operand is a conv-window view;
+ *   outputs: bit 0 out, 1 out_pre, 2 out_f32;  sides: bit 0 bias, 1 resid, 2 dgelu_u, 3 pos;  ldc, ldr, ldu: their leading dimensions;
+ *   misalign: the low four address bits of out / out_pre / resid / dgelu_u or-ed together (0 = all 16-byte aligned);
+ *   colsum, colsum_scratch: given or not;  forced_path: the code of oasr_gemm_force_general (0 = automatic);  pp_schedule: 2, 7 or -1 = the
+ *   per-layout default (oasr_gemm_set_variant bits 0-3);  geom_env: the OASR_GEMM_GEOM experiment value (0 = none).
+ * symbol (cap bytes) receives the kernel symbol exactly as oasr_profile_gemm_records prints it, *post the step that follows the kernel:
+ * 0 = none, 1 = column sums reduced from `out`, 2 = column sums reduced from the colsum_scratch rows. */
+int oasr_gemm_route_debug(int M, int N, int K, int ta, int tb, int a_view, int b_view, int split_k, int atomic, int atomic_on_pp, int outputs,
+                          int sides, long long ldc, long long ldr, long long ldu, int misalign, int colsum, int colsum_scratch, int forced_path,
+                          int pp_schedule, int geom_env, char* symbol, int cap, int* post);
 int oasr_profile_gemm_collect(double* ms4, double* flops4, int64_t* count4, char* by_symbol /* "symbol\tlaunches\tms\tflops\n"... or NULL */, int cap);
 int oasr_probe_lds_oob(const void* src_u16 /*[512]*/, void* dst_u16 /*[512]*/, void* stream);
 int oasr_probe_tr16(const void* src_bf16 /*[16][64]*/, void* dst_bf16 /*[64 lanes][4]*/, void* stream);

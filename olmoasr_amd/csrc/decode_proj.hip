@@ -5,7 +5,7 @@
 // (B <= 4: the timestamp-mode transcribe loop decodes ONE window at a time) the LayerNorm in front of a projection is folded into
 // the projection's operand load: every workgroup recomputes the B row statistics (B rows of d) and normalises the rows on their
 // way into the MFMA operands (8 launches per layer instead of 11; bit-identical to the separate kernels: same rounding points --
-// bf16 LN output, bf16 Linear output before GELU / residual -- same skinny-GEMM accumulation scheme as gemm.hip: 32 output columns
+// bf16 LN output, bf16 Linear output before GELU / residual -- same skinny-GEMM accumulation scheme as gemm_general.hip: 32 output columns
 // per workgroup, K split over the 4 waves, weights streamed once straight into MFMA operands).  From B = 16 the recomputed
 // statistics cost more than the launches they save (+20 %, profiles/r02_decode_step.txt), so larger batches keep the separate
 // LayerNorm kernels.  (Round 2 also carried a ONE-launch step built on this phase body with device-wide barriers between phases;

@@ -273,7 +273,7 @@ struct Runner {
     const long kt = cdiv(M, 64);
     // Split-K choice (scripts/wgrad_sweep.py): 768 workgroups are resident at once (3 per CU); what matters is how the
     // tiles x split grid quantises onto them (1.33 waves is the worst case), the (16 + split) K-tiles' worth of atomic epilogue
-    // every workgroup adds, and that multiples of 8 let every XCD own whole K-ranges (gemm.hip).
+    // every workgroup adds, and that multiples of 8 let every XCD own whole K-ranges (gemm_fast.hip).
     long split = 1;
     double best = 1e30;
     static const int cand[] = {1, 2, 4, 8, 16, 24, 32};

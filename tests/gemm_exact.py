@@ -47,6 +47,46 @@ PAD_COLS = 72
 COL0 = 8  # the view starts this many elements into each row of the allocation (16-byte aligned for bf16 and fp32)
 U_VALUES = (0.0, 0.25, -0.25, 0.5, -0.5, 1.0, -1.0, 2.0, -2.0)
 
+# The kernel paths the GPU suite forces (tests/test_gpu_gemm_exact.py) and the hand-written rule of which call can run on which;
+# tests/test_gemm_route_cpu.py holds the rule to the library's own route (csrc/gemm.hip: gemm_route) without a GPU.
+# path -> (oasr_gemm_force_general mode, oasr_gemm_set_variant value, kernel family)
+PATHS = {
+    "general": (1, -1, "general"),
+    "fast128": (2, -1, "fast128"),
+    "fast256": (3, -1, "fast256"),
+    "pp": (4, 24, "pp"),                          # default schedule, plain launch
+    "pp_nt": (4, 24 | 64 | 128, "pp"),            # + non-temporal epilogue stores and side-input loads
+    "pp_persistent": (4, 40, "pp"),               # one workgroup per CU walking the plain launch's grid
+    "pp_persistent_nt": (4, 40 | 64 | 128, "pp"),
+    "skinny": (0, -1, "skinny"),
+}
+
+
+def family_of(symbol):
+    if symbol.startswith("gemm_kernel<"):
+        return "general"
+    if symbol.startswith("gemm_skinny_kernel<"):
+        return "skinny"
+    if symbol.startswith("oasr_gemm_pp_kernel<"):
+        return "pp"
+    assert symbol.startswith("oasr_gemm_fast_kernel<"), symbol
+    return "fast128" if symbol.split(", ")[2] == "128" else "fast256"
+
+
+def takes(path, M, N, K, ta, tb, *, atomic_only=False, f32=False):
+    """launch_gemm's routing rules: can a call of this shape run on ``path`` (forced as PATHS says)?"""
+    if N % 4 or ((not ta or not tb) and K % 8):
+        return False
+    fam = PATHS[path][2]
+    if fam == "general":
+        return True
+    if fam == "skinny":
+        return M <= 64 and not ta and not tb and K % 64 == 0 and not atomic_only
+    ok = K % 64 == 0 and (not ta or M % 8 == 0) and (not tb or N % 8 == 0) and M >= 8 and N >= 8 and (atomic_only or (not f32 and N % 8 == 0))
+    if path.startswith("pp_persistent"):  # (the ping-pong launcher, csrc/gemm_pp.hip: more virtual blocks than CUs; this suite only uses it unsplit)
+        ok = ok and not atomic_only and ((M + 255) // 256) * ((N + 255) // 256) > 256
+    return ok
+
 
 def amplitude(K):
     """Regime R: 15 while K a^2 < 2^24, then 7 (the 192,000-token weight gradients), then 5 (conv1's 384,000 window rows)."""

@@ -31,17 +31,7 @@ BF = torch.bfloat16
 F64 = torch.float64
 LAYOUTS = {"NT": (False, False), "NN": (False, True), "TN": (True, False), "TT": (True, True)}
 
-# path -> (oasr_gemm_force_general mode, oasr_gemm_set_variant value, kernel family)
-PATHS = {
-    "general": (1, -1, "general"),
-    "fast128": (2, -1, "fast128"),
-    "fast256": (3, -1, "fast256"),
-    "pp": (4, 24, "pp"),                          # default schedule, plain launch
-    "pp_nt": (4, 24 | 64 | 128, "pp"),            # + non-temporal epilogue stores and side-input loads
-    "pp_persistent": (4, 40, "pp"),               # one workgroup per CU walking the plain launch's grid
-    "pp_persistent_nt": (4, 40 | 64 | 128, "pp"),
-    "skinny": (0, -1, "skinny"),
-}
+PATHS, takes, family_of = gx.PATHS, gx.takes, gx.family_of  # (shared with tests/test_gemm_route_cpu.py, which holds them to the library's route)
 FLAG = dict(BIAS=1, RESID=2, U=4, UDERIV=8, PRE=16, OUT=32, GELU=64, DERIV=128, POS=256, SCALE=512, NT_ST=1024, NT_LD=2048)
 COVERED = set()  # ledger keys of the cases that ran (e)
 
@@ -51,36 +41,10 @@ def ops():
     return o
 
 
-def family_of(symbol):
-    if symbol.startswith("gemm_kernel<"):
-        return "general"
-    if symbol.startswith("gemm_skinny_kernel<"):
-        return "skinny"
-    if symbol.startswith("oasr_gemm_pp_kernel<"):
-        return "pp"
-    assert symbol.startswith("oasr_gemm_fast_kernel<"), symbol
-    return "fast128" if symbol.split(", ")[2] == "128" else "fast256"
-
-
 def ledger_key(r):
     """What (e) compares: layout and kernel variant are part of the symbol; the non-temporal policy bits are not a launch property."""
     return (r["symbol"], r["flags"] & ~(FLAG["NT_ST"] | FLAG["NT_LD"]), r["N"], r["K"], r["split_k"], r["atomic_on_pp"],
             int(r["stagger"] > 0 and r["stagger_phases"] > 1))
-
-
-def takes(path, M, N, K, ta, tb, *, atomic_only=False, f32=False):
-    """launch_gemm's routing rules: can a call of this shape run on ``path`` (forced as PATHS says)?"""
-    if N % 4 or ((not ta or not tb) and K % 8):
-        return False
-    fam = PATHS[path][2]
-    if fam == "general":
-        return True
-    if fam == "skinny":
-        return M <= 64 and not ta and not tb and K % 64 == 0 and not atomic_only
-    ok = K % 64 == 0 and (not ta or M % 8 == 0) and (not tb or N % 8 == 0) and M >= 8 and N >= 8 and (atomic_only or (not f32 and N % 8 == 0))
-    if path.startswith("pp_persistent"):  # (launch_pp_variant: more virtual blocks than CUs; this suite only uses it unsplit)
-        ok = ok and not atomic_only and ((M + 255) // 256) * ((N + 255) // 256) > 256
-    return ok
 
 
 class forced:
@@ -379,7 +343,7 @@ def test_edge_conv_window_views(which):
 # ======================================================================================================================================
 # b. epilogues, regime S
 # ======================================================================================================================================
-# name -> (layout, options).  The first seven are gemm.hip's EPI_MODES in order; the rest take the generic instantiation (MODE < 0).
+# name -> (layout, options).  The first seven are gemm_common.h's EPI_MODES in order; the rest take the generic instantiation (MODE < 0).
 EPILOGUES = {
     "bias": ("NT", dict(bias=1)),
     "bias_resid": ("NT", dict(bias=1, resid=1)),
