@@ -288,25 +288,33 @@ int launch_cross_entropy(float* logits, long ld, int V, const int64_t* targets, 
 int launch_loss_reduce(const float* row_loss, long rows, const int32_t* n_valid_dev, float mul, float* loss_out, int accumulate,
                        hipStream_t s);
 
+// ---- token selection (select.hip) ---------------------------------------------------------------------------------------------------
+// The argument block of the four launchers, in the order of the C ABI (include/oasr.h at oasr_pick_tokens_ts): logits fp32 [rows][ld], V
+// columns valid; mask / mask2: optional additive fp32 [V] (0 / -inf); hist int64 [rows][hist_ld], n_hist tokens sampled so far, and the
+// token ids whisper's ApplyTimestampRules needs (n_hist < 0: no timestamp rules, none of these is read); tok / logprob: the outputs.
+struct SelectArgs {
+  const float* logits;
+  long ld;
+  int V;
+  long rows;
+  const float *mask, *mask2;
+  const int64_t* hist = nullptr;
+  long hist_ld = 0;
+  int n_hist = -1, ts_begin = 0, eot = 0, no_ts = 0, max_initial_index = -1;
+  int64_t* tok = nullptr;
+  float* logprob = nullptr;
+};
 // tok[r] = argmax_c (logits[r][c] + mask[c] + mask2[c]) (lowest index on ties), logprob[r] = log_softmax of that entry (optional)
 // The empty row, for this launcher and the three below: a row in which no column survives (every entry -inf after the masks and the rules) gives
 // token 0 and log-probability -inf -- never NaN -- and top-k entries past the last survivor are (0, -inf) likewise.  Columns [V, ld) are never read.
-int launch_pick_tokens(const float* logits, long ld, int V, long rows, const float* mask, const float* mask2, int64_t* tok, float* logprob,
-                       hipStream_t s);
-// + whisper's ApplyTimestampRules evaluated from the device-resident sampled history (loss.hip::pick_ts_kernel)
-int launch_pick_tokens_ts(const float* logits, long ld, int V, long rows, const float* mask, const float* mask2, const int64_t* hist,
-                          long hist_ld, int n_hist, int ts_begin, int eot, int no_ts, int max_initial_index, int64_t* tok, float* logprob,
-                          hipStream_t s);
-
+int launch_pick_tokens(const SelectArgs& a, hipStream_t s);  // (no rules: reads neither the history nor the ids)
+// + whisper's ApplyTimestampRules evaluated from the device-resident sampled history (n_hist >= 0 required)
+int launch_pick_tokens_ts(const SelectArgs& a, hipStream_t s);
 // the K best (log_softmax, token) pairs per row over the same filtered distribution (n_hist < 0: masks only, no timestamp rules):
 // tok / logprob [rows][K] -- BeamSearchDecoder.update's topk(beam_size + 1)
-int launch_topk_tokens_ts(const float* logits, long ld, int V, long rows, const float* mask, const float* mask2, const int64_t* hist,
-                          long hist_ld, int n_hist, int ts_begin, int eot, int no_ts, int max_initial_index, int K, int64_t* tok,
-                          float* logprob, hipStream_t s);
+int launch_topk_tokens_ts(const SelectArgs& a, int K, hipStream_t s);
 // one draw per row from softmax(filtered logits / temperature) by inverse CDF on u[row] in [0, 1); logprob at temperature 1
-int launch_sample_tokens_ts(const float* logits, long ld, int V, long rows, const float* mask, const float* mask2, const int64_t* hist,
-                            long hist_ld, int n_hist, int ts_begin, int eot, int no_ts, int max_initial_index, float temperature,
-                            const float* u, int64_t* tok, float* logprob, hipStream_t s);
+int launch_sample_tokens_ts(const SelectArgs& a, float temperature, const float* u, hipStream_t s);
 
 // ---- word-timestamp alignment (align.hip; the argument block and the contracts: include/oasr.h) ---------------------------------
 // score planes of the selected heads, read in place -> fp32 [n_tok, n_frames]; workspace of oasr_alignment_workspace_bytes

@@ -192,7 +192,7 @@ def _decode(model, mel, options, tokenizer, kwargs):
     if options.patience is not None and options.beam_size is None:
         raise ValueError("patience requires beam_size to be given")
     if options.beam_size is not None and not 1 <= options.beam_size <= MAX_BEAM_SIZE:
-        # the selection kernel keeps beam_size + 1 candidates per row in registers (csrc/loss.hip: topk_ts_kernel, K <= 16); whisper and
+        # the selection kernel keeps beam_size + 1 candidates per row in registers (csrc/select.hip: topk_ts_kernel, K <= 16); whisper and
         # the reference's eval use 5 (eval.py:2077-2084).  Refused up front instead of failing inside the first step.
         raise ValueError(f"beam_size must be in [1, {MAX_BEAM_SIZE}] on the native selection kernel, got {options.beam_size}")
     if options.length_penalty is not None and not (0 <= options.length_penalty <= 1):

@@ -716,25 +716,10 @@ def pick_tokens(logits, mask=None, mask2=None, want_logprob=True):
     return tok, lp
 
 
-def pick_tokens_ts(logits, history, n_history, *, timestamp_begin, eot, no_timestamps, max_initial_index=None, mask=None, mask2=None):
-    """``pick_tokens`` with whisper's ApplyTimestampRules evaluated on the device: ``history`` int64 [rows, >= n_history] holds the
-    tokens sampled so far (after the sot sequence).  Returns (ids int64 [rows], log_softmax of the pick over the surviving columns)."""
-    N.require_gpu(logits, "logits")
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
-    rows, V = logits.shape
-    assert n_history == 0 or (history.dtype == torch.int64 and history.dim() == 2 and history.shape[0] == rows and history.stride(1) == 1
-                              and history.shape[1] >= n_history and history.device == logits.device)
-    tok = torch.empty(rows, device=logits.device, dtype=torch.int64)
-    lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
-    for m in (mask, mask2):
-        assert m is None or (m.dtype == torch.float32 and m.numel() == V and m.is_contiguous())
-    N.call("oasr_pick_tokens_ts", logits, logits.stride(0), V, rows, mask, mask2, history if n_history else None,
-           history.stride(0) if n_history else 0, int(n_history), int(timestamp_begin), int(eot), int(no_timestamps),
-           -1 if max_initial_index is None else int(max_initial_index), tok, lp, N.STREAM)
-    return tok, lp
-
-
-def _ts_args(logits, history, n_history, mask, mask2):
+def _ts_args(logits, history, n_history, ids, mask, mask2, k=None):
+    """What the three rule-aware selections share: the checks, the native arguments from ``logits`` to ``max_initial_index`` (``ids``:
+    timestamp_begin, eot, no_timestamps, max_initial_index; ``n_history`` None: no timestamp rules) and the two outputs, ids int64 and
+    log-probabilities f32 of shape [rows] or [rows, k]."""
     N.require_gpu(logits, "logits")
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     rows, V = logits.shape
@@ -744,7 +729,19 @@ def _ts_args(logits, history, n_history, mask, mask2):
     for m in (mask, mask2):
         assert m is None or (m.dtype == torch.float32 and m.numel() == V and m.is_contiguous())
     nh = -1 if n_history is None else int(n_history)
-    return rows, V, (history if nh > 0 else None), (history.stride(0) if nh > 0 else 0), nh
+    shape = (rows,) if k is None else (rows, k)
+    tok = torch.empty(shape, device=logits.device, dtype=torch.int64)
+    lp = torch.empty(shape, device=logits.device, dtype=torch.float32)
+    return (logits, logits.stride(0), V, rows, mask, mask2, (history if nh > 0 else None), (history.stride(0) if nh > 0 else 0), nh,
+            int(ids[0]), int(ids[1]), int(ids[2]), -1 if ids[3] is None else int(ids[3])), tok, lp
+
+
+def pick_tokens_ts(logits, history, n_history, *, timestamp_begin, eot, no_timestamps, max_initial_index=None, mask=None, mask2=None):
+    """``pick_tokens`` with whisper's ApplyTimestampRules evaluated on the device: ``history`` int64 [rows, >= n_history] holds the
+    tokens sampled so far (after the sot sequence).  Returns (ids int64 [rows], log_softmax of the pick over the surviving columns)."""
+    args, tok, lp = _ts_args(logits, history, int(n_history), (timestamp_begin, eot, no_timestamps, max_initial_index), mask, mask2)
+    N.call("oasr_pick_tokens_ts", *args, tok, lp, N.STREAM)
+    return tok, lp
 
 
 def topk_tokens(logits, k, *, history=None, n_history=None, timestamp_begin=50363, eot=50256, no_timestamps=50362, max_initial_index=None,
@@ -752,11 +749,8 @@ def topk_tokens(logits, k, *, history=None, n_history=None, timestamp_begin=5036
     """The k best (log_softmax value, token) pairs per row of the filtered distribution (suppress masks; ``n_history`` not None: whisper's
     ApplyTimestampRules from ``history``, as ``pick_tokens_ts``) -- BeamSearchDecoder.update's ``logprobs.topk(beam_size + 1)`` in one
     kernel.  Returns (logprob f32 [rows, k] descending, ids int64 [rows, k])."""
-    rows, V, hp, hld, nh = _ts_args(logits, history, n_history, mask, mask2)
-    tok = torch.empty(rows, k, device=logits.device, dtype=torch.int64)
-    lp = torch.empty(rows, k, device=logits.device, dtype=torch.float32)
-    N.call("oasr_topk_tokens", logits, logits.stride(0), V, rows, mask, mask2, hp, hld, nh, int(timestamp_begin), int(eot), int(no_timestamps),
-           -1 if max_initial_index is None else int(max_initial_index), int(k), tok, lp, N.STREAM)
+    args, tok, lp = _ts_args(logits, history, n_history, (timestamp_begin, eot, no_timestamps, max_initial_index), mask, mask2, k)
+    N.call("oasr_topk_tokens", *args, int(k), tok, lp, N.STREAM)
     return lp, tok
 
 
@@ -764,12 +758,9 @@ def sample_tokens(logits, temperature, uniforms, *, history=None, n_history=None
                   max_initial_index=None, mask=None, mask2=None):
     """One draw per row from softmax(filtered logits / temperature) by inverse CDF on ``uniforms`` (f32 [rows] in [0, 1)); returns
     (ids int64 [rows], log_softmax of the draw at temperature 1) -- GreedyDecoder.update at temperature > 0."""
-    rows, V, hp, hld, nh = _ts_args(logits, history, n_history, mask, mask2)
-    assert uniforms.dtype == torch.float32 and uniforms.numel() == rows and uniforms.device == logits.device
-    tok = torch.empty(rows, device=logits.device, dtype=torch.int64)
-    lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
-    N.call("oasr_sample_tokens", logits, logits.stride(0), V, rows, mask, mask2, hp, hld, nh, int(timestamp_begin), int(eot), int(no_timestamps),
-           -1 if max_initial_index is None else int(max_initial_index), float(temperature), uniforms, tok, lp, N.STREAM)
+    args, tok, lp = _ts_args(logits, history, n_history, (timestamp_begin, eot, no_timestamps, max_initial_index), mask, mask2)
+    assert uniforms.dtype == torch.float32 and uniforms.numel() == logits.shape[0] and uniforms.device == logits.device
+    N.call("oasr_sample_tokens", *args, float(temperature), uniforms, tok, lp, N.STREAM)
     return tok, lp
 
 

@@ -1,5 +1,5 @@
-"""The kernels of csrc/loss.hip -- ce_kernel<REG>, count_valid, loss_reduce, pick / pick_ts / topk_ts / sample_ts -- and the fp32 engine's
-ce_f32_kernel on the planted rows of tests/vocab_planted.py, against float64.  The cases, the bounds and the check functions live there
+"""The kernels of csrc/loss.hip -- ce_kernel<REG>, count_valid, loss_reduce --, those of csrc/select.hip -- pick / pick_ts / topk_ts /
+sample_ts -- and the fp32 engine's ce_f32_kernel on the planted rows of tests/vocab_planted.py, against float64.  The cases, the bounds and the check functions live there
 (``check_ce``, ``check_topk``, ``check_sample``); tests/test_vocab_planted_cpu.py shows on the CPU that those checks catch a dropped
 register slot, a wave missing from a reduction, a loop bound off by a tile, a truncating store, ties to the wrong side and the like.
 
@@ -148,6 +148,26 @@ def test_selection_kernels(V):
         f = P.sel_failures(case, _gpu_run(case))
         if f:
             bad[case["name"]] = f
+    assert bad == {}, bad
+
+
+@pytest.mark.parametrize("V", P.SEL_V)
+def test_pick_ts_equals_topk_first(V):
+    """pick_ts_kernel stores what row_stat computes, and topk_ts_kernel's first entry is taken from the same row_stat: on every planted
+    case with rules ops.pick_tokens_ts and ops.topk_tokens(k = 1) give equal ids and log-probabilities that compare == (-inf == -inf on
+    the empty rows; a zero of either sign on a row with one survivor)."""
+    bad = {}
+    n = 0
+    for case in P.sel_cases(V):
+        if case["rules"] is None:
+            continue
+        n += 1
+        run = _gpu_run(case)
+        (tok, lp), (tok1, lp1) = run("pick"), run("topk", K=1)
+        rows = [r for r in range(tok.shape[0]) if int(tok[r]) != int(tok1[r, 0]) or not float(lp[r]) == float(lp1[r, 0])]
+        if rows:
+            bad[case["name"]] = [(r, int(tok[r]), int(tok1[r, 0]), float(lp[r]), float(lp1[r, 0])) for r in rows]
+    assert n > 0 or P.sel_ids(V) is None
     assert bad == {}, bad
 
 

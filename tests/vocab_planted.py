@@ -1,4 +1,4 @@
-"""Planted rows for the kernels of csrc/loss.hip (and the fp32 cross-entropy of csrc/fp32ref.hip): case builders, float64 expectations, the
+"""Planted rows for the kernels of csrc/loss.hip and csrc/select.hip (and the fp32 cross-entropy of csrc/fp32ref.hip): case builders, float64 expectations, the
 check functions the GPU suite applies, and stand-ins for the kernels with one deliberate flaw at a time (plain torch, no GPU needed).
 
 Seeded Gaussian rows at the full vocabulary say little about where these kernels can go wrong: which thread, register slot and wave owns a
