@@ -425,6 +425,58 @@ typedef struct oasr_edit_args {
 size_t oasr_sizeof_edit_args(void);
 int oasr_edit_counts(const oasr_edit_args*, void* stream);
 int oasr_edit_counts_host(const oasr_edit_args*);
+/* Device-resident beam search (csrc/beam.hip; the rule itself: csrc/beam_core.h): whisper's BeamSearchDecoder.update for every audio window
+ * of a batch in one launch, and rearrange_kv_cache as one in-place launch.  Entry points only: OASR_ABI_VERSION is unchanged, and a binding
+ * checks oasr_sizeof_beam_args like oasr_sizeof_edit_args.
+ *
+ * One update.  n = n_audio * beam rows, K = beam + 1 candidates per row, `len` tokens per row so far (the sot sequence included).
+ *   top_logprob f32 [n, K], top_token i64 [n, K]: oasr_topk_tokens' output.  tokens_in i64 [n, n_ctx]: the rows of this step; tokens_out i64
+ *   [n, n_ctx]: the rows of the next one (another buffer: rows are gathered).  sums f32 [n], in place.  sources i32 [n]: row r of the next
+ *   step continues row sources[r] (oasr_decode_reorder's index).  last_token i64 [n]: the token appended to row r (oasr_decode_step's input).
+ *   Pool of finished sequences per window: pool_tokens i64 [n_audio, max_candidates, n_ctx], pool_len i32 and pool_score f64 [n_audio,
+ *   max_candidates], pool_count i32 [n_audio].  Status: pool_full_len i32 [n_audio] = the `len` of the step that filled the window's pool
+ *   (OASR_BEAM_NOT_FULL until then; the caller initialises it, pool_count = 0 and short_step = 0), short_step i32 [n_audio].
+ * Per window: candidates in (row, k) order with key (row's prefix, token) and score (double)sum + (double)logprob; equal keys collapse to
+ * the first position with the score and origin row of the last; entries are ordered by score descending, position ascending; walking them,
+ * an eot entry is newly finished, any other becomes the next row of the window until `beam` rows exist, where the walk ends.  Row m of
+ * the window then holds the origin's `len` tokens + the token, sums = (float)score.  Newly finished entries enter the pool in walk order
+ * (tokens + eot, the double score) while it holds fewer than max_candidates.  Fewer than `beam` continuations: nothing of the window is
+ * written, short_step = 1 and the window is skipped from then on.  Once EVERY window's pool_full_len is below the step's `len` (all pools
+ * were full before this step) the step is latched: tokens_in's `len` tokens are copied to tokens_out unchanged, sources are the identity,
+ * and sums, last tokens and pools stay as they are -- a caller may therefore poll the status every few steps without changing a result.
+ * Nothing past token len of a row, and nothing outside the window's own rows and pool slots, is written.
+ * oasr_beam_update: device pointers, one launch on `stream`, one workgroup per window.  oasr_beam_update_host: HOST function (no GPU call,
+ * host pointers), the same rule from the same text.  Both refuse (OASR_EINVAL) null pointers, beam outside [1, OASR_BEAM_MAX],
+ * max_candidates < 1 and len outside [1, n_ctx).
+ *
+ * oasr_decode_reorder: row j of the KV cache continues row sources[j] (device i32 [B]) -- per decoder layer the self-attention K | V
+ * columns [d, 3d) of positions < pos move, in place; cross-attention K/V, the q slots, later positions and the control tail are not
+ * touched.  Every source must lie in its destination's group of `group` rows (1 <= group <= OASR_BEAM_MAX, B % group == 0): a group whose
+ * device index breaks that, or is the identity, is left as it is; sources_host (host i32 [B], may be NULL), when given, is the same index
+ * readable by the host and is checked first (OASR_EINVAL).  oasr_decode_reorder_host: HOST function, the same gather over a host copy of
+ * the self-attention rows (`rows`: L layers, `layer_stride` BYTES apart, each [B, n_ctx, 3d] elements of `elem_size` 2 or 4 bytes); a source
+ * outside its group is OASR_EINVAL before anything moves. */
+#define OASR_BEAM_MAX 15
+#define OASR_BEAM_NOT_FULL 0x7fffffff
+typedef struct oasr_beam_args {
+  const float* top_logprob;
+  const int64_t *top_token, *tokens_in;
+  int64_t* tokens_out;
+  float* sums;
+  int32_t* sources;
+  int64_t *last_token, *pool_tokens;
+  int32_t* pool_len;
+  double* pool_score;
+  int32_t *pool_count, *pool_full_len, *short_step;
+  int32_t n_audio, beam, max_candidates, n_ctx, len, reserved;
+  int64_t eot;
+} oasr_beam_args;
+size_t oasr_sizeof_beam_args(void);
+int oasr_beam_update(const oasr_beam_args*, void* stream);
+int oasr_beam_update_host(const oasr_beam_args*);
+int oasr_decode_reorder(oasr_ctx*, void* kv_cache, int B, int pos, int group, const int32_t* sources, const int32_t* sources_host, void* stream);
+int oasr_decode_reorder_host(void* rows, int64_t layer_stride, int L, int B, int n_ctx, int d, int elem_size, int pos, int group,
+                             const int32_t* sources);
 /* Speed perturbation (Ko et al. 2015; Kaldi's 0.9 / 1.0 / 1.1) of int16 PCM AHEAD of oasr_log_mel, with the transcript's timestamp tokens
  * moved along (csrc/speed.hip; the rule itself: csrc/speed_core.h).  Entry points only: OASR_ABI_VERSION is unchanged, and a binding checks
  * oasr_sizeof_speed and oasr_sizeof_speed_args like oasr_sizeof_specaug.  The operator is an integer function: int16 in, Q15 integer taps,

@@ -63,6 +63,14 @@ class EditArgs(C.Structure):  # include/oasr.h: oasr_edit_args
                 ("ld_hyp", C.c_int64), ("ld_ref", C.c_int64), ("B", C.c_int32), ("Lh", C.c_int32), ("Lr", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BeamArgs(C.Structure):  # include/oasr.h: oasr_beam_args
+    MAX_BEAM = 15  # OASR_BEAM_MAX
+    NOT_FULL = 0x7fffffff  # OASR_BEAM_NOT_FULL
+    _fields_ = [(n, C.c_void_p) for n in ("top_logprob", "top_token", "tokens_in", "tokens_out", "sums", "sources", "last_token", "pool_tokens",
+                                          "pool_len", "pool_score", "pool_count", "pool_full_len", "short_step")] + \
+               [(n, C.c_int32) for n in ("n_audio", "beam", "max_candidates", "n_ctx", "len", "reserved")] + [("eot", C.c_int64)]
+
+
 class Speed(C.Structure):  # include/oasr.h: oasr_speed
     MAX_FACTORS = 8  # OASR_SPEED_MAX_FACTORS
     _fields_ = [("n_factors", C.c_int32), ("P", C.c_int32 * 8), ("Q", C.c_int32 * 8)]
@@ -91,6 +99,7 @@ STRUCT_SIZES = [
     ("oasr_sizeof_align_args", AlignArgs),  # came with the word-timestamp operators (oasr_alignment_matrix, oasr_dtw)
     ("oasr_sizeof_specaug", SpecAug),  # came with oasr_spec_augment
     ("oasr_sizeof_edit_args", EditArgs),  # came with oasr_edit_counts and oasr_test_argmax_rows
+    ("oasr_sizeof_beam_args", BeamArgs),  # came with oasr_beam_update and oasr_decode_reorder
     ("oasr_sizeof_speed", Speed),  # came with oasr_speed_perturb
     ("oasr_sizeof_speed_args", SpeedArgs),
     ("oasr_sizeof_train_step_args", TrainStepArgs),  # last grown by label_smoothing / z_loss / loss_parts_*
@@ -190,6 +199,11 @@ def _declare(lib):
         "oasr_sizeof_edit_args": (sz, []),
         "oasr_edit_counts": (i32, [C.POINTER(EditArgs), vp]),
         "oasr_edit_counts_host": (i32, [C.POINTER(EditArgs)]),
+        "oasr_sizeof_beam_args": (sz, []),
+        "oasr_beam_update": (i32, [C.POINTER(BeamArgs), vp]),
+        "oasr_beam_update_host": (i32, [C.POINTER(BeamArgs)]),
+        "oasr_decode_reorder": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "oasr_decode_reorder_host": (i32, [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp]),
         "oasr_sizeof_speed": (sz, []),
         "oasr_sizeof_speed_args": (sz, []),
         "oasr_speed_perturb": (i32, [C.POINTER(SpeedArgs), vp]),

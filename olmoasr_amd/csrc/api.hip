@@ -208,6 +208,8 @@ extern "C" int oasr_spec_augment(float* mel, int B, int n_mels, int T, const oas
 
 extern "C" int oasr_edit_counts(const oasr_edit_args* a, void* stream) { return launch_edit_counts(a, (hipStream_t)stream); }
 
+extern "C" int oasr_beam_update(const oasr_beam_args* a, void* stream) { return launch_beam_update(a, (hipStream_t)stream); }
+
 extern "C" size_t oasr_sizeof_speed(void) { return sizeof(oasr_speed); }
 extern "C" size_t oasr_sizeof_speed_args(void) { return sizeof(oasr_speed_args); }
 extern "C" int oasr_speed_perturb(const oasr_speed_args* a, void* stream) { return launch_speed_perturb(a, (hipStream_t)stream); }

@@ -263,6 +263,24 @@ extern "C" int oasr_decode_step(oasr_ctx* c, const int64_t* tokens_last, int B, 
   return OASR_BY_DTYPE(c, oasr_decode_step_impl, c, tokens_last, B, pos, kv_cache, logits_out, workspace, workspace_bytes, stream);
 }
 
+// whisper's rearrange_kv_cache on the engine-owned cache, in place and in one launch (beam.hip: kv_reorder_kernel): row j continues row
+// sources[j] (device int32 [B]).  Only the self-attention k | v columns of positions < pos move; sources_host, when given, is the same index
+// where the host can read it, and an index that leaves its group of `group` rows is refused there before the launch.
+extern "C" int oasr_decode_reorder(oasr_ctx* c, void* kv_cache, int B, int pos, int group, const int32_t* sources, const int32_t* sources_host,
+                                   void* stream) {
+  OASR_REQUIRE(c && kv_cache && sources && B > 0, "oasr_decode_reorder: bad args");
+  OASR_REQUIRE(group >= 1 && group <= OASR_BEAM_MAX && B % group == 0, "oasr_decode_reorder: 1 <= group <= %d must divide B = %d", OASR_BEAM_MAX, B);
+  OASR_REQUIRE(pos >= 0 && pos <= c->S_max, "oasr_decode_reorder: pos = %d outside [0, %d]", pos, c->S_max);
+  if (sources_host)
+    for (int j = 0; j < B; ++j) {
+      const int lo = j / group * group;
+      OASR_REQUIRE(sources_host[j] >= lo && sources_host[j] < lo + group,
+                   "oasr_decode_reorder: row %d continues row %d, outside its group of %d rows (beams never cross windows)", j, sources_host[j], group);
+    }
+  const int esz = c->f32 ? 4 : 2;
+  return launch_kv_reorder(kv_cache, (long)(kv_layer_elems(c, B) * esz), c->L_dec, B, c->S_max, c->d, esz, pos, group, sources, (hipStream_t)stream);
+}
+
 // Synchronises the stream before the caller reads a window's tokens back (the step engines themselves cannot fail once enqueued).
 extern "C" int oasr_decode_check(oasr_ctx* c, int B, void* kv_cache, void* stream) {
   OASR_REQUIRE(c && kv_cache && B > 0, "oasr_decode_check: bad args");

@@ -328,6 +328,14 @@ int launch_dtw(const float* cost, long ld, int N, int M, int negate, int32_t* te
 struct oasr_edit_args;
 int launch_edit_counts(const oasr_edit_args* a, hipStream_t s);
 
+// ---- device-resident beam search (beam.hip; the contract: include/oasr.h at oasr_beam_update, the rule: beam_core.h) --------------------
+struct oasr_beam_args;
+int launch_beam_update(const oasr_beam_args* a, hipStream_t s);
+// row j of the self-attention cache continues row sources[j] (device int32 [B]), in place: per layer (layer_stride BYTES apart) the rows are
+// [B][n_ctx][3d] elements of elem_size bytes, and the columns [d, 3d) of positions < pos move; d * elem_size % 16 == 0
+int launch_kv_reorder(void* rows, long layer_stride, int L, int B, int n_ctx, int d, int elem_size, int pos, int group, const int32_t* sources,
+                      hipStream_t s);
+
 // ---- teacher-forced predictions of the span step (argmax.hip) --------------------------------------------------------------------------
 // pred[b, s] = argmax_c<V logits[rows[b][s >> 6] + (s & 63)][c] (lowest index among equal maxima) for s < span[b], else -1; logits
 // [n_rows][ld], rows int32 [B][OASR_ROWTAB], span int32 [B] (multiples of 64), pred int32 [B][S].  Reads each active row once.

@@ -23,7 +23,9 @@ Step engines: greedy / sampling run on the engine-owned KV cache (``kv_cache_beg
 suppress masks is one HIP kernel, ``oasr_pick_tokens`` -- in timestamp mode ``oasr_pick_tokens_ts``, which also applies
 ApplyTimestampRules from the device-resident token history, so the greedy loop never waits for the GPU); beam search runs on the
 same cache, its rows re-gathered in place between steps (``kv_cache_reorder`` = whisper's ``rearrange_kv_cache``,
-inf_model.py:422-453 hooks); ``use_kv_cache=False`` re-runs the decoder on the whole prefix each step (the pattern of
+inf_model.py:422-453 hooks) -- with ``beam_backend="native"`` the update itself (candidate merge, finished pool, patience) and that re-gather
+run on the device too, ``ops.beam_update`` + ``kv_cache_reorder_native``, bit-identical to the host path, which stays the default --;
+``use_kv_cache=False`` re-runs the decoder on the whole prefix each step (the pattern of
 notebooks/ow_decoding.py:42-72).
 """
 import zlib
@@ -78,6 +80,7 @@ class DecodingOptions:
     suppress_mask: Optional[torch.Tensor] = None     # extra additive mask [rows] (0 / -inf)
     seed: Optional[int] = None                       # sampling generator seed (temperature > 0)
     use_kv_cache: bool = True
+    beam_backend: str = "host"                       # "native": BeamSearchDecoder.update and the cache reorder stay on the device (ops.beam_update)
 
 
 @dataclass
@@ -195,6 +198,8 @@ def _decode(model, mel, options, tokenizer, kwargs):
         # the selection kernel keeps beam_size + 1 candidates per row in registers (csrc/select.hip: topk_ts_kernel, K <= 16); whisper and
         # the reference's eval use 5 (eval.py:2077-2084).  Refused up front instead of failing inside the first step.
         raise ValueError(f"beam_size must be in [1, {MAX_BEAM_SIZE}] on the native selection kernel, got {options.beam_size}")
+    if options.beam_size is not None and options.beam_backend not in ("host", "native"):
+        raise ValueError(f"beam_backend must be 'host' or 'native', got {options.beam_backend!r}")
     if options.length_penalty is not None and not (0 <= options.length_penalty <= 1):
         raise ValueError("length_penalty (alpha) should be a value between 0 and 1")
     single = mel.dim() == 2
@@ -247,7 +252,45 @@ def _decode(model, mel, options, tokenizer, kwargs):
             step_logits = model.kv_cache_step(state, tokens[:, p])
             if p == sot_index:
                 no_speech = torch.softmax(step_logits.float(), dim=-1)[::n_group, NO_SPEECH].tolist()
-    for i in range(sample_len):
+    native_beam = bool(beam) and options.beam_backend == "native"
+    if native_beam:
+        # BeamSearchDecoder.update on the device (ops.beam_update; the rule: csrc/beam_core.h): per step the decoder step, the selection, the
+        # merge and the cache reorder are enqueued back to back, and the host reads nothing but the status words, every 8th step like the
+        # greedy loop.  Once every pool is full the operator latches, so the surplus steps before the next poll change nothing.
+        if max_candidates < 1:
+            raise ValueError("beam_backend='native' needs round(beam_size * patience) >= 1")
+        bs = ops.beam_state(n_audio, beam, max_candidates, dims.n_text_ctx, init, dev)
+        for i in range(sample_len):
+            if cached:
+                lg = step_logits if i == 0 else model.kv_cache_step(state, bs.last_token)
+            elif i == 0:
+                full = model.logits(bs.tokens[:, :bs.len], xa_g)
+                no_speech = torch.softmax(full[:, sot_index].float(), dim=-1)[::n_group, NO_SPEECH].tolist()
+                lg = full[:, -1].contiguous()
+            else:
+                lg = model.logits(bs.tokens[:, :bs.len], xa_g, last_only=True)
+            top_lp, top_tok = ops.topk_tokens(lg.float().contiguous(), beam + 1, history=bs.tokens[:, sample_begin:],
+                                              n_history=None if options.without_timestamps else bs.len - sample_begin,
+                                              timestamp_begin=TIMESTAMP_BEGIN, eot=EOT, no_timestamps=NO_TIMESTAMPS, max_initial_index=max_init_idx,
+                                              mask=base_mask, mask2=first_mask if i == 0 else None)
+            ops.beam_update(bs, top_lp, top_tok, eot=EOT)
+            if cached:
+                model.kv_cache_reorder_native(state, bs.sources, beam)
+            if i % 8 == 7 or i == sample_len - 1:  # the only host read of the loop
+                completed, short, _, _ = bs.read_status()
+                if completed or short or bs.len > dims.n_text_ctx:
+                    break
+        completed, short, live_len, count = bs.read_status()
+        if short:  # fewer than beam_size continuations survived the masks: the host path fails on its ragged tensor at the same step
+            if state is not None and not model.kv_cache_check(state):
+                return _RETRY
+            raise RuntimeError("beam search: a step left fewer than beam_size continuations (too few tokens survive the suppress masks)")
+        pool_tok, pool_len, pool_score = bs.pool_tokens.cpu(), bs.pool_len.tolist(), bs.pool_score.tolist()
+        for a in range(n_audio):
+            for k in range(count[a]):
+                finished[a][tuple(pool_tok[a, k, :pool_len[a][k]].tolist())] = pool_score[a][k]
+        tokens, sum_logprobs = bs.tokens[:, :live_len], bs.sums
+    for i in range(0 if native_beam else sample_len):  # (the native beam loop above has run its steps already)
         if cached:
             lg = step_logits if i == 0 else model.kv_cache_step(state, tokens[:, -1])
         elif i == 0:

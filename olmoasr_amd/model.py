@@ -957,6 +957,17 @@ class OLMoASR(nn.Module):
             rows = flat[layer, :n_self].view(B, self.dims.n_text_ctx, 3 * d)[:, :pos, d:]
             rows.copy_(rows.index_select(0, idx))
 
+    @torch.no_grad()
+    def kv_cache_reorder_native(self, state, sources_dev: Tensor, group: int) -> None:
+        """``kv_cache_reorder`` as ONE in-place launch from a DEVICE index (oasr_decode_reorder; csrc/beam.hip): ``sources_dev`` int32 [B]
+        on the cache's device, e.g. ``ops.beam_update``'s ``state.sources``; row j continues row ``sources_dev[j]``, which must lie in j's
+        group of ``group`` rows (one audio window's beams).  Nothing is read back: a group whose index is the identity -- or leaves the
+        group -- is left as it is by the kernel.  The moved bytes are exactly those ``kv_cache_reorder`` moves."""
+        if not (isinstance(sources_dev, Tensor) and sources_dev.dtype == torch.int32 and sources_dev.is_contiguous()
+                and sources_dev.numel() == state["B"] and sources_dev.device == state["cache"].device):
+            raise ValueError(f"kv_cache_reorder_native: sources_dev must be a contiguous int32 [{state['B']}] on {state['cache'].device}")
+        N.call("oasr_decode_reorder", self._ctx, state["cache"], state["B"], state["pos"], int(group), sources_dev, None, N.STREAM)
+
     def kv_cache_check(self, state) -> bool:
         """Synchronises the stream (oasr_decode_check); call once per decoded window, before reading the tokens back.  False: the
         one-launch step engine could not keep its team resident (a shared or CU-masked device) and the context has switched to the

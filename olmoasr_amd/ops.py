@@ -454,6 +454,119 @@ def edit_counts_host(hyp, hyp_len, ref, ref_len):
     return out
 
 
+class BeamState:
+    """What a device-resident beam search keeps between steps (include/oasr.h at oasr_beam_update), on one device -- the GPU, or the CPU
+    for ``beam_update_host``: the two ``[n, n_ctx]`` int64 token buffers a step alternates between (``tokens`` is the current one, ``len``
+    tokens of each row are meaningful), the fp32 ``sums``, the int32 ``sources`` and int64 ``last_token`` of the last step, the pool of
+    finished sequences (``pool_tokens`` [n_audio, C, n_ctx], ``pool_len``, ``pool_score`` f64) and ONE int32 ``status`` tensor
+    [3, n_audio] = (pool_count, pool_full_len, short_step) so that a poll is a single device read.  Built by ``beam_state``."""
+
+    def __init__(self, n_audio, beam, max_candidates, n_ctx, init_tokens, device, fill=0, guard=0):
+        init = [int(t) for t in init_tokens]
+        if not 1 <= beam <= N.BeamArgs.MAX_BEAM:
+            raise ValueError(f"beam_state: beam must be in [1, {N.BeamArgs.MAX_BEAM}], got {beam}")
+        if n_audio < 1 or max_candidates < 1 or not 1 <= len(init) < n_ctx:
+            raise ValueError("beam_state: n_audio >= 1, max_candidates >= 1 and 1 <= len(init_tokens) < n_ctx")
+        self.n_audio, self.beam, self.max_candidates, self.n_ctx, self.len = n_audio, beam, max_candidates, n_ctx, len(init)
+        self.device, self.cur, self.backing, self.guard = torch.device(device), 0, {}, guard
+        n = n_audio * beam
+
+        def alloc(name, shape, dtype, value):  # `guard` rows of `fill` on either side of every tensor: nothing may write them
+            back = torch.full((shape[0] + 2 * guard, *shape[1:]), fill, dtype=dtype, device=self.device)
+            view = back[guard:guard + shape[0]]
+            if value is not None:
+                view.fill_(value)
+            self.backing[name] = back
+            return view
+        self.buffers = [alloc("tokens0", (n, n_ctx), torch.int64, None), alloc("tokens1", (n, n_ctx), torch.int64, None)]
+        self.buffers[0][:, :len(init)] = torch.tensor(init, dtype=torch.int64, device=self.device)
+        self.sums = alloc("sums", (n,), torch.float32, 0.0)
+        self.sources = alloc("sources", (n,), torch.int32, None)
+        self.sources.copy_(torch.arange(n, dtype=torch.int32, device=self.device))
+        self.last_token = alloc("last_token", (n,), torch.int64, init[-1])
+        self.pool_tokens = alloc("pool_tokens", (n_audio, max_candidates, n_ctx), torch.int64, None)
+        self.pool_len = alloc("pool_len", (n_audio, max_candidates), torch.int32, 0)
+        self.pool_score = alloc("pool_score", (n_audio, max_candidates), torch.float64, None)
+        self.status = alloc("status", (3, n_audio), torch.int32, 0)
+        self.status[1].fill_(N.BeamArgs.NOT_FULL)
+
+    @property
+    def tokens(self):
+        return self.buffers[self.cur]
+
+    def read_status(self):
+        """ONE device read: (completed, any short step, live length, pool counts).  ``completed``: every window's pool is full -- later
+        updates are latched and change nothing; the live rows then hold ``live length`` tokens, those of the step that completed."""
+        count, full_len, short = self.status.cpu().tolist()
+        completed = all(f != N.BeamArgs.NOT_FULL for f in full_len)
+        return completed, any(short), (max(full_len) + 1 if completed else self.len), count
+
+
+def beam_state(n_audio, beam, max_candidates, n_ctx, init_tokens, device, fill=0, guard=0):
+    """The state of a beam search over ``n_audio`` windows x ``beam`` rows whose rows all start as ``init_tokens`` (the sot sequence), with
+    pools of ``max_candidates`` finished sequences per window (``BeamState``).  ``fill`` / ``guard``: every tensor is allocated with ``guard``
+    extra rows on either side, and those rows, the unused token columns and the pool hold ``fill`` (tests plant a sentinel there)."""
+    return BeamState(n_audio, beam, max_candidates, n_ctx, init_tokens, device, fill, guard)
+
+
+def _beam_update(state, top_lp, top_tok, eot, cuda):
+    what = "beam_update" if cuda else "beam_update_host"
+    n, K = state.n_audio * state.beam, state.beam + 1
+    if not isinstance(state, BeamState) or (state.device.type == "cuda") != cuda:
+        raise ValueError(f"{what}: the state must live on the {'GPU' if cuda else 'CPU'}")
+    for t, nm, dt in ((top_lp, "top_lp", torch.float32), (top_tok, "top_tok", torch.int64)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == (n, K) and t.is_contiguous() and t.device == state.sums.device):
+            raise ValueError(f"{what}: {nm} must be a contiguous {dt} [{n}, {K}] (rows, beam + 1) on the state's device")
+    if state.len + 1 > state.n_ctx:
+        raise ValueError(f"{what}: the rows already hold n_ctx = {state.n_ctx} tokens")
+    a = N.BeamArgs()
+    a.top_logprob, a.top_token = top_lp.data_ptr(), top_tok.data_ptr()
+    a.tokens_in, a.tokens_out = state.buffers[state.cur].data_ptr(), state.buffers[1 - state.cur].data_ptr()
+    a.sums, a.sources, a.last_token = state.sums.data_ptr(), state.sources.data_ptr(), state.last_token.data_ptr()
+    a.pool_tokens, a.pool_len, a.pool_score = state.pool_tokens.data_ptr(), state.pool_len.data_ptr(), state.pool_score.data_ptr()
+    a.pool_count, a.pool_full_len, a.short_step = state.status[0].data_ptr(), state.status[1].data_ptr(), state.status[2].data_ptr()
+    a.n_audio, a.beam, a.max_candidates, a.n_ctx, a.len, a.eot = state.n_audio, state.beam, state.max_candidates, state.n_ctx, state.len, int(eot)
+    if cuda:
+        N.call("oasr_beam_update", C.byref(a), N.STREAM, device=state.sums.device)
+    else:
+        N.call("oasr_beam_update_host", C.byref(a))
+    state.cur, state.len = 1 - state.cur, state.len + 1
+    return state
+
+
+def beam_update(state, top_lp, top_tok, *, eot):
+    """One BeamSearchDecoder.update for every window of ``state`` in one launch and with no host read (include/oasr.h: oasr_beam_update;
+    the rule: csrc/beam_core.h): ``top_lp`` f32 / ``top_tok`` int64 [n_audio * beam, beam + 1] from ``topk_tokens``.  Afterwards
+    ``state.tokens`` (the other buffer) holds the next rows with ``state.len`` tokens each, ``state.sums`` their fp32 scores,
+    ``state.sources`` the row each continues (``kv_cache_reorder_native``) and ``state.last_token`` the appended tokens (``kv_cache_step``);
+    sequences that ended in ``eot`` went to the pool.  Wrong shapes / dtypes / devices raise ValueError before anything is launched."""
+    return _beam_update(state, top_lp, top_tok, eot, True)
+
+
+def beam_update_host(state, top_lp, top_tok, *, eot):
+    """``beam_update`` on a CPU state and CPU tensors through the library's host twin (oasr_beam_update_host: the same rule from the same
+    text, no GPU)."""
+    return _beam_update(state, top_lp, top_tok, eot, False)
+
+
+def kv_reorder_host(rows, pos, group, sources):
+    """``OLMoASR.kv_cache_reorder_native`` on a host copy of the self-attention cache rows (oasr_decode_reorder_host): ``rows`` CPU bf16 / fp32
+    [L, B, n_ctx, 3d], contiguous, in place -- row j of every layer continues row ``sources[j]`` over the k | v columns of positions
+    < ``pos``.  A source outside its destination's group of ``group`` rows raises ValueError before anything moves."""
+    if not (isinstance(rows, torch.Tensor) and not rows.is_cuda and rows.dim() == 4 and rows.is_contiguous() and rows.dtype in (BF, torch.float32)
+            and rows.shape[3] % 3 == 0):
+        raise ValueError("kv_reorder_host: rows must be a contiguous CPU bf16 / fp32 [L, B, n_ctx, 3d]")
+    L, B, n_ctx, d3 = rows.shape
+    src = torch.as_tensor(sources, dtype=torch.int32).reshape(-1).contiguous()
+    if not (1 <= group <= N.BeamArgs.MAX_BEAM and B % group == 0 and src.numel() == B and 0 <= pos <= n_ctx):
+        raise ValueError(f"kv_reorder_host: {B} sources, 1 <= group <= {N.BeamArgs.MAX_BEAM} dividing B, 0 <= pos <= n_ctx")
+    lo = torch.arange(B, dtype=torch.int32) // group * group
+    if bool(((src < lo) | (src >= lo + group)).any()):
+        raise ValueError(f"kv_reorder_host: a source lies outside its destination's group of {group} rows (beams never cross windows)")
+    N.call("oasr_decode_reorder_host", rows, rows.stride(0) * rows.element_size(), L, B, n_ctx, d3 // 3, rows.element_size(), int(pos), int(group), src)
+    return rows
+
+
 def check_loss_regularisers(label_smoothing, z_loss, who):
     """The refusals of the C side (``check_ce_reg``): label_smoothing in [0, 1), z_loss >= 0, both finite.  Returns them as floats."""
     eps, z = float(label_smoothing), float(z_loss)
