@@ -21,7 +21,7 @@ int oasr_profile_gemm(int enable);
  * nothing.  bits 4-5: 1 = plain launches, 2 = persistent launches (next tile's prologue ahead of the epilogue); bit 6 / 7: non-temporal epilogue
  * stores / side loads */
 int oasr_gemm_set_variant(int v);
-/* tests / A-B of the KV-cached step engine: -1 = default (ONE sequence on the bf16 engine: the chip-wide one-launch engine of
+/* tests / A-B: selects the ENGINE of the KV-cached step (the name is historical; csrc/decode_step_core.h: StepMode).  -1 = default (ONE sequence on the bf16 engine: the chip-wide one-launch engine of
  * csrc/decode_wide.hip; 2-4: LayerNorm folded into the projections; more: separate kernels), 0 = separate LayerNorm kernels, 1 = LayerNorm
  * folded into the projections' operand loads for every B <= 32, 2 = the one-launch TEAM engine of csrc/decode_xcd.hip on the 32 CUs of one
  * XCD (B <= 4), 3 / 4 = that team as 32 / 64 workgroups spread over the chip, 5 = the chip-wide engine (one sequence; more: as 2).
@@ -45,7 +45,7 @@ int oasr_xcd_plan_debug(int d, int H, int Te, int M, int L, int team, int wg, in
 int oasr_wide_supports_debug(int d, int H, int Te, int S_max, int L, int M, int nwg, int V);
 int oasr_wide_plan_debug(int d, int nwg, int N, int K, int wg, int wave, int* out, int max_units);
 /* tests (CPU): 1 when every 32-bit buffer offset of a one-launch step stays below 2 GiB (layer0 = the 18 element offsets of decoder layer 0
- * in csrc/decode_xcd.hip::XLayer order, strides in elements), 0 when the engine must take the multi-launch step instead. */
+ * in the field order of csrc/decode_step_core.h::DecLayerOffsets, strides in elements), 0 when the engine must take the multi-launch step instead. */
 int oasr_xcd_offsets_ok_debug(const int64_t* layer0, long long lstride, long long cache_lstride, int d, int Te, int L, int M);
 /* tests / A-B: 1 (default) = the unmasked attention cases (encoder self-, cross-attention) run the 8-wave ping-pong kernels,
  * 0 = the general (maskable) kernels run everything.  Same results up to accumulation order (tests/test_gpu_ops.py). */

@@ -106,6 +106,10 @@ STRUCT_SIZES = [
 ]
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
+# The tail's layout in 32-bit words (csrc/decode_step_core.h; tests/test_native_abi.py holds these mirrors to that header): the control words,
+KV_TEAM_COUNTER, KV_ERROR, KV_TEAM_EPOCH, KV_XCC_MASK, KV_WIDE_EPOCH, KV_CTRL_WORDS = 0, 1, 2, 3, 4, 5
+# ... and the chip-wide engine's per-workgroup phase flags: replica r (one per XCC) starts at word KV_FLAGS_WORD + r * KV_FLAG_STRIDE
+KV_REPLICAS, KV_FLAG_STRIDE, KV_FLAGS_WORD = 8, 1024, 1024
 MODE_INFER, MODE_TRAIN, MODE_TRAIN_ENC, MODE_TRAIN_DEC = 0, 1, 2, 3  # include/oasr.h: OASR_MODE_* (oasr_workspace_bytes)
 ROWTAB = 16        # include/oasr.h: OASR_ROWTAB (entries per sample of a chunk-row table)
 LORA_MAX_RANK = 64  # include/oasr.h: OASR_LORA_MAX_RANK

@@ -4,7 +4,7 @@
 // same contraction, same result.  Reference semantics: TextDecoder.forward for one new token with the kv_cache hooks,
 // olmoasr/model.py:786-817, 925-964; MultiHeadAttention.qkv_attention :347-442.
 #pragma once
-#include "kernels.h"
+#include "kernels.h"  // (decode_step_core.h comes with it)
 
 namespace dec {
 
@@ -100,9 +100,7 @@ __device__ __forceinline__ float epi_logit(float acc, float bias) { return bf_ro
 // Keys are processed in segments of <= SEG_KEYS (the scores of a segment live in LDS); a segment yields (m_s, l_s, o_s[64]) with
 // its own maximum, segments are merged in order (merge_segments).  One segment (self-attention: <= 448 keys) reduces to the plain
 // two-pass softmax.  Numerics as the tiled kernels: fp32 scores and normaliser, P rounded to bf16 before it multiplies V.
-constexpr int SEG_KEYS = 768;
-__host__ __device__ __forceinline__ int n_segments(int Tk) { return (Tk + SEG_KEYS - 1) / SEG_KEYS; }
-
+// (SEG_KEYS, MAX_SEG, n_segments: decode_step_core.h -- the host-side plan code needs them without HIP)
 __device__ __forceinline__ void load_q8(const u32x4_t& q4, float (&qv)[8]) { unpack8(q4, qv); }
 
 // value of lane (lane ^ X), X in {1, 2, 4}: __shfl_xor through the DPP cross-lane path (register to register) instead of the
@@ -153,7 +151,6 @@ __device__ __forceinline__ void reduce_groups(const float (*red)[64], const floa
   }
 }
 // merge of the segments' (m_s, l_s, o_s) in segment order; returns the attention output value of this thread's dimension
-constexpr int MAX_SEG = 2;  // Tk <= 1536
 __device__ __forceinline__ float merge_segments(const float (&m_s)[MAX_SEG], const float (&l_s)[MAX_SEG], const float (&o_s)[MAX_SEG], int ns,
                                                 float& m_out, float& l_out) {
   float m = m_s[0];
@@ -175,3 +172,19 @@ __device__ __forceinline__ float merge_segments(const float (&m_s)[MAX_SEG], con
 }
 
 }  // namespace dec
+
+// ---- agent-scope data accesses of the one-launch engines (coherent across workgroups wherever they run) -------------------------------------------
+__device__ __forceinline__ uint64_t ld8_agent(const void* p) {
+  return __hip_atomic_load((const uint64_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ u32x4_t ld16_agent(const void* p) {
+  const uint64_t a = ld8_agent(p), b = ld8_agent((const char*)p + 8);
+  u32x4_t r;
+  r[0] = (unsigned)a, r[1] = (unsigned)(a >> 32), r[2] = (unsigned)b, r[3] = (unsigned)(b >> 32);
+  return r;
+}
+__device__ __forceinline__ unsigned ld4_agent(const void* p) { return __hip_atomic_load((const unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float ldf_agent(const float* p) { return __uint_as_float(ld4_agent(p)); }
+__device__ __forceinline__ void st4_agent(void* p, unsigned v) { __hip_atomic_store((unsigned*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// lane l's value (l wave-uniform): v_readlane, a scalar broadcast, not a ds_bpermute round trip
+__device__ __forceinline__ float rdlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }

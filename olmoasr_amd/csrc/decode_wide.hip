@@ -26,54 +26,15 @@
 // GELU input, residual sum, P before it multiplies V); the K reduction order differs (512-element spans, summed in order), so results agree
 // with the other engines to fp32 rounding of the accumulation, not to the last bit (tests/test_gpu_decode_step.py states the tolerance).
 #include "decode_shared.h"
+#include "decode_wide_plan.h"
 
 namespace {
 
-#ifndef DW_WT
-#define DW_WT 576
-#endif
-constexpr int WT = DW_WT;  // threads per workgroup
-constexpr int WW = WT / 64;
-constexpr int WC = WW - 1;  // compute waves 1 .. WW-1; wave 0 is the helper: poll, operand row, epilogue, stores, flag -- it requests no weights, so nothing slow sits in front of its polls
-constexpr int WNG = WT / 8;  // 8-lane groups (attention: one key per group and step)
-constexpr int WMAXU = (64 + WC - 1) / WC;  // units per compute wave and phase (64 units per workgroup at most)
-#ifndef DW_NS_LOG
-#define DW_NS_LOG 3
-#endif
-constexpr int WNS_LOG = DW_NS_LOG;
-constexpr int WNS = 1 << WNS_LOG;  // cross-attention key segments per head (one workgroup each)
-constexpr int WSK = (448 + WNG - 1) / WNG;  // self-attention keys per 8-lane group: S_max <= 448
-constexpr int WCK = (1536 / WNS + WNG - 1) / WNG;  // cross-attention keys per group and segment: Te <= 1536
-constexpr int WMAXD = 1280;
-constexpr int WLNC = 3;    // 16-byte chunks per lane of a LayerNorm row: d <= 1536
-constexpr int WMAXL = 32;
-constexpr int WMAXWG = 256;
 constexpr unsigned WSPIN = 1u << 20;
-constexpr int WREP = 8;      // flag replicas: 256 workgroups polling the same eight cache lines serialise on one memory channel; a replica per XCC, 4 KB apart
-constexpr int WFS = 1024;    // dwords between replicas
-// Rows that every workgroup consumes in the very next phase travel as PACKETS: the producing workgroup's (<= 6) bf16 values and the phase's epoch
-// number in ONE 16-byte store per replica; a consumer polls the packets themselves.  No acknowledgement wait before a flag, no separate
-// flag-then-row round trip.  Vectors: the block output x (mlp.2 -> the next attn_ln, or the final LayerNorm), x2 (attention output projection ->
-// cross_attn_ln), x3 (cross output projection -> mlp_ln), q (cross query -> cross-attention).
-constexpr int WPKV = 5, WV_X = 0, WV_X2 = 1, WV_X3 = 2, WV_Q = 3, WV_O = 4;  // (O: the self-attention output, 11 packets per head, slot h 11 + j)
-constexpr int WQKS = 3 * 256;  // slots per replica of the q | k | v row of the new position: <= 3 packets per workgroup (R <= 18), slot wg 3 + j
-constexpr int WPKS = 256;    // packet slots per replica: one per workgroup
-constexpr int WPKR = 6;      // values per packet at most: R <= 6 for an N = d projection (the kernel is instantiated per R: 2, 4, 6)
 
 #define WWAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
-struct WLayer {  // element offsets of one decoder layer (the order of DecodeXcdArgs::layer_offsets)
-  long ln1g, ln1b, wqkv, bqkv_aux, wo, bo, lncg, lncb, wcq, bcq, wco, bco, ln2g, ln2b, w1, b1, w2, b2;
-};
-struct WArgs {
-  const bf16_t* wflat;
-  const float* params;
-  const float* aux;
-  bf16_t* cache;
-  long cache_lstride;
-  bf16_t *x, *x2, *x3, *q, *o, *hg;
-  float* part;      // [H * WNS][66]: m, l, o[64]
-  unsigned* ctrl;   // [1] error flag  [3] XCC ids seen  [4] epoch base of this engine
+struct WArgs : DecodeStepBufs {  // (part: [H * WNS][66])
   u32x4_t* pk;      // [WPKV][WREP][WPKS] packets: {bf16 x 6, epoch}
   u32x4_t* pkqkv;   // [WREP][WQKS] packets of the new position's q | k | v row
   unsigned* flagv;  // [WREP][WFS]: replica r (polled by the workgroups on XCC r) of the per-workgroup flags = last completed phase (epoch-based)
@@ -83,21 +44,9 @@ struct WArgs {
   const float *lnf_g, *lnf_b;
   float* logits_out;
   int V;
-  WLayer l0;
+  DecLayerOffsets l0;  // decoder layer 0; layer l = dec::layer_at(l0, l, lstride, astride)
   long lstride, astride;
 };
-// ---- agent-scope accesses --------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32x4_t ld16_agent(const void* p) {
-  const uint64_t a = __hip_atomic_load((const uint64_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint64_t b = __hip_atomic_load((const uint64_t*)((const char*)p + 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  u32x4_t r;
-  r[0] = (unsigned)a, r[1] = (unsigned)(a >> 32), r[2] = (unsigned)b, r[3] = (unsigned)(b >> 32);
-  return r;
-}
-__device__ __forceinline__ u32x4_t ld16_agent_off(const void* sbase, unsigned off) { return ld16_agent((const char*)sbase + (size_t)off); }
-__device__ __forceinline__ unsigned ld4_agent(const void* p) { return __hip_atomic_load((const unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ldf_agent(const float* p) { return __uint_as_float(ld4_agent(p)); }
-__device__ __forceinline__ void st4_agent(void* p, unsigned v) { __hip_atomic_store((unsigned*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // 16-byte agent-scope accesses as ONE instruction each (the HIP atomics stop at 8 bytes; a packet must not tear): issued from inline assembly, so the
 // compiler does not count them -- every reader below waits with an explicit s_waitcnt before it looks at the data
@@ -129,20 +78,29 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
-__device__ __forceinline__ float rdl(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 __device__ __forceinline__ float wsum(float v) {
   v += dpp_mov<0xB1>(v);   // quad_perm [1, 0, 3, 2]
   v += dpp_mov<0x4E>(v);   // quad_perm [2, 3, 0, 1]
   v += dpp_mov<0x141>(v);  // row_half_mirror
   v += dpp_mov<0x140>(v);  // row_mirror: every lane holds its 16-lane row's sum
-  return (rdl(v, 0) + rdl(v, 16)) + (rdl(v, 32) + rdl(v, 48));
+  return (rdlane(v, 0) + rdlane(v, 16)) + (rdlane(v, 32) + rdlane(v, 48));
 }
 __device__ __forceinline__ float wmaxf(float v) {
   v = fmaxf(v, dpp_mov<0xB1>(v));
   v = fmaxf(v, dpp_mov<0x4E>(v));
   v = fmaxf(v, dpp_mov<0x141>(v));
   v = fmaxf(v, dpp_mov<0x140>(v));
-  return fmaxf(fmaxf(rdl(v, 0), rdl(v, 16)), fmaxf(rdl(v, 32), rdl(v, 48)));
+  return fmaxf(fmaxf(rdlane(v, 0), rdlane(v, 16)), fmaxf(rdlane(v, 32), rdlane(v, 48)));
+}
+// one more round of a poll: sleep; false once it gives up -- past the spin limit, or when somebody else already has: somebody never arrived or a packet
+// never came, so the launch is poisoned instead of hanging
+__device__ __forceinline__ bool poll_again(const WArgs& a, unsigned& spins, int lane) {
+  if (!(a.flags & dec::XF_NO_SLEEP)) __builtin_amdgcn_s_sleep(1);
+  if (++spins > WSPIN || ((spins & 63) == 0 && ld4_agent(a.ctrl + dec::KV_ERROR) != 0)) {
+    if (lane == 0) __hip_atomic_fetch_or(a.ctrl + dec::KV_ERROR, dec::KV_ERR_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return false;
+  }
+  return true;
 }
 // wave 0: every workgroup has completed phase `target` (or the wait gave up and poisoned the launch)
 __device__ __forceinline__ void wide_wait(const WArgs& a, const unsigned* myflags, unsigned target, int lane) {
@@ -155,11 +113,7 @@ __device__ __forceinline__ void wide_wait(const WArgs& a, const unsigned* myflag
       for (int i = 0; i < 4; ++i) ok = ok && (int)(f[i] - target) >= 0;
     }
     if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-    if (!(a.flags & 4)) __builtin_amdgcn_s_sleep(1);
-    if (++spins > WSPIN || ((spins & 63) == 0 && ld4_agent(a.ctrl + 1) != 0)) {
-      if (lane == 0) __hip_atomic_fetch_or(a.ctrl + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // somebody never arrived: poison, do not hang
-      break;
-    }
+    if (!poll_again(a, spins, lane)) break;
   }
 }
 
@@ -188,11 +142,7 @@ __device__ __forceinline__ void pk_poll(const WArgs& a, int vec, int rep, unsign
         else missing = true;
       }
     if (__builtin_amdgcn_ballot_w64(missing) == 0) break;
-    if (!(a.flags & 4)) __builtin_amdgcn_s_sleep(1);
-    if (++spins > WSPIN || ((spins & 63) == 0 && ld4_agent(a.ctrl + 1) != 0)) {
-      if (lane == 0) __hip_atomic_fetch_or(a.ctrl + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // a packet never came: poison, do not hang
-      break;
-    }
+    if (!poll_again(a, spins, lane)) break;
   }
 }
 static_assert(WPKL == 4, "pk_poll pins four packets per lane");
@@ -267,60 +217,36 @@ struct WPh {  // what projection phase PH is, at compile time
   // reads the current one's in its epilogue)
   static constexpr int PAR = (PH == 2 || PH == 5 || PH == 7) ? 1 : 0;
 };
-// units per compute wave and phase at most, at 256 workgroups (decode_wide_supports checks the shape against it): keeps the unrolled unit loops -- and the
-// kernel under the 64 KB of instruction cache two CUs share -- as short as the instantiation allows
-template <int RD, int PH>
-constexpr int wmu() {  // ceil(units of the workgroup at most / compute waves); units: RD = 2: 6 / 2 / 8 / 8 (q|k|v, N = d, mlp.0, mlp.2), 4: 24 / 8 / 32 / 32, 6 (d <= 1280): 48 / 18 / 60 / 60
-  constexpr int u = RD == 2 ? (PH == 0 ? 6 : (PH == 6 || PH == 7) ? 8 : 2) : RD == 4 ? (PH == 0 ? 24 : (PH == 6 || PH == 7) ? 32 : 8) : (PH == 0 ? 48 : (PH == 6 || PH == 7) ? 60 : 18);
-  return (u + WC - 1) / WC;
-}
 template <int PH>
 __device__ __forceinline__ WGemv gemv_of(const WArgs& a, int layer) {
-  const long s = (long)layer * a.lstride;
+  const DecLayerOffsets ly = dec::layer_at(a.l0, layer, a.lstride, a.astride);
   WGemv p;
   p.merge = WPh<PH>::MERGE, p.gelu = WPh<PH>::GELU, p.ln_g = p.ln_b = nullptr, p.resid = nullptr, p.K = a.d, p.N = a.d, p.xin = nullptr;
   if constexpr (PH == 0) {  // attn_ln -> q | k | v of position pos, straight into the cache row
-    p.w = a.wflat + (a.l0.wqkv + s), p.xin = a.x, p.N = 3 * a.d, p.ln_g = a.params + (a.l0.ln1g + s), p.ln_b = a.params + (a.l0.ln1b + s);
-    p.bias = a.aux + (a.l0.bqkv_aux + (long)layer * a.astride);
+    p.w = a.wflat + ly.wqkv, p.xin = a.x, p.N = 3 * a.d, p.ln_g = a.params + ly.ln1g, p.ln_b = a.params + ly.ln1b;
+    p.bias = a.aux + ly.bqkv_aux;
     p.out = a.cache + (long)layer * a.cache_lstride + (long)a.pos * 3 * a.d;
   } else if constexpr (PH == 2) {  // self-attention output projection + residual
-    p.w = a.wflat + (a.l0.wo + s), p.xin = a.o, p.bias = a.params + (a.l0.bo + s), p.resid = a.x, p.out = a.x2;
+    p.w = a.wflat + ly.wo, p.xin = a.o, p.bias = a.params + ly.bo, p.resid = a.x, p.out = a.x2;
   } else if constexpr (PH == 3) {  // cross_attn_ln -> cross query
-    p.w = a.wflat + (a.l0.wcq + s), p.xin = a.x2, p.ln_g = a.params + (a.l0.lncg + s), p.ln_b = a.params + (a.l0.lncb + s), p.bias = a.params + (a.l0.bcq + s);
+    p.w = a.wflat + ly.wcq, p.xin = a.x2, p.ln_g = a.params + ly.lncg, p.ln_b = a.params + ly.lncb, p.bias = a.params + ly.bcq;
     p.out = a.q;
   } else if constexpr (PH == 5) {  // cross-attention output projection + residual (operand = merged segment partials)
-    p.w = a.wflat + (a.l0.wco + s), p.bias = a.params + (a.l0.bco + s), p.resid = a.x2, p.out = a.x3;
+    p.w = a.wflat + ly.wco, p.bias = a.params + ly.bco, p.resid = a.x2, p.out = a.x3;
   } else if constexpr (PH == 6) {  // mlp_ln -> mlp.0 + GELU
-    p.w = a.wflat + (a.l0.w1 + s), p.xin = a.x3, p.N = 4 * a.d, p.ln_g = a.params + (a.l0.ln2g + s), p.ln_b = a.params + (a.l0.ln2b + s), p.bias = a.params + (a.l0.b1 + s);
+    p.w = a.wflat + ly.w1, p.xin = a.x3, p.N = 4 * a.d, p.ln_g = a.params + ly.ln2g, p.ln_b = a.params + ly.ln2b, p.bias = a.params + ly.b1;
     p.out = a.hg;
   } else {  // 7: mlp.2 + residual
-    p.w = a.wflat + (a.l0.w2 + s), p.xin = a.hg, p.K = 4 * a.d, p.bias = a.params + (a.l0.b2 + s), p.resid = a.x3, p.out = a.x;
+    p.w = a.wflat + ly.w2, p.xin = a.hg, p.K = 4 * a.d, p.bias = a.params + ly.b2, p.resid = a.x3, p.out = a.x;
   }
-  p.R = 2 * ((p.N + 2 * a.nwg - 1) / (2 * a.nwg));
+  p.R = wide_rows(p.N, a.nwg);
   return p;
 }
 
-// this wave's weight chunks of a projection phase -> registers (unit u = wave + 8 i: row u / J of the workgroup's run, K span u % J)
-// Units (row r of the workgroup's run, 512-element K span j), numbered u = r J + j, are dealt to the compute waves in contiguous runs of
-// upw = ceil(U / WC): one division per wave and phase, then (r, j) by stepping.
-struct WUnits {
-  int U, upw, u0, r0, j0, J, KC;
-};
-__host__ __device__ __forceinline__ WUnits units_of(const WGemv& p, int wg, int wave) {
-  WUnits q;
-  q.KC = p.K >> 3, q.J = (q.KC + 63) >> 6;
-  int rows = p.N - wg * p.R;
-  rows = rows < 0 ? 0 : (rows > p.R ? p.R : rows);
-  q.U = rows * q.J;
-  q.upw = (q.U + WC - 1) / WC;  // (WC is a compile-time constant)
-  q.u0 = (wave - 1) * q.upw;
-  q.r0 = q.u0 / q.J, q.j0 = q.u0 - q.r0 * q.J;
-  return q;
-}
 template <int MU>
 __device__ __forceinline__ void request_units(const WGemv& p, int wg, int wave, int lane, u32x4_t (&wreg)[WMAXU]) {
   if (wave == 0) return;
-  const WUnits q = units_of(p, wg, wave);
+  const WUnits q = units_of(p.K, p.N, p.R, wg, wave);
   const bf16_t* row = p.w + (long)(wg * p.R + q.r0) * p.K;
   int j = q.j0;
   const int cnt = q.U - q.u0 < q.upw ? q.U - q.u0 : q.upw;  // this wave's units
@@ -364,7 +290,6 @@ __device__ __forceinline__ float dot8(const u32x4_t& w, const u32x4_t& x) {
   for (int i = 0; i < 4; ++i) s += bf_lo(w[i]) * bf_lo(x[i]) + bf_hi(w[i]) * bf_hi(x[i]);
   return s;
 }
-__device__ __forceinline__ float rdlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 __device__ __forceinline__ float merge_w(const float (&m_s)[WNS], const float (&l_s)[WNS], const float (&o_s)[WNS]) {
   float m = m_s[0];
 #pragma unroll
@@ -489,7 +414,7 @@ __device__ __forceinline__ void self_phase(const WArgs& a, int layer, unsigned g
     if (wave == 0) {
       // the new position's q | k | v values of this head arrive as packets (the projection a phase ago): lane (t, wi, j) polls packet j of the wi-th
       // workgroup that holds rows of range t (0 q, 1 k, 2 v: rows t d + h 64 .. + 63 of the 3 d), and spreads its six values out in LDS
-      const int R0 = 2 * ((3 * a.d + 2 * a.nwg - 1) / (2 * a.nwg)), NP0 = (R0 + 5) / 6;
+      const int R0 = wide_rows(3 * a.d, a.nwg), NP0 = (R0 + 5) / 6;
       const int t = lane >> 4, li = lane & 15;
       const int wi = li / NP0, j = li - wi * NP0;
       const int lo = t * a.d + h * 64;               // first row of the range
@@ -504,11 +429,7 @@ __device__ __forceinline__ void self_phase(const WArgs& a, int layer, unsigned g
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(pq)::"memory");
         if (need && pq[3] == target) need = false;
         if (__builtin_amdgcn_ballot_w64(need) == 0) break;
-        if (!(a.flags & 4)) __builtin_amdgcn_s_sleep(1);
-        if (++spins > WSPIN || ((spins & 63) == 0 && ld4_agent(a.ctrl + 1) != 0)) {
-          if (lane == 0) __hip_atomic_fetch_or(a.ctrl + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
+        if (!poll_again(a, spins, lane)) break;
       }
       if (mine) {
 #pragma unroll
@@ -588,11 +509,7 @@ __device__ __forceinline__ void cross_phase(const WArgs& a, int layer, unsigned 
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(pq)::"memory");
         if (need && pq[3] == target) need = false;
         if (__builtin_amdgcn_ballot_w64(need) == 0) break;
-        if (!(a.flags & 4)) __builtin_amdgcn_s_sleep(1);
-        if (++spins > WSPIN || ((spins & 63) == 0 && ld4_agent(a.ctrl + 1) != 0)) {
-          if (lane == 0) __hip_atomic_fetch_or(a.ctrl + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
+        if (!poll_again(a, spins, lane)) break;
       }
       if (s0 + lane <= s1) {
 #pragma unroll
@@ -633,12 +550,13 @@ __device__ __forceinline__ void gemv_phase(const WArgs& a, int layer, unsigned g
   const WGemv p = gemv_of<PH>(a, layer);
   const int row0 = wg * p.R;
   if (row0 < p.N) {
-    const int KC = p.K >> 3, J = (KC + 63) >> 6;
+    const int KC = p.K >> 3;
     int rows = p.N - row0;
     rows = rows > p.R ? p.R : rows;
-    const int U = rows * J;
-    WUnits q = {};  // (before the poll: off the path from the flags to the stores; the helper wave has no units)
-  if (wave > 0) q = units_of(p, wg, wave);
+    // (never read, the unit loop below takes its own; but without it the register allocation of the 2-row instantiation differs: kept, see
+    // profiles/decode_split_isa.txt)
+    WUnits q = {};
+    if (wave > 0) q = units_of(p.K, p.N, p.R, wg, wave);
     // the compute waves hand over what they fetched for the helper wave (request_phase)
     float* biasv = lds.biasv[WPh<PH>::PAR];
     if (tid >= 64) {
@@ -723,7 +641,7 @@ __device__ __forceinline__ void gemv_phase(const WArgs& a, int layer, unsigned g
         WWAIT_VM0();
         if (wg == a.swg && layer == 1 && tid == 64) a.stamps[ph * 8 + 5] = __builtin_amdgcn_s_memtime();
       }
-      const WUnits q = units_of(p, wg, wave);
+      const WUnits q = units_of(p.K, p.N, p.R, wg, wave);
       // lane-wise partial products of consecutive spans of the SAME row are added up before the wave reduction: one reduction per (wave, row),
       // its result in rowsum[row][wave] (zeroed at the top of the phase); the epilogue adds a row's WC slots in wave order
       const int cnt = q.U - q.u0 < q.upw ? q.U - q.u0 : q.upw;
@@ -765,7 +683,7 @@ __device__ __forceinline__ void gemv_phase(const WArgs& a, int layer, unsigned g
         if constexpr (PH == 7) res.x = yb;
         u32x4_t w;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) w[i] = i < RD / 2 ? pack_bf2(rdl(yb, 2 * i), rdl(yb, 2 * i + 1)) : 0u;  // (lanes >= rows hold 0)
+        for (int i = 0; i < 3; ++i) w[i] = i < RD / 2 ? pack_bf2(rdlane(yb, 2 * i), rdlane(yb, 2 * i + 1)) : 0u;  // (lanes >= rows hold 0)
         w[3] = base + gp + 1;
         if (lane < WREP) st16_agent(a.pk + (size_t)(PKOUT * WREP + lane) * WPKS + wg, w);
       } else if constexpr (PH == 0) {
@@ -882,12 +800,12 @@ __device__ __forceinline__ void request_phase(const WArgs& a, int layer, u32x4_t
 template <bool STAMPS, int RD>
 __global__ __launch_bounds__(WT) void decode_wide_kernel(WArgs a) {
   __shared__ WLds lds;
-  const unsigned base = a.ctrl[4];
+  const unsigned base = a.ctrl[dec::KV_WIDE_EPOCH];
   unsigned xcc;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
   const int rep = (int)(xcc & (WREP - 1));
   const unsigned* myflags = a.flagv + (size_t)rep * WFS;
-  if (threadIdx.x == 0) __hip_atomic_fetch_or(a.ctrl + 3, 1u << (xcc & 15), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) __hip_atomic_fetch_or(a.ctrl + dec::KV_XCC_MASK, 1u << (xcc & 15), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   u32x4_t wreg[WMAXU];
   WStage st;
   WRes res = {0.f, 0.f, 0.f};
@@ -915,62 +833,28 @@ __global__ __launch_bounds__(WT) void decode_wide_kernel(WArgs a) {
   if (a.logits_out) logits_phase<STAMPS, RD>(a, gp, base, myflags, rep, lds);
   if (blockIdx.x == 0 && threadIdx.x < 64) {  // everybody has read the epoch base long ago; publish the next launch's once every workgroup is through
     wide_wait(a, myflags, base + gp, threadIdx.x);
-    if (threadIdx.x == 0) a.ctrl[4] = base + gp;
+    if (threadIdx.x == 0) a.ctrl[dec::KV_WIDE_EPOCH] = base + gp;
   }
 }
 
 }  // namespace
 
-// ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t decode_wide_part_floats(int H) { return (size_t)H * WNS * 66; }
-
-// V: the rows of the tied logits projection as the last phase deals them out (the token embedding's rows, unpadded: logits_phase's RW)
-bool decode_wide_supports(int d, int H, int Te, int S_max, int L, int M, int nwg, int V) {
-  if (!(M == 1 && L >= 1 && L <= WMAXL && d % 64 == 0 && d == H * 64 && d <= WMAXD && H <= 32 && S_max >= 1 && S_max <= WNG * WSK && Te >= 1 &&
-        (Te + WNS - 1) / WNS <= WNG * WCK && nwg >= 64 && nwg <= WMAXWG && nwg % 4 == 0 && H * WNS <= nwg))
-    return false;
-  if (2 * ((d + 2 * nwg - 1) / (2 * nwg)) > WPKR) return false;  // an N = d projection's rows per workgroup fill one packet
-  if (V < 1 || (V + nwg - 1) / nwg > 64 * WC) return false;       // the logits phase parks a wave's rows of the workgroup's run in its 64 lanes
-  {
-    const int R0 = 2 * ((3 * d + 2 * nwg - 1) / (2 * nwg)), NP0 = (R0 + 5) / 6;  // the q | k | v row: <= 3 packets per workgroup, <= 16 packets per head and range
-    if (NP0 > 3 || ((63 + R0 - 1) / R0 + 1) * NP0 > 16 || H * 11 > WPKS) return false;
-  }
-  // units per wave: rows R x spans J dealt to 8 waves, within what the instantiation for this R_d unrolls (wmu)
-  {
-    const int rd = 2 * ((d + 2 * nwg - 1) / (2 * nwg));
-    const int mu0 = rd == 2 ? wmu<2, 0>() : rd == 4 ? wmu<4, 0>() : wmu<6, 0>(), mu2 = rd == 2 ? wmu<2, 2>() : rd == 4 ? wmu<4, 2>() : wmu<6, 2>();
-    const int mu6 = rd == 2 ? wmu<2, 6>() : rd == 4 ? wmu<4, 6>() : wmu<6, 6>();
-    auto upw = [&](int N, int K) { return (2 * ((N + 2 * nwg - 1) / (2 * nwg)) * ((K / 8 + 63) / 64) + WC - 1) / WC; };
-    if (upw(3 * d, d) > mu0 || upw(d, d) > mu2 || upw(4 * d, d) > mu6 || upw(d, 4 * d) > mu6) return false;
-  }
-  const int Ns[3] = {3 * d, d, 4 * d}, Ks[3] = {d, 4 * d, d};
-  for (int i = 0; i < 3; ++i) {
-    const int R = 2 * ((Ns[i] + 2 * nwg - 1) / (2 * nwg)), J = (Ks[i] / 8 + 63) / 64;
-    if (R * J > 64 || R > 64) return false;
-  }
-  return true;
-}
-
-int launch_decode_wide(const DecodeXcdArgs& h, hipStream_t s) {
+// (which shapes the engine takes: decode_plan_host.cpp)
+int launch_decode_wide(const DecodeStepArgs& h, hipStream_t s) {
   OASR_REQUIRE(decode_wide_supports(h.d, h.H, h.Te, h.S_max, h.L, h.M, h.team, h.logits_out ? h.V : 1), "decode_wide: unsupported shape");
-  OASR_REQUIRE(h.pos >= 0 && h.pos < h.S_max && h.layer_offsets, "decode_wide: bad launch shape");
+  OASR_REQUIRE(h.pos >= 0 && h.pos < h.S_max, "decode_wide: bad launch shape");
   WArgs a;
-  a.wflat = h.wflat, a.params = h.params, a.aux = h.aux, a.cache = h.cache, a.cache_lstride = h.cache_lstride;
-  a.x = h.x, a.x2 = h.x2, a.x3 = h.x3, a.q = h.q, a.o = h.o, a.hg = h.hg, a.part = h.part;
-  a.ctrl = h.ctrl, a.flagv = h.ctrl + 1024;  // the flag replicas start 4 KB into the cache's control tail
-  a.pk = (u32x4_t*)(h.ctrl + 16384);         // ... the packets 64 KB in (5 vectors x 8 replicas x 256 x 16 bytes = 160 KB)
-  a.pkqkv = a.pk + (size_t)WPKV * WREP * WPKS;  // ... and the q | k | v row's behind them (8 replicas x 768 x 16 bytes = 96 KB)
+  static_cast<DecodeStepBufs&>(a) = h;
+  a.flagv = h.ctrl + dec::KV_FLAGS_WORD;  // the exchange areas of the cache's control tail (decode_step_core.h)
+  a.pk = (u32x4_t*)(h.ctrl + dec::KV_PACKETS_WORD);
+  a.pkqkv = (u32x4_t*)(h.ctrl + dec::KV_QKV_PACKETS_WORD);
   a.d = h.d, a.H = h.H, a.Te = h.Te, a.S_max = h.S_max, a.L = h.L, a.pos = h.pos, a.nwg = h.team, a.flags = h.flags;
   a.stamps = (unsigned long long*)h.stamps;
   a.w_logits = h.w_logits, a.lnf_g = h.lnf_g, a.lnf_b = h.lnf_b, a.logits_out = h.logits_out, a.V = h.V;
   OASR_REQUIRE(!h.logits_out || (h.w_logits && h.lnf_g && h.lnf_b && h.V > 0 && (h.V + h.team - 1) / h.team <= 64 * WC), "decode_wide: bad logits phase");
   a.swg = (h.flags >> 8) & 0xff;  // (the engine passes OASR_XCD_FLAGS bits 9-16 here: the workgroup whose stamps are taken)
-  {
-    long* dst = &a.l0.ln1g;
-    for (int i = 0; i < 18; ++i) dst[i] = (long)h.layer_offsets[i];
-    a.lstride = h.lstride, a.astride = h.astride;
-  }
-  const int rd = 2 * ((h.d + 2 * h.team - 1) / (2 * h.team));
+  a.l0 = h.l0, a.lstride = h.lstride, a.astride = h.astride;
+  const int rd = wide_rows(h.d, h.team);
 #define DW_LAUNCH(ST, R) hipLaunchKernelGGL((decode_wide_kernel<ST, R>), dim3(h.team), dim3(WT), 0, s, a)
   if (a.stamps) {  // (measurement: medium / small only)
     OASR_REQUIRE(rd == 4, "decode_wide: the stamped instantiation is built for 4 rows per workgroup");
@@ -983,27 +867,3 @@ int launch_decode_wide(const DecodeXcdArgs& h, hipStream_t s) {
   return OASR_OK;
 }
 
-// Test hooks (include/oasr_testing.h): the host-side view of the work split -- whether a shape runs on this engine, and which (row, K span) units compute
-// wave `wave` (1 .. 8) of workgroup `wg` is dealt for an [N x K] projection: out[2 i] = row (absolute), out[2 i + 1] = span; returns the count, or -1
-// past the instantiation's unrolled bound (wmu).  tests/test_native_abi.py checks that the units of all waves tile the matrix exactly once.
-extern "C" int oasr_wide_supports_debug(int d, int H, int Te, int S_max, int L, int M, int nwg, int V) {
-  return decode_wide_supports(d, H, Te, S_max, L, M, nwg, V) ? 1 : 0;
-}
-extern "C" int oasr_wide_plan_debug(int d, int nwg, int N, int K, int wg, int wave, int* out, int max_units) {
-  WGemv p{};
-  p.N = N, p.K = K, p.R = 2 * ((N + 2 * nwg - 1) / (2 * nwg));
-  if (wave < 1 || wave > WC || wg < 0 || wg >= nwg) return -1;
-  const WUnits q = units_of(p, wg, wave);
-  const int cnt = q.U - q.u0 < q.upw ? q.U - q.u0 : q.upw;
-  const int rd = 2 * ((d + 2 * nwg - 1) / (2 * nwg));
-  const int ph = N == 3 * d ? 0 : (N == 4 * d ? 6 : (K == 4 * d ? 7 : 2));
-  const int mu = rd == 2 ? (ph == 0 ? wmu<2, 0>() : ph == 2 ? wmu<2, 2>() : wmu<2, 6>()) : rd == 4 ? (ph == 0 ? wmu<4, 0>() : ph == 2 ? wmu<4, 2>() : wmu<4, 6>())
-                                                                                                   : (ph == 0 ? wmu<6, 0>() : ph == 2 ? wmu<6, 2>() : wmu<6, 6>());
-  if (cnt > mu) return -1;
-  int n = 0, j = q.j0, r = q.r0;
-  for (int i = 0; i < cnt && n < max_units; ++i, ++n) {
-    out[2 * n] = wg * p.R + r, out[2 * n + 1] = j;
-    if (++j == q.J) j = 0, ++r;
-  }
-  return n;
-}

@@ -17,350 +17,14 @@
 //     operand exactly like decode_proj.hip), the K-split reduction + epilogue and the stores -- the four streaming waves issue no other
 //     vector-memory instruction, so their vmcnt counts ring blocks only.
 // Data crosses workgroups ONLY through agent-scope (sc1) atomic loads / stores, so results do not depend on where the team's workgroups
-// land; the XCD placement is a speed matter (recorded in ctrl[3]).  Arithmetic is decode_shared.h's: bit-identical to the multi-launch step.
-#include "decode_shared.h"
+// land; the XCD placement is a speed matter (recorded in the control word KV_XCC_MASK).  Arithmetic is decode_shared.h's: bit-identical to the multi-launch step.
+#include "decode_xcd_ring.h"
 
 namespace {
 
-constexpr int XR = 6;        // ring slots per streaming wave
-constexpr int SLOT = 4096;   // bytes per slot: 4 DMA instructions of 64 lanes x 16 B
-constexpr int XMAXM = 4;     // sequences this engine takes
-constexpr int XMAXL = 32;    // decoder layers
-constexpr int NSEG = 7;      // streamed segments per layer (the self-attention phase streams nothing)
-constexpr unsigned SPIN_LIMIT = 1u << 21;
-constexpr int XMAXPAIR = 40;  // (head, key segment) pairs of one sequence: H * ns <= 40 (d <= 1280)
 constexpr int XHG = 8;        // heads merged per batch of partial loads
 
-struct XLayer {  // element offsets of one decoder layer: w* into the bf16 shadow, the rest into the fp32 parameter arena / aux region
-  long ln1g, ln1b, wqkv, bqkv_aux, wo, bo, lncg, lncb, wcq, bcq, wco, bco, ln2g, ln2b, w1, b1, w2, b2;
-};
-struct XArgs {
-  const bf16_t* wflat;
-  const float* params;
-  const float* aux;
-  bf16_t* cache;       // per layer: self q|k|v [M, S_max, 3d] then cross k|v [M, Te, 2d]
-  long cache_lstride;  // elements
-  bf16_t *x, *x2, *x3, *q, *o, *hg;  // activation rows [M][d] ([M][4d] for hg), exchanged through agent-scope accesses
-  float* part;         // cross-attention partials [M * H * ns][66]: m, l, o[64]
-  unsigned* ctrl;      // [0] team barrier counter  [1] error flag  [2] epoch base  [3] XCC ids seen (bit mask)
-  int d, H, Te, S_max, L, M, pos, team, stride;
-  int flags;             // experiments: bit 0 = plain (not agent-scope) activation stores, bit 2 = no sleep in the barrier poll, bit 3 = checked
-                         // instantiation, bit 4 = consume ring blocks without waiting for them, bit 5 = issue no DMA (4, 5: timing only, garbage results)
-  unsigned long long* stamps;  // optional [8 phases][8] s_memtime stamps of workgroup 0 in layer 1 (null: off)
-  XLayer l0;             // decoder layer 0; layer l = l0 + l * (lstride | astride): the blocks are laid out back to back (host-checked)
-  long lstride, astride;
-};
-__host__ __device__ __forceinline__ XLayer layer_of(const XArgs& a, int l) {
-  XLayer y = a.l0;
-  const long s = (long)l * a.lstride;
-  y.ln1g += s, y.ln1b += s, y.wqkv += s, y.wo += s, y.bo += s, y.lncg += s, y.lncb += s, y.wcq += s, y.bcq += s, y.wco += s, y.bco += s;
-  y.ln2g += s, y.ln2b += s, y.w1 += s, y.b1 += s, y.w2 += s, y.b2 += s;
-  y.bqkv_aux += (long)l * a.astride;
-  return y;
-}
-
-// ---- the static block sequence of one workgroup (identical for its four streaming waves) ---------------------------------------------
-struct XGeom {
-  int d, H, Te, M, team, wg, L, ns;
-  int nst_d, nst_4d;  // k16 steps per wave and tile for K = d / 4d
-  int nkb_d, nkb_4d;  // ring blocks per wave and tile
-  int cnt_qkv, cnt_d, cnt_4d, cnt_it;  // tiles of this workgroup in a phase of 3d/32, d/32, 4d/32 tiles; cross-attention items
-};
-__host__ __device__ __forceinline__ int cnt_of(int n, int wg, int team) {  // tiles t = wg, wg + team, ... < n (a short loop instead of a division)
-  int c = 0;
-  for (int t = wg; t < n; t += team) ++c;
-  return c;
-}
-__host__ __device__ __forceinline__ XGeom make_geom(int d, int H, int Te, int M, int L, int team, int wg) {
-  XGeom g;
-  g.d = d, g.H = H, g.Te = Te, g.M = M, g.team = team, g.wg = wg, g.L = L;
-  g.ns = Te > dec::SEG_KEYS ? 2 : 1;
-  g.nst_d = d >> 6, g.nst_4d = d >> 4;
-  g.nkb_d = (g.nst_d + 3) >> 2, g.nkb_4d = (g.nst_4d + 3) >> 2;
-  g.cnt_qkv = cnt_of((3 * d) >> 5, wg, team);
-  g.cnt_d = cnt_of(d >> 5, wg, team);
-  g.cnt_it = cnt_of(M * H * g.ns, wg, team);
-  g.cnt_4d = cnt_of((4 * d) >> 5, wg, team);
-  return g;
-}
-// tiles (items for segment 3) of this workgroup in streamed segment `seg` (selects, not a table: the cursors live in SGPRs)
-__host__ __device__ __forceinline__ int seg_cnt(const XGeom& g, int seg) { return seg == 0 ? g.cnt_qkv : seg == 3 ? g.cnt_it : seg == 5 ? g.cnt_4d : g.cnt_d; }
-struct XItem {
-  int b, h, sg, n, kvb;  // sequence, head, key segment, keys in it, ring blocks per K (or V) stream
-};
-// (no integer division anywhere near the cursors: hipcc expands a 32-bit division through VALU float reciprocals, whose result -- and
-// everything computed from it, i.e. the whole block bookkeeping -- then lives in VGPRs under exec-mask branches instead of SGPRs)
-__host__ __device__ __forceinline__ XItem item_of(const XGeom& g, int idx) {
-  const int id = g.wg + g.team * idx;
-  const int hn = g.H * g.ns;
-  XItem it;
-  it.b = (id >= hn ? 1 : 0) + (id >= 2 * hn ? 1 : 0) + (id >= 3 * hn ? 1 : 0);  // M <= 4 sequences
-  const int rem = id - it.b * hn;
-  it.h = g.ns == 2 ? rem >> 1 : rem;  // ns <= MAX_SEG = 2
-  it.sg = g.ns == 2 ? rem & 1 : 0;
-  int n = g.Te - it.sg * dec::SEG_KEYS;
-  it.n = n > dec::SEG_KEYS ? dec::SEG_KEYS : n;
-  it.kvb = (((it.n + 31) >> 5) + 3) >> 2;
-  return it;
-}
-struct XCur {
-  int layer, seg, idx, sub;
-};
-#if defined(__HIP_DEVICE_COMPILE__)
-#define XU(x) __builtin_amdgcn_readfirstlane(x)  // pin a wave-uniform value to an SGPR (hipcc's uniformity analysis gives up on the cursors)
-#else
-#define XU(x) (x)
-#endif
-__host__ __device__ __forceinline__ int nsub_of(const XGeom& g, int seg, int idx) {
-  if (seg == 3) return 2 * item_of(g, idx).kvb;
-  return seg == 6 ? g.nkb_4d : g.nkb_d;
-}
-// the cursor's sub already points one past the unit's last full block: roll over into the next tile / item / segment if the unit ends there
-__host__ __device__ __forceinline__ bool cur_normalise(const XGeom& g, XCur& c);
-__host__ __device__ __forceinline__ int nsub_of(const XGeom& g, int seg, int idx);
-__host__ __device__ __forceinline__ bool cur_advance_from(const XGeom& g, XCur& c) {
-  if (c.sub >= nsub_of(g, c.seg, c.idx)) c.sub = 0, ++c.idx;
-  const bool more = cur_normalise(g, c);
-  c.layer = XU(c.layer), c.seg = XU(c.seg), c.idx = XU(c.idx), c.sub = XU(c.sub);
-  return more;
-}
-// skip empty segments; returns false past the last layer
-__host__ __device__ __forceinline__ bool cur_normalise(const XGeom& g, XCur& c) {
-  while (c.layer < g.L && c.idx >= seg_cnt(g, c.seg)) {
-    c.idx = 0;
-    if (++c.seg == NSEG) c.seg = 0, ++c.layer;
-  }
-  return c.layer < g.L;
-}
-__host__ __device__ __forceinline__ bool cur_advance(const XGeom& g, XCur& c) {
-  if (++c.sub >= nsub_of(g, c.seg, c.idx)) c.sub = 0, ++c.idx;
-  const bool more = cur_normalise(g, c);
-  c.layer = XU(c.layer), c.seg = XU(c.seg), c.idx = XU(c.idx), c.sub = XU(c.sub);
-  return more;
-}
-
-// ---- agent-scope data accesses (coherent across workgroups wherever they run) ---------------------------------------------------------
-__device__ __forceinline__ uint64_t ld8_agent(const void* p) {
-  return __hip_atomic_load((const uint64_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u32x4_t ld16_agent(const void* p) {
-  const uint64_t a = ld8_agent(p), b = ld8_agent((const char*)p + 8);
-  u32x4_t r;
-  r[0] = (unsigned)a, r[1] = (unsigned)(a >> 32), r[2] = (unsigned)b, r[3] = (unsigned)(b >> 32);
-  return r;
-}
-__device__ __forceinline__ float ldf_agent(const float* p) {
-  return __uint_as_float(__hip_atomic_load((const unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ void st4_agent(void* p, unsigned v) { __hip_atomic_store((unsigned*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// (experiment switch: plain stores -- they stay in this XCD's L2, which is all a team on ONE XCD needs; not valid for a spread team)
-__device__ __forceinline__ void st4_x(void* p, unsigned v, int flags) {
-  if (flags & 1) *(volatile unsigned*)p = v;
-  else st4_agent(p, v);
-}
-
-// ---- LDS-DMA of one ring block (4 x 1 KiB), issued from inline assembly (hipcc would otherwise order every later ds_read behind it with
-// s_waitcnt vmcnt(0) and drain the ring) ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dma16(const u32x4_t rs_in, unsigned lds_addr, unsigned voff, unsigned soff) {
-  u32x4_t rs;  // (re-pinned: a descriptor that travelled through a loop-carried struct comes back as VGPRs)
-  rs[0] = __builtin_amdgcn_readfirstlane(rs_in[0]), rs[1] = __builtin_amdgcn_readfirstlane(rs_in[1]);
-  rs[2] = 0x7fffffffu, rs[3] = 0x00020000u;
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rs),
-               "s"(__builtin_amdgcn_readfirstlane(soff))
-               : "memory");
-}
-// (descriptor already in SGPRs)
-__device__ __forceinline__ void dma16_s(const u32x4_t rs_in, unsigned lds_addr, unsigned voff, unsigned soff) {
-  u32x4_t rs;
-  rs[0] = __builtin_amdgcn_readfirstlane(rs_in[0]), rs[1] = __builtin_amdgcn_readfirstlane(rs_in[1]);
-  rs[2] = 0x7fffffffu, rs[3] = 0x00020000u;
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rs),
-               "s"(__builtin_amdgcn_readfirstlane(soff))
-               : "memory");
-}
-__device__ __forceinline__ u32x4_t rsrc_of(const void* base) {
-  const unsigned long addr = (unsigned long)base;
-  u32x4_t rs;  // (readfirstlane: the descriptor must sit in SGPRs; the inline-asm "s" constraint does not move it there by itself)
-  rs[0] = __builtin_amdgcn_readfirstlane((unsigned)addr);
-  rs[1] = __builtin_amdgcn_readfirstlane((unsigned)(addr >> 32) & 0xffffu);  // stride 0: raw buffer
-  rs[2] = 0x7fffffffu;
-  rs[3] = 0x00020000u;
-  return rs;
-}
-#define XWAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define XBAR() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-// ---- the producer: a table of UNITS per wave ------------------------------------------------------------------------------------------
-// A unit = a run of ring blocks that share one descriptor and one set of per-lane offsets: all tiles of one projection segment that belong
-// to this workgroup (consecutive tiles lie a constant distance apart), the full blocks of one item's K (or V) stream, or the one clamped
-// block that ends a stream.  The units of decoder layer 0 are listed ONCE per launch by walking the cursor (the CPU-tested sequence) and
-// kept in a wave-private LDS table; layer l adds l x (layer stride) to the soffset.  Issuing a block is then: 4 DMA instructions, three
-// scalar updates, and -- at a unit's end -- one 16-byte LDS read.  (Versions 1-5 advanced the cursor per block: ~2 k cycles of single-wave
-// instruction issue at every unit boundary, profiles/r05_decode_xcd_stamps_v5.txt.)
-constexpr int XTABN = 32;  // units per layer and wave (6 projection segments + 4 per cross-attention item, <= 5 items)
-struct XStream {  // per streaming wave (all fields wave-uniform, SGPR-resident)
-  bool more;      // the producer has blocks left
-  int issued, consumed;
-  int islot, cslot;  // issued % XR, consumed % XR, kept incrementally
-  int u, nunits, layer;  // current unit, units per layer, layer of the block to issue next
-  unsigned soff, jump;   // soffset of the next block; step from a tile's last block to this workgroup's next tile (weights)
-  int left, kind;        // blocks left in the unit; lane-offset set: 0 weights K = d, 1 weights K = 4d, 2 cross K/V, 3 cross K/V last (clamped) block
-  int tleft, tnkb;       // blocks left in the tile being issued (incl. the next one), blocks per tile
-};
-// per-lane byte offsets that do not depend on the block (computed once per wave): the DMA source offsets of a weight block for K = d / K = 4d,
-// of a K/V block, of the clamped last K/V block of the partial key segment, and the LDS fragment offsets of the 4 k16 steps of a weight block
-struct XLane {
-  unsigned w_d[4], w_4d[4], kv[4], kvc[4], frag[4];
-};
-__device__ __forceinline__ XLane make_lane(int d, int Te, int wave, int lane) {
-  XLane v;
-  const int r8 = lane >> 3, l8 = lane & 7, row = lane & 31, kc = lane >> 5;
-  const int n_p = Te - (Te > dec::SEG_KEYS ? dec::SEG_KEYS : 0);  // keys of the last (possibly partial) segment
-  const int last = n_p - 1 - 128 * ((n_p - 1) >> 7);              // last valid key of its last block, relative to that block
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int c16 = l8 ^ ((q * 4 + (r8 >> 1)) & 7);
-    v.w_d[q] = (unsigned)(((q * 8 + r8) * d + c16 * 8) * 2);
-    v.w_4d[q] = (unsigned)(((q * 8 + r8) * 4 * d + c16 * 8) * 2);
-    const int t = 32 * q + 8 * wave + r8;
-    v.kv[q] = (unsigned)((t * 2 * d + l8 * 8) * 2);
-    v.kvc[q] = (unsigned)(((t < last ? t : last) * 2 * d + l8 * 8) * 2);  // keys past the segment's end re-read its last key (never used)
-    v.frag[q] = (unsigned)(row * 128 + (((2 * q + kc) ^ ((row >> 1) & 7)) << 4));
-  }
-  return v;
-}
-
-// List the units of decoder layer 0 for this wave into its LDS table (4 words each: soffset, blocks, kind | blocks per tile << 8, tile jump);
-// returns their number.  Runs once per launch; walks the same cursor functions the CPU test pins.
-struct XBuild {  // what the unit walk needs, BY VALUE (a reference to the kernel arguments would pull them out of SGPRs into scratch memory)
-  int d, H, Te, M, L, team, wg;
-  long w[6];  // layer 0 weight offsets by streamed segment: qkv, attn.out, cross q, (3 unused), cross out, mlp.0, mlp.2 -> indices 0,1,2,3,4,5
-};
-__device__ __attribute__((noinline)) int build_units(XBuild p, int wave, int lane, unsigned* tab) {
-  const XGeom g = make_geom(p.d, p.H, p.Te, p.M, p.L, p.team, p.wg);
-  XCur c{0, 0, 0, 0};
-  bool more = cur_normalise(g, c);
-  int n = 0;
-  while (more && c.layer == 0 && n < XTABN) {
-    unsigned soff, jump = 0;
-    int nblk, kind, tnkb = 0x400000;
-    if (c.seg == 3) {
-      const XItem it = item_of(g, c.idx);
-      const bool is_v = c.sub >= it.kvb;
-      const int j = is_v ? c.sub - it.kvb : c.sub;
-      soff = (unsigned)((((long)it.b * p.Te + (long)it.sg * dec::SEG_KEYS + 128 * j) * 2 * p.d + it.h * 64 + (is_v ? p.d : 0)) * 2);
-      const int nfull = it.n >> 7;
-      if (nfull > j) nblk = nfull - j, kind = 2;
-      else nblk = 1, kind = 3;
-      c.sub += nblk;
-      more = cur_advance_from(g, c);
-    } else {
-      const long woff = p.w[c.seg < 3 ? c.seg : c.seg - 1];
-      const int K = c.seg == 6 ? 4 * p.d : p.d, nkb = c.seg == 6 ? g.nkb_4d : g.nkb_d;
-      const int tile = g.wg + g.team * c.idx;
-      soff = (unsigned)((unsigned long)((woff + ((long)tile * 32) * K + (long)wave * (K >> 2)) * 2));  // relative to the arena's bf16 shadow
-      nblk = (seg_cnt(g, c.seg) - c.idx) * nkb, kind = c.seg == 6 ? 1 : 0, tnkb = nkb;
-      jump = (unsigned)((long)g.team * 32 * K * 2 - (long)(nkb - 1) * 128);
-      c.idx = seg_cnt(g, c.seg), c.sub = 0;
-      more = cur_normalise(g, c);
-    }
-    if (lane == 0) {
-      tab[4 * n] = soff, tab[4 * n + 1] = (unsigned)nblk, tab[4 * n + 2] = (unsigned)kind | ((unsigned)tnkb << 8), tab[4 * n + 3] = jump;
-    }
-    ++n;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (read back by this wave only)
-  return n;
-}
-// load unit st.u of layer st.layer into the producer state
-__device__ __forceinline__ void unit_load(const XArgs& a, XStream& st, const unsigned* tab) {
-  const u32x4_t e = *(const u32x4_t*)(tab + 4 * st.u);
-  const int kind = XU(e[2] & 0xffu);
-  const long stride = kind >= 2 ? a.cache_lstride : a.lstride;
-  st.soff = XU(e[0] + (unsigned)((long)st.layer * stride * 2));
-  st.left = XU(e[1]);
-  st.kind = kind;
-  st.tnkb = XU(e[2] >> 8);
-  st.tleft = st.tnkb;
-  st.jump = XU(e[3]);
-}
-// after a block has been issued: next block of the unit, next tile, or next unit / layer
-__device__ __forceinline__ void unit_advance(const XArgs& a, XStream& st, const unsigned* tab) {
-  st.left = XU(st.left - 1);
-  if (st.left == 0) {
-    st.u = XU(st.u + 1);
-    if (st.u == st.nunits) st.u = 0, st.layer = XU(st.layer + 1);
-    if (st.layer == a.L) st.more = false;
-    else unit_load(a, st, tab);
-  } else if (st.tleft == 1) {
-    st.soff = XU(st.soff + st.jump), st.tleft = st.tnkb;  // the tile's last block: on to this workgroup's next tile of the segment
-  } else {
-    st.soff = XU(st.soff + (st.kind >= 2 ? (unsigned)(128 * 2 * a.d * 2) : 128u)), st.tleft = XU(st.tleft - 1);
-  }
-}
-// the four DMA instructions of one block
-__device__ __forceinline__ void issue_block(const XStream& st, const XLane& lv, const u32x4_t rs_w, const u32x4_t rs_kv, unsigned dst) {
-  const int kind = XU(st.kind);
-  const unsigned soff = XU(st.soff);
-  if (kind == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dma16_s(rs_w, dst + q * 1024, lv.w_d[q], soff);
-  } else if (kind == 1) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dma16_s(rs_w, dst + q * 1024, lv.w_4d[q], soff);
-  } else if (kind == 2) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dma16_s(rs_kv, dst + q * 1024, lv.kv[q], soff);
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dma16_s(rs_kv, dst + q * 1024, lv.kvc[q], soff);
-  }
-}
-struct XProd {  // launch constants of the producer
-  u32x4_t rs_w, rs_kv;  // descriptors: the bf16 shadow of the parameter arena; layer 0's cross K/V
-  const unsigned* tab;  // this wave's unit table (LDS)
-  unsigned ring_lds;    // LDS byte address of this wave's ring
-};
-// issue the next block into ring slot islot and advance
-__device__ __forceinline__ void ring_issue(const XArgs& a, XStream& st, const XLane& lv, const XProd& pr) {
-  if (!st.more) return;
-  issue_block(st, lv, pr.rs_w, pr.rs_kv, pr.ring_lds + (unsigned)st.islot * SLOT);
-  st.issued = XU(st.issued + 1);
-  st.islot = XU(st.islot + 1 == XR ? 0 : st.islot + 1);
-  unit_advance(a, st, pr.tab);
-}
-// block `consumed` has landed: at most (issued - consumed - 1) younger blocks may still be in flight (loads return in order)
-__device__ __forceinline__ void ring_wait(const XStream& st, int = 0) {
-  const int younger = XU(st.issued - st.consumed - 1);
-  if (younger >= 5) XWAIT_VM(20);
-  else if (younger == 4) XWAIT_VM(16);
-  else if (younger == 3) XWAIT_VM(12);
-  else if (younger == 2) XWAIT_VM(8);
-  else if (younger == 1) XWAIT_VM(4);
-  else XWAIT_VM(0);
-}
-
-// ---- team barrier (helper wave) ----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void team_arrive(unsigned* ctrl) {
-  XWAIT_VM(0);  // this workgroup's stores of the phase have been acknowledged
-  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(ctrl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void team_wait(unsigned* ctrl, unsigned target, int flags = 0) {
-  if ((threadIdx.x & 63) == 0) {  // one lane polls; the wave reconverges behind it
-    unsigned spins = 0;
-    while ((int)(__hip_atomic_load(ctrl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
-      if (!(flags & 4)) __builtin_amdgcn_s_sleep(1);
-      if (++spins > SPIN_LIMIT || ((spins & 63) == 0 && __hip_atomic_load(ctrl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-        __hip_atomic_fetch_or(ctrl + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // a team member never arrived: poison, do not hang
-        break;
-      }
-    }
-  }
-}
-
 // dynamic LDS block, byte offsets (compile-time: d <= XMAXD fixes the operand row stride)
-constexpr int XMAXD = 1280;
-constexpr unsigned XL_RING = 0;
 constexpr unsigned XL_XS = 4 * XMAXD * 2 + 16;  // row stride of the activation operand: K_max = 4d, + 16 so the rows sit on different banks
 constexpr unsigned XL_XBUF = XL_RING + 4 * XR * SLOT;
 constexpr unsigned XL_RED = XL_XBUF + XMAXM * XL_XS;
@@ -385,8 +49,6 @@ struct XGemv {  // one projection phase
   bf16_t* out;
   long ldc;
 };
-
-__device__ __forceinline__ float rdlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
 // helper wave: activation rows of a projection phase -> LDS operand rows (bf16).  Every global load of a row is issued before the first
 // one is used: ONE round trip per row, not one per chunk.
@@ -505,37 +167,6 @@ __device__ __forceinline__ void helper_epilogue(const XArgs& a, const XGemv& ph,
   st4_x(ph.out + (long)m * ph.ldc + n0 + 2 * cp, pack_bf2(y[0], y[1]), a.flags);
 }
 
-// ---- fast run: `run` consecutive ring blocks during which nothing special happens on either side -- the consumer's blocks are full, the
-// producer stays inside its current unit (st.left full blocks with one descriptor / lane-offset set) and the ring is in its steady state
-// (XR blocks in flight: the block consumed and the block issued share a slot).  Per block: one counted wait, the consumer's body on the
-// slot, four DMA instructions, a handful of scalar updates -- no cursor arithmetic (the general path costs ~1.7 k cycles of
-// instruction issue per block, profiles/r05_decode_xcd_stamps_v3_instruction_bound.txt).
-__device__ __forceinline__ int fast_run_len(const XStream& st, int consumer_full_left) {
-  return (consumer_full_left > 0 && st.more && st.issued - st.consumed == XR) ? consumer_full_left : 0;
-}
-template <typename F>
-__device__ __forceinline__ void fast_run(const XArgs& a, XStream& st, const XLane& lv, const XProd& pr, char* smem, int wave, int run, F&& body) {
-  int i = 0;
-  for (; i < run && st.more; ++i) {
-    XWAIT_VM(20);  // 4 * (XR - 1): the oldest block in flight has landed
-    body(smem + XL_RING + (wave * XR + st.cslot) * SLOT, i);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the body's reads of the slot have retired: it may be re-staged
-    issue_block(st, lv, pr.rs_w, pr.rs_kv, pr.ring_lds + (unsigned)st.cslot * SLOT);  // (steady state: islot == cslot)
-    st.cslot = XU(st.cslot + 1 == XR ? 0 : st.cslot + 1);
-    unit_advance(a, st, pr.tab);
-  }
-  st.islot = st.cslot;
-  st.issued = XU(st.issued + i), st.consumed = XU(st.consumed + i);
-  // the producer ran dry inside the run (the step's last blocks): the rest of the run is consumed without issuing
-  for (; i < run; ++i) {
-    ring_wait(st, a.flags);
-    body(smem + XL_RING + (wave * XR + st.cslot) * SLOT, i);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    st.consumed = XU(st.consumed + 1);
-    st.cslot = XU(st.cslot + 1 == XR ? 0 : st.cslot + 1);
-  }
-}
-
 // streaming waves: the tiles of one projection phase, back to back.  A tile = this wave's K quarter of 32 weight rows against the operand
 // rows, through the ring; its 16 accumulators go to one of NRED reduction buffers.  The helper wave is met once per GROUP of NRED tiles
 // (every phase of every model up to d = 1024 is one group), not once per tile.
@@ -584,10 +215,10 @@ __device__ __forceinline__ void stream_phase(const XArgs& a, const XGeom& g, XSt
       });
     } else {
       if (DBG) {
-        if (cc.seg != ph.seg || cc.idx != tile || cc.sub != kb) __hip_atomic_fetch_or(a.ctrl + 1, 0x100u | (unsigned)ph.seg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cc.seg != ph.seg || cc.idx != tile || cc.sub != kb) __hip_atomic_fetch_or(a.ctrl + dec::KV_ERROR, dec::KV_ERR_STREAM | (unsigned)ph.seg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         cur_advance(g, cc);
       }
-      ring_wait(st, a.flags);
+      ring_wait(st);
       const char* slot = smem + XL_RING + (wave * XR + st.cslot) * SLOT;
       int steps = nst - kb * 4;
       steps = steps > 4 ? 4 : steps;
@@ -596,10 +227,7 @@ __device__ __forceinline__ void stream_phase(const XArgs& a, const XGeom& g, XSt
         const bf16x8_t xf = *(const bf16x8_t*)(xrow + (kb * 4 + q) * 32);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, xf, acc, 0, 0, 0);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's reads have retired before it is re-staged
-      st.consumed = XU(st.consumed + 1);
-      st.cslot = XU(st.cslot + 1 == XR ? 0 : st.cslot + 1);
-      ring_issue(a, st, lv, pr);
+      ring_consumed(a, st, lv, pr);
       if (++kb == nkb) tile_done();
     }
     if (kb == 0 && (tile == ntile || (tile & (NRED - 1)) == 0)) {  // a group is complete: hand its accumulators to the helper wave
@@ -610,7 +238,7 @@ __device__ __forceinline__ void stream_phase(const XArgs& a, const XGeom& g, XSt
 }
 
 __device__ __forceinline__ XGemv gemv_of(const XArgs& a, int layer, int ph) {
-  XLayer ly = layer_of(a, layer);
+  const DecLayerOffsets ly = dec::layer_at(a.l0, layer, a.lstride, a.astride);
   bf16_t* self = a.cache + (long)layer * a.cache_lstride;
   XGemv p;
   p.merge_attn = false, p.gelu = false, p.ln_g = p.ln_b = nullptr, p.resid = nullptr, p.K = a.d, p.N = a.d, p.ldc = a.d;
@@ -655,7 +283,7 @@ __global__ __launch_bounds__(320) void decode_xcd_kernel(XArgs a) {
   XGeom g = make_geom(a.d, a.H, a.Te, a.M, a.L, a.team, wg);
   g.cnt_qkv = __builtin_amdgcn_readfirstlane(g.cnt_qkv), g.cnt_d = __builtin_amdgcn_readfirstlane(g.cnt_d);
   g.cnt_4d = __builtin_amdgcn_readfirstlane(g.cnt_4d), g.cnt_it = __builtin_amdgcn_readfirstlane(g.cnt_it);
-  const unsigned base = a.ctrl[2];  // epoch: the counter is never reset, every launch adds (phases x team) to it
+  const unsigned base = a.ctrl[dec::KV_TEAM_EPOCH];  // epoch: the counter is never reset, every launch adds (phases x team) to it
   const unsigned ring_lds = (unsigned)(size_t)(smem + XL_RING) + (unsigned)wave * XR * SLOT;
   unsigned gphase = 0;  // phases completed by the whole team before the current one
   const XLane lv = make_lane(a.d, a.Te, wave, lane);
@@ -678,7 +306,7 @@ __global__ __launch_bounds__(320) void decode_xcd_kernel(XArgs a) {
       st.nunits = XU(build_units(bp, wave, lane, (unsigned*)(smem + XL_TAB) + wave * (XTABN * 4)));
     }
     st.more = st.nunits > 0 && st.nunits < XTABN;  // (a full table means the walk was cut short: never the case for a supported shape)
-    if (st.nunits >= XTABN && lane == 0) __hip_atomic_fetch_or(a.ctrl + 1, 0x200u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (st.nunits >= XTABN && lane == 0) __hip_atomic_fetch_or(a.ctrl + dec::KV_ERROR, dec::KV_ERR_TABLE_FULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (st.more) unit_load(a, st, pr.tab);
     cur_normalise(g, cc);
     for (int i = 0; i < XR; ++i) ring_issue(a, st, lv, pr);
@@ -687,7 +315,7 @@ __global__ __launch_bounds__(320) void decode_xcd_kernel(XArgs a) {
     if (lane == 0) {
       unsigned xcc;
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      __hip_atomic_fetch_or(a.ctrl + 3, 1u << (xcc & 15), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_or(a.ctrl + dec::KV_XCC_MASK, 1u << (xcc & 15), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     for (int i = lane; i < (int)(XMAXM * XL_XS / 4); i += 64) ((unsigned*)(smem + XL_XBUF))[i] = 0u;  // operand rows >= M read as zeros
   }
@@ -771,10 +399,10 @@ __global__ __launch_bounds__(320) void decode_xcd_kernel(XArgs a) {
                   continue;
                 }
                 if (DBG) {
-                  if (cc.seg != 3 || cc.idx != j || cc.sub != kb) __hip_atomic_fetch_or(a.ctrl + 1, 0x103u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                  if (cc.seg != 3 || cc.idx != j || cc.sub != kb) __hip_atomic_fetch_or(a.ctrl + dec::KV_ERROR, dec::KV_ERR_STREAM_K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                   cur_advance(g, cc);
                 }
-                ring_wait(st, a.flags);
+                ring_wait(st);
                 const char* slot = smem + XL_RING + (wave * XR + st.cslot) * SLOT;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -785,10 +413,7 @@ __global__ __launch_bounds__(320) void decode_xcd_kernel(XArgs a) {
                     mx = fmaxf(mx, s2);
                   }
                 }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                st.consumed = XU(st.consumed + 1);
-                st.cslot = XU(st.cslot + 1 == XR ? 0 : st.cslot + 1);
-                ring_issue(a, st, lv, pr);
+                ring_consumed(a, st, lv, pr);
                 ++kb;
               }
             } else {
@@ -831,20 +456,17 @@ __global__ __launch_bounds__(320) void decode_xcd_kernel(XArgs a) {
                   continue;
                 }
                 if (DBG) {
-                  if (cc.seg != 3 || cc.idx != j || cc.sub != it.kvb + kb) __hip_atomic_fetch_or(a.ctrl + 1, 0x113u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                  if (cc.seg != 3 || cc.idx != j || cc.sub != it.kvb + kb) __hip_atomic_fetch_or(a.ctrl + dec::KV_ERROR, dec::KV_ERR_STREAM_V, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                   cur_advance(g, cc);
                 }
-                ring_wait(st, a.flags);
+                ring_wait(st);
                 const char* slot = smem + XL_RING + (wave * XR + st.cslot) * SLOT;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                   const int t = 32 * (kb * 4 + q) + grp;
                   dec::accum_pv(t < n ? __builtin_amdgcn_exp2f(sc[t] - m) : 0.f, *(const u32x4_t*)(slot + q * 1024 + lane * 16), l, o);
                 }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                st.consumed = XU(st.consumed + 1);
-                st.cslot = XU(st.cslot + 1 == XR ? 0 : st.cslot + 1);
-                ring_issue(a, st, lv, pr);
+                ring_consumed(a, st, lv, pr);
                 ++kb;
               }
             } else {
@@ -920,79 +542,29 @@ __global__ __launch_bounds__(320) void decode_xcd_kernel(XArgs a) {
   if (helper) {
     if (wg == 0) {  // everybody has read the epoch base long ago; publish the next launch's once the whole team is through
       team_wait(a.ctrl, base + gphase * (unsigned)a.team);
-      if (lane == 0) a.ctrl[2] = base + gphase * (unsigned)a.team;
+      if (lane == 0) a.ctrl[dec::KV_TEAM_EPOCH] = base + gphase * (unsigned)a.team;
     }
   }
 }
 
 }  // namespace
 
-// ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t decode_xcd_part_floats(int M, int H, int Te) { return (size_t)M * H * dec::n_segments(Te) * 66; }
-
-bool decode_xcd_supports(int d, int H, int Te, int S_max, int L, int M) {
-  // (d % 256: a wave's K quarter is whole 64-element ring blocks)
-  return M >= 1 && M <= XMAXM && L >= 1 && L <= XMAXL && d % 256 == 0 && d == H * 64 && d <= XMAXD && S_max <= dec::SEG_KEYS &&
-         Te <= dec::MAX_SEG * dec::SEG_KEYS && Te >= 1 && H * dec::n_segments(Te) <= XMAXPAIR;
-}
-
-// The ring DMA addresses everything through raw buffer descriptors with 32-bit byte offsets from the start of the bf16 weight shadow and
-// from layer 0's cross K/V rows (rsrc_of / dma16: num_records 0x7fffffff): an offset at or past 2 GiB would read zeros without any error.
-// True when the furthest byte any block of this launch can address stays below that (weights: OLMoASR-large ends at ~1.7 GB because the
-// decoder sits at the start of the arena); the engine takes the multi-launch step otherwise.
-bool decode_xcd_offsets_ok(const int64_t* layer0, long lstride, long cache_lstride, int d, int Te, int L, int M) {
-  const long kLimit = (1L << 31) - (1L << 20);  // 1 MiB of slack for the per-lane part of an address
-  const int wsel[6] = {2, 4, 8, 10, 14, 16};  // XLayer: wqkv, wo, wcq, wco, w1, w2
-  const long wsize[6] = {3L * d * d, (long)d * d, (long)d * d, (long)d * d, 4L * d * d, 4L * d * d};
-  // layer l = layer 0 + l * lstride; the arena keeps the decoder blocks in gradient-completion order (last block first), so the stride
-  // is NEGATIVE in the product's layout: both ends of the walk are checked
-  const long span = (long)(L - 1) * lstride;
-  for (int k = 0; k < 6; ++k) {
-    const long first = layer0[wsel[k]] + (span < 0 ? span : 0), last = layer0[wsel[k]] + (span > 0 ? span : 0) + wsize[k];
-    if (first < 0 || last * 2 >= kLimit) return false;
-  }
-  const long kv_end = (long)(L - 1) * cache_lstride + (long)M * Te * 2 * d;  // from layer 0's cross K/V rows
-  return cache_lstride >= 0 && kv_end * 2 < kLimit;
-}
-
-extern "C" int oasr_xcd_offsets_ok_debug(const int64_t* layer0, long long lstride, long long cache_lstride, int d, int Te, int L, int M) {
-  return decode_xcd_offsets_ok(layer0, (long)lstride, (long)cache_lstride, d, Te, L, M) ? 1 : 0;
-}
-
-// Debug / CPU test: the block sequence (seg, idx, sub) of workgroup `wg` as the kernel's cursors generate it
-extern "C" int oasr_xcd_plan_debug(int d, int H, int Te, int M, int L, int team, int wg, int* out, int max_blocks) {
-  const XGeom g = make_geom(d, H, Te, M, L, team, wg);
-  XCur c{0, 0, 0, 0};
-  int n = 0;
-  bool more = cur_normalise(g, c);
-  while (more) {
-    if (n < max_blocks) out[4 * n] = c.layer, out[4 * n + 1] = c.seg, out[4 * n + 2] = c.idx, out[4 * n + 3] = c.sub;
-    ++n;
-    more = cur_advance(g, c);
-  }
-  return n;
-}
-
-int launch_decode_xcd(const DecodeXcdArgs& h, hipStream_t s) {
+// (which shapes and layouts the engine takes: decode_plan_host.cpp)
+int launch_decode_xcd(const DecodeStepArgs& h, hipStream_t s) {
   OASR_REQUIRE(decode_xcd_supports(h.d, h.H, h.Te, h.S_max, h.L, h.M), "decode_xcd: unsupported shape (d=%d H=%d Te=%d S=%d L=%d M=%d)", h.d, h.H,
                h.Te, h.S_max, h.L, h.M);
   OASR_REQUIRE(h.team >= 1 && h.team <= 256 && (h.stride == 1 || h.stride == 8) && h.pos >= 0 && h.pos < h.S_max, "decode_xcd: bad launch shape");
-  OASR_REQUIRE(decode_xcd_offsets_ok(h.layer_offsets, h.lstride, h.cache_lstride, h.d, h.Te, h.L, h.M),
+  OASR_REQUIRE(decode_xcd_offsets_ok(h.l0, h.lstride, h.cache_lstride, h.d, h.Te, h.L, h.M),
                "decode_xcd: a weight / cross K/V byte offset reaches 2 GiB (32-bit buffer offsets); use the multi-launch step");
   XArgs a;
-  a.wflat = h.wflat, a.params = h.params, a.aux = h.aux, a.cache = h.cache, a.cache_lstride = h.cache_lstride;
-  a.x = h.x, a.x2 = h.x2, a.x3 = h.x3, a.q = h.q, a.o = h.o, a.hg = h.hg, a.part = h.part, a.ctrl = h.ctrl;
+  static_cast<DecodeStepBufs&>(a) = h;
   a.d = h.d, a.H = h.H, a.Te = h.Te, a.S_max = h.S_max, a.L = h.L, a.M = h.M, a.pos = h.pos, a.team = h.team, a.stride = h.stride;
   a.flags = h.flags, a.stamps = (unsigned long long*)h.stamps;
-  {
-    const int64_t* o = h.layer_offsets;  // layer 0
-    a.l0 = XLayer{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12], o[13], o[14], o[15], o[16], o[17]};
-    a.lstride = h.lstride, a.astride = h.astride;
-  }
+  a.l0 = h.l0, a.lstride = h.lstride, a.astride = h.astride;
   const unsigned lds = XL_TOTAL;
   static LdsAttrOnce attr;
   static LdsAttrOnce attr_dbg;
-  if (h.flags & 8) {  // checked instantiation (tests)
+  if (h.flags & dec::XF_CHECKED) {  // checked instantiation (tests)
     { const int rc_ = ensure_dynamic_lds(attr_dbg, (const void*)decode_xcd_kernel<true>, (int)lds); if (rc_) return rc_; }
     hipLaunchKernelGGL(decode_xcd_kernel<true>, dim3(h.team * h.stride), dim3(320), lds, s, a);
   } else {

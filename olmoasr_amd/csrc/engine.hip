@@ -196,26 +196,27 @@ extern "C" oasr_ctx* oasr_create_ex3(const oasr_dims* dm, int embed_rows, int co
     c->pr.tr.assign(c->tensors.size(), 0);
     c->pr.need.assign(c->tensors.size(), 0);
   }
-  {  // decoder layer 0's tensor offsets (decode_xcd.hip::XLayer order) + the per-layer strides: the one-launch step engine derives every
-     // layer's addresses from them, so the blocks must be laid out back to back with one stride -- checked here, engine off otherwise
+  {  // decoder layer 0's tensor offsets + the per-layer strides: the one-launch step engines derive every layer's addresses from them, so
+     // the blocks must be laid out back to back with one stride -- checked here, engines off otherwise
     auto offs = [](const BlockP& bp) {
-      return std::vector<int64_t>{bp.attn_ln_w, bp.attn_ln_b, bp.attn.qw, bp.attn.fused_bias, bp.attn.ow, bp.attn.ob, bp.cln_w, bp.cln_b, bp.cattn.qw,
-                                  bp.cattn.qb, bp.cattn.ow, bp.cattn.ob, bp.mlp_ln_w, bp.mlp_ln_b, bp.w1, bp.b1, bp.w2, bp.b2};
+      DecLayerOffsets o;
+      o.ln1g = bp.attn_ln_w, o.ln1b = bp.attn_ln_b, o.wqkv = bp.attn.qw, o.bqkv_aux = bp.attn.fused_bias, o.wo = bp.attn.ow, o.bo = bp.attn.ob;
+      o.lncg = bp.cln_w, o.lncb = bp.cln_b, o.wcq = bp.cattn.qw, o.bcq = bp.cattn.qb, o.wco = bp.cattn.ow, o.bco = bp.cattn.ob;
+      o.ln2g = bp.mlp_ln_w, o.ln2b = bp.mlp_ln_b, o.w1 = bp.w1, o.b1 = bp.b1, o.w2 = bp.w2, o.b2 = bp.b2;
+      return o;
     };
     if (c->L_dec >= 1) {
-      c->xcd_offsets = offs(c->dec[0]);
-      c->xcd_lstride = c->xcd_astride = 0;
+      c->dec_l0 = offs(c->dec[0]);
       if (c->L_dec >= 2) {
-        const std::vector<int64_t> o1 = offs(c->dec[1]);
-        c->xcd_lstride = o1[0] - c->xcd_offsets[0];
-        c->xcd_astride = o1[3] - c->xcd_offsets[3];
+        const DecLayerOffsets o1 = offs(c->dec[1]);
+        c->dec_lstride = o1.ln1g - c->dec_l0.ln1g;
+        c->dec_astride = o1.bqkv_aux - c->dec_l0.bqkv_aux;
       }
-      bool regular = true;
+      c->dec_regular = true;
       for (int l = 0; l < c->L_dec; ++l) {
-        const std::vector<int64_t> ol = offs(c->dec[l]);
-        for (int k = 0; k < 18; ++k) regular = regular && ol[k] == c->xcd_offsets[k] + (int64_t)l * (k == 3 ? c->xcd_astride : c->xcd_lstride);
+        const DecLayerOffsets ol = offs(c->dec[l]), want = dec::layer_at(c->dec_l0, l, c->dec_lstride, c->dec_astride);
+        for (int k = 0; k < DecLayerOffsets::FIELDS; ++k) c->dec_regular = c->dec_regular && ol.fields()[k] == want.fields()[k];
       }
-      if (!regular) c->xcd_offsets.clear();
     }
   }
   // shadow: [bf16 flat arena + zero pad rows for the padded vocab] [W1p d x 256] [W2p d x 3d] [aux fp32]

@@ -51,8 +51,9 @@ struct oasr_ctx {
   size_t sh_flat, sh_w1p, sh_w2p, sh_aux, sh_total;
   int64_t aux_floats;
   int f32 = 0;  // compute_dtype: 0 = bf16 production kernels, 1 = fp32 validation kernels (fp32ref.hip)
-  std::vector<int64_t> xcd_offsets;  // decoder layer 0's 18 tensor offsets in decode_xcd.hip::XLayer order (empty: irregular layout, engine off)
-  int64_t xcd_lstride = 0, xcd_astride = 0;  // layer l = layer 0 + l * stride
+  DecLayerOffsets dec_l0 = {};       // decoder layer 0's tensor offsets (the one-launch step engines derive every layer's from them)
+  int64_t dec_lstride = 0, dec_astride = 0;  // layer l = dec::layer_at(dec_l0, l, dec_lstride, dec_astride)
+  bool dec_regular = false;          // ... holds for every decoder block (false: irregular layout, one-launch engines off)
   // Side stream of the span step's decoder backward (Runner::wgrad_side): created on first use, lowest priority, so its weight-gradient
   // workgroups fill the compute units the main stream's launches leave idle
   struct Side {

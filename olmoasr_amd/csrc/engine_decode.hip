@@ -1,5 +1,7 @@
 // KV-cache greedy decoding: cache layout, the choice between the three step engines, and the multi-launch step itself.
 #include "engine_run.h"
+#include "decode_wide_plan.h"
+#include "decode_xcd_plan.h"
 
 // ---- cached greedy decoding (OLMoASR.install_kv_cache_hooks, olmoasr/model.py:925-964 / inf_model.py:422-453) -----------
 // The reference caches every key/value Linear output in a dict via forward hooks (self-attention K/V grow by torch.cat per
@@ -25,33 +27,30 @@ unsigned* kv_ctrl(const oasr_ctx* c, void* cache, int B) {  // the control tail 
   return (unsigned*)((char*)cache + kv_layer_elems(c, B) * (c->f32 ? 4 : 2) * c->L_dec);
 }
 
-// A/B and test switch of the step engine: -1 = default (ONE sequence on the bf16 engine: the chip-wide one-launch engine of decode_wide.hip; 2-4
-// sequences: LayerNorm folded into the projections; more: separate kernels), 0 = separate LayerNorm kernels, 1 = LayerNorm folded into the projections'
-// operand loads (the round-2/3 default for B <= 4) for every B <= 32, 2 = the one-launch team engine of decode_xcd.hip on one XCD, 3 = that team as 32
-// workgroups spread over the chip, 4 = the same with 64, 5 = the chip-wide engine.  0-4 bit-identical, 5 within fp32 summation-order rounding
-// (tests/test_gpu_decode_step.py).
-int g_decode_ln_fold = -1;
+// A/B and test switch of the step engine (oasr_decode_set_ln_fold; decode_step_core.h: StepMode).  STEP_SEPARATE_LN .. STEP_TEAM_SPREAD64 are
+// bit-identical, STEP_WIDE within fp32 summation-order rounding (tests/test_gpu_decode_step.py).
+int g_step_mode = dec::STEP_DEFAULT;
 
 // The engine one step runs on.  Neither `wide` nor `team`: the multi-launch step, with (`folded`) or without LayerNorm folded into the projections.
 struct StepEngine {
   bool folded = false, team = false, wide = false;
-  int nwg = 0, stride = 0;  // one-launch engines: workgroups, and 8 = one per CU of ONE XCD / 1 = spread over the chip (DecodeXcdArgs::team, stride)
+  int nwg = 0, stride = 0;  // one-launch engines: workgroups, and 8 = one per CU of ONE XCD / 1 = spread over the chip (DecodeStepArgs::team, stride)
 };
 int pick_step_engine(oasr_ctx* c, int B, StepEngine& e) {
   e = StepEngine();
   if (c->f32) return OASR_OK;  // (fp32 validation: separate kernels only)
-  const int d = c->d, S_max = c->S_max, mode = g_decode_ln_fold;
+  const int d = c->d, S_max = c->S_max, mode = g_step_mode;
   // a few sequences on the bf16 engine: every LayerNorm rides in the operand load of the projection that consumes it and the
   // logits leave as fp32 (8 launches per layer instead of 11; bit-identical to the separate kernels).  Measured
   // (profiles/r02_decode_step.txt): -5 % per step at B = 1, but every workgroup recomputes the B row statistics, which loses
   // from B = 16 on (+20 %) -- so only small batches take it (oasr_decode_set_ln_fold forces either side for the A/B and the
   // bit-identity test).
-  e.folded = d % 64 == 0 && d <= 2048 && mode != 0 && (B <= 4 || (mode == 1 && B <= 32));
+  e.folded = d % 64 == 0 && d <= 2048 && mode != dec::STEP_SEPARATE_LN && (B <= 4 || (mode == dec::STEP_FOLDED_LN && B <= 32));
   // one launch for the whole decoder stack (decode_xcd.hip): the default for a handful of sequences
   // (default: ONE sequence -- the timestamp-mode transcribe loop -- on the chip-wide one-launch engine, decode_wide.hip: 0.74 ms per token at medium
   // against 1.76 for the one-XCD team of decode_xcd.hip and 2.44 multi-launch, profiles/r06_decode_wide.txt; at small B = 4 the multi-launch
-  // kernels, which spread over the whole chip, win: profiles/r05_decode_xcd_probe_v8.txt.  Mode 5 forces the chip-wide engine, modes 2-4 the
-  // team engine up to B = 4.)
+  // kernels, which spread over the whole chip, win: profiles/r05_decode_xcd_probe_v8.txt.  STEP_WIDE forces the chip-wide engine, the STEP_TEAM_*
+  // modes the team engine up to B = 4.)
   if (c->n_cu == 0) {
     int dev = 0, n = 0;
     OASR_CHECK_HIP(hipGetDevice(&dev));
@@ -59,12 +58,13 @@ int pick_step_engine(oasr_ctx* c, int B, StepEngine& e) {
     c->n_cu = n > 0 ? n : -1;
   }
   const int nwg = c->n_cu >= 256 ? 256 : (c->n_cu > 0 ? c->n_cu & ~3 : 0);
-  const bool one_launch = !c->xcd_disabled && !c->xcd_offsets.empty();
-  e.wide = (mode == -1 || mode == 5) && B == 1 && one_launch && decode_wide_supports(d, c->H, c->Te, S_max, c->L_dec, B, nwg, c->V);
-  e.team = !e.wide && ((mode == -1 && B == 1) || mode >= 2) && one_launch && decode_xcd_supports(d, c->H, c->Te, S_max, c->L_dec, B) &&
-           decode_xcd_offsets_ok(c->xcd_offsets.data(), c->xcd_lstride, (long)kv_layer_elems(c, B), d, c->Te, c->L_dec, B);
-  e.nwg = e.wide ? nwg : (mode == 4 ? 64 : 32);
-  e.stride = (e.wide || mode == 3 || mode == 4) ? 1 : 8;
+  const bool one_launch = !c->xcd_disabled && c->dec_regular;
+  const bool spread = mode == dec::STEP_TEAM_SPREAD32 || mode == dec::STEP_TEAM_SPREAD64;
+  e.wide = (mode == dec::STEP_DEFAULT || mode == dec::STEP_WIDE) && B == 1 && one_launch && decode_wide_supports(d, c->H, c->Te, S_max, c->L_dec, B, nwg, c->V);
+  e.team = !e.wide && ((mode == dec::STEP_DEFAULT && B == 1) || mode >= dec::STEP_TEAM_XCD) && one_launch && decode_xcd_supports(d, c->H, c->Te, S_max, c->L_dec, B) &&
+           decode_xcd_offsets_ok(c->dec_l0, c->dec_lstride, (long)kv_layer_elems(c, B), d, c->Te, c->L_dec, B);
+  e.nwg = e.wide ? nwg : (mode == dec::STEP_TEAM_SPREAD64 ? 64 : 32);
+  e.stride = (e.wide || spread) ? 1 : 8;
   return OASR_OK;
 }
 }  // namespace
@@ -75,7 +75,7 @@ extern "C" size_t oasr_kv_cache_bytes(const oasr_ctx* c, int B) {
 }
 extern "C" int oasr_decode_set_ln_fold(int mode) {
   OASR_HOOK_GATE("oasr_decode_set_ln_fold");
-  g_decode_ln_fold = mode < 0 ? -1 : (mode > 5 ? 1 : mode);
+  g_step_mode = mode < 0 ? dec::STEP_DEFAULT : (mode > dec::STEP_WIDE ? dec::STEP_FOLDED_LN : mode);  // (the clamping is part of the hook's contract)
   return OASR_OK;
 }
 
@@ -92,7 +92,7 @@ static int oasr_decode_begin_impl(oasr_ctx* c, const void* xa, int B, void* kv_c
   OASR_REQUIRE(xa && kv_cache && B > 0, "oasr_decode_begin: bad args");
   typename Engine<T>::Runner r{c, (hipStream_t)stream, B, 1, nullptr};
   const int d = c->d;
-  // the one-launch step engine's control words (barrier counter, error flag, epoch base, XCC mask) live in the cache's 256-byte tail
+  // the one-launch step engines' control words, flags and packets live in the cache's tail (decode_step_core.h: KvCtrl)
   OASR_CHECK_HIP(hipMemsetAsync(kv_ctrl(c, kv_cache, B), 0, OASR_KV_TAIL_BYTES, (hipStream_t)stream));
   for (int i = 0; i < c->L_dec; ++i) {
     const BlockP& bp = c->dec[i];
@@ -139,7 +139,7 @@ int folded_logits(const oasr_ctx* c, const bf16_t* x, int B, float* logits_out, 
 // the whole decoder stack of one token in ONE launch (w.x: the embedded token): the chip-wide engine, which also projects the logits, or the
 // team engine followed by the folded logits projection
 int launch_one_launch_step(const oasr_ctx* c, const StepEngine& e, StepWs<bf16_t>& w, int B, int pos, void* kv_cache, float* logits_out, hipStream_t st) {
-  DecodeXcdArgs xa;
+  DecodeStepArgs xa;
   xa.wflat = c->Wt<bf16_t>(0);
   xa.params = c->params;
   xa.aux = c->aux(0);
@@ -156,11 +156,10 @@ int launch_one_launch_step(const oasr_ctx* c, const StepEngine& e, StepWs<bf16_t
       const char* e = oasr_experiment_env("OASR_XCD_FLAGS");
       return e ? atoi(e) : 0;
     }();
-    xa.flags = (xflags & 0xff) | (((xflags >> 9) & 0xff) << 8);  // (bits 9-16: the workgroup whose stamps the chip-wide engine takes)
-    xa.stamps = (xflags & 0x100) ? (void*)(w.A.base + w.A.cap - 512) : nullptr;
+    xa.flags = (xflags & 0xff) | (((xflags >> dec::XF_STAMP_WG_SHIFT) & 0xff) << 8);  // (bits 9-16: the workgroup whose stamps the chip-wide engine takes)
+    xa.stamps = (xflags & dec::XF_STAMPS) ? (void*)(w.A.base + w.A.cap - 512) : nullptr;
   }
-  xa.layer_offsets = c->xcd_offsets.data();
-  xa.lstride = c->xcd_lstride, xa.astride = c->xcd_astride;
+  xa.l0 = c->dec_l0, xa.lstride = c->dec_lstride, xa.astride = c->dec_astride;
   if (e.wide) {  // ... and the final LayerNorm + logits projection as its last phase: one launch per token behind the embedding
     xa.w_logits = c->Wt<bf16_t>(c->tok_emb), xa.lnf_g = c->P(c->dec_ln_w), xa.lnf_b = c->P(c->dec_ln_b), xa.logits_out = logits_out, xa.V = c->V;
     return launch_decode_wide(xa, st);
@@ -285,9 +284,9 @@ extern "C" int oasr_decode_reorder(oasr_ctx* c, void* kv_cache, int B, int pos, 
 extern "C" int oasr_decode_check(oasr_ctx* c, int B, void* kv_cache, void* stream) {
   OASR_REQUIRE(c && kv_cache && B > 0, "oasr_decode_check: bad args");
   OASR_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-  unsigned ctrl[4] = {0, 0, 0, 0};  // the one-launch step engine's control words: a poisoned team barrier / a desynchronised stream is an error
+  unsigned ctrl[dec::KV_CTRL_WORDS] = {};  // the one-launch step engines' control words: a poisoned team barrier / a desynchronised stream is an error
   OASR_CHECK_HIP(hipMemcpy(ctrl, kv_ctrl(c, kv_cache, B), sizeof(ctrl), hipMemcpyDeviceToHost));
-  if (ctrl[1] != 0) {
+  if (ctrl[dec::KV_ERROR] != 0) {
     // The one-launch engine needs its whole team (32 workgroups x ~160 KB of LDS on one XCD) resident at once; a second decoder on the same
     // device, or a CU-masked / partitioned device, can leave part of a team queued behind the rest, and the bounded spin then poisons the
     // barrier instead of hanging.  Nothing is wrong with the cache's K/V rows written before that step, but the window's tokens are: the
@@ -297,7 +296,7 @@ extern "C" int oasr_decode_check(oasr_ctx* c, int B, void* kv_cache, void* strea
     OASR_CHECK_HIP(hipMemset(kv_ctrl(c, kv_cache, B), 0, OASR_KV_TAIL_BYTES));
     oasr_set_error("oasr_decode_check: the one-launch decoder step reported 0x%x (1 = a team member never reached a barrier -- is the device "
                    "shared or CU-masked? --, 0x1xx = block stream out of step); XCC mask 0x%x.  The one-launch engine is now disabled for this "
-                   "context; decode the window again (it will run on the multi-launch engine)", ctrl[1], ctrl[3]);
+                   "context; decode the window again (it will run on the multi-launch engine)", ctrl[dec::KV_ERROR], ctrl[dec::KV_XCC_MASK]);
     return OASR_ERETRY;
   }
   return OASR_OK;

@@ -1,6 +1,7 @@
 // Internal launch interface between the kernel translation units and the engine (not part of the C ABI).
 #pragma once
 #include "common.h"
+#include "decode_step_core.h"
 
 // A row-major bf16 operand, optionally viewed as overlapping convolution windows:
 //   plain   : element (r, k) at  r*ld + k
@@ -171,18 +172,21 @@ int launch_attention_scores(const AttnArgsF& a, float* out, hipStream_t s);
 int launch_decode_proj(const bf16_t* x, int M, int K, const bf16_t* W, int N, const float* ln_g, const float* ln_b, const float* bias,
                        int gelu, const bf16_t* resid, long ldr, bf16_t* out, long ldc, float* out_f32, long ldf, hipStream_t s);
 
-// ---- one-launch decoder step for <= 4 sequences (decode_xcd.hip) -----------------------------------------------
-struct DecodeXcdArgs {
+// ---- one-launch decoder steps: the one-XCD team for <= 4 sequences (decode_xcd.hip), the chip-wide engine for one (decode_wide.hip) ----------
+// Host-only: what either launcher takes.  Which shapes and layouts an engine accepts: decode_xcd_plan.h / decode_wide_plan.h.
+struct DecodeStepBufs {  // the memory of a step: what the launchers hand on unchanged, so both kernels' arguments begin with it too
   const bf16_t* wflat;  // bf16 shadow of the flat parameter arena
   const float* params;  // fp32 parameter arena (LayerNorm parameters, biases)
   const float* aux;     // fused [q_bias | 0 | v_bias] rows
   bf16_t* cache;        // KV cache (per layer: self q|k|v [M, S_max, 3d], cross k|v [M, Te, 2d])
   long cache_lstride;   // elements per layer
-  bf16_t *x, *x2, *x3, *q, *o, *hg;  // activation rows: x holds the embedded token on entry and the last block's output on return
-  float* part;          // decode_xcd_part_floats() floats
-  unsigned* ctrl;       // 4 words, zeroed once per cache (oasr_decode_begin): barrier counter, error flag, epoch base, XCC mask
+  bf16_t *x, *x2, *x3, *q, *o, *hg;  // activation rows [M][d] ([M][4d] for hg): x holds the embedded token on entry and the last block's output on return
+  float* part;          // cross-attention partials (m, l, o[64]): decode_xcd_part_floats() / decode_wide_part_floats() floats
+  unsigned* ctrl;       // the cache's control tail (OASR_KV_TAIL_BYTES, laid out by decode_step_core.h), zeroed once per cache (oasr_decode_begin)
+};
+struct DecodeStepArgs : DecodeStepBufs {
   int d, H, Te, S_max, L, M, pos;
-  int flags;            // experiments (decode_xcd.hip::XArgs::flags), 0 in production
+  int flags;            // experiments (decode_step_core.h: StepFlags), 0 in production
   void* stamps;         // optional 512-byte device buffer for in-kernel cycle stamps (measurement), or null
   int team, stride;     // `team` workgroups; stride 8 = one per CU of ONE XCD (grid 8 x team, blockIdx % 8 == 0), 1 = spread over the chip
   // chip-wide engine only: the final LayerNorm + tied logits projection as the launch's last phase (null logits_out: not done there)
@@ -190,20 +194,11 @@ struct DecodeXcdArgs {
   const float *lnf_g = nullptr, *lnf_b = nullptr;
   float* logits_out = nullptr;       // f32 [V]
   int V = 0;
-  const int64_t* layer_offsets;   // HOST: [18] element offsets of decoder layer 0 in decode_xcd.hip::XLayer order
+  DecLayerOffsets l0;             // element offsets of decoder layer 0
   long lstride, astride;          // layer l = layer 0 + l * lstride (arena / shadow elements), + l * astride for the aux entry
 };
-int launch_decode_xcd(const DecodeXcdArgs& a, hipStream_t s);
-bool decode_xcd_supports(int d, int H, int Te, int S_max, int L, int M);
-// every 32-bit buffer offset of the launch stays below 2 GiB (else: the multi-launch step)
-bool decode_xcd_offsets_ok(const int64_t* layer0, long lstride, long cache_lstride, int d, int Te, int L, int M);
-size_t decode_xcd_part_floats(int M, int H, int Te);
-// chip-wide one-launch step for ONE sequence (decode_wide.hip): `team` = workgroups (one per CU), ctrl = the cache's control tail
-// (OASR_KV_TAIL_BYTES: words [1] error flag, [3] XCC mask, [4] epoch base; the per-workgroup flag array 4 KB in)
-int launch_decode_wide(const DecodeXcdArgs& a, hipStream_t s);
-// (V: the rows the logits phase deals out -- the token embedding's rows, unpadded; else: the team or the multi-launch step)
-bool decode_wide_supports(int d, int H, int Te, int S_max, int L, int M, int nwg, int V);
-size_t decode_wide_part_floats(int H);
+int launch_decode_xcd(const DecodeStepArgs& a, hipStream_t s);
+int launch_decode_wide(const DecodeStepArgs& a, hipStream_t s);  // `team` = workgroups (one per CU)
 
 // ---- elementwise / reductions -------------------------------------------------------------------------
 int launch_cast_f32_bf16(const float* src, bf16_t* dst, long n, hipStream_t s);

@@ -47,7 +47,7 @@ def main():
         torch.cuda.synchronize()
         net.kv_cache_check(st)
         ms = e0.elapsed_time(e1) / n
-        ctrl = st["cache"][-N.KV_TAIL_BYTES:].view(torch.int32)[:8].tolist()
+        ctrl = st["cache"][-N.KV_TAIL_BYTES:].view(torch.int32)[:N.KV_CTRL_WORDS].tolist()
         same = "" if ref is None else f"  logits == mode {modes[0]}: {bool(torch.equal(ref, last))} (max |d| {float((ref - last).abs().max()):.3g})"
         if ref is None:
             ref = last.clone()
@@ -76,7 +76,7 @@ def main():
                       f"  | phase total {(nxt - r[0]) if nxt else r[4] - r[0]:6d}")
             print(f"     layer total {t[7][4] - t[0][0]} ticks")
         print(f"{variant} B={B} pos={pos} mode {mode} [{NAMES[mode]}]: {ms:.3f} ms/step = {dbytes / ms / 1e6:.0f} GB/s = {dbytes / ms / 1e6 / 8000:.3f} of 8 TB/s; "
-              f"ctrl (counter, flag, epoch, xcc mask, wide epoch) = {ctrl[0]} {ctrl[1]:#x} {ctrl[2]} {ctrl[3]:#x} {ctrl[4]}{same}", flush=True)
+              f"ctrl (counter, flag, epoch, xcc mask, wide epoch) = {ctrl[N.KV_TEAM_COUNTER]} {ctrl[N.KV_ERROR]:#x} {ctrl[N.KV_TEAM_EPOCH]} {ctrl[N.KV_XCC_MASK]:#x} {ctrl[N.KV_WIDE_EPOCH]}{same}", flush=True)
     N.lib().oasr_decode_set_ln_fold(-1)
 
 

@@ -16,7 +16,7 @@ def _dims(mo_dims):
 
 
 def _tail(state):
-    """the control words at the start of the cache's tail (include/oasr.h, OASR_KV_TAIL_BYTES)"""
+    """the cache's tail as 32-bit words (include/oasr.h, OASR_KV_TAIL_BYTES; its layout: _native.KV_*, csrc/decode_step_core.h)"""
     from olmoasr_amd import _native as N
     return state["cache"][-N.KV_TAIL_BYTES:].view(torch.int32)
 
@@ -177,6 +177,7 @@ def test_poisoned_one_launch_engine_falls_back_to_the_multi_launch_engine(tiny_c
     hanging.  oasr_decode_check then returns OASR_ERETRY once, clears the flag and disables the one-launch engine for the CONTEXT;
     ``decode`` repeats the window and returns the tokens of the multi-launch engine."""
     import warnings
+    from olmoasr_amd import _native as N
     from olmoasr_amd.decoding import DecodingOptions, decode
     from olmoasr_amd.model import OLMoASR
     from oracle import model_oracle as mo
@@ -188,12 +189,12 @@ def test_poisoned_one_launch_engine_falls_back_to_the_multi_launch_engine(tiny_c
     xa = net.embed_audio(mel)
     st = net.kv_cache_begin(xa)
     net.kv_cache_step(st, torch.tensor([50257], device=DEV))
-    _tail(st)[1] = 1  # what a timed-out team barrier / flag poll writes
+    _tail(st)[N.KV_ERROR] = 1  # what a timed-out team barrier / flag poll writes
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         assert net.kv_cache_check(st) is False
     assert w and "multi-launch" in str(w[0].message)
-    assert int(_tail(st)[1]) == 0 and net.kv_cache_check(st) is True  # flag cleared, context switched
+    assert int(_tail(st)[N.KV_ERROR]) == 0 and net.kv_cache_check(st) is True  # flag cleared, context switched
     again = decode(net, mel, opts)  # multi-launch engine now (the same arithmetic; the chip-wide engine's K sums are ordered differently)
     assert again[0].tokens == clean[0].tokens and abs(again[0].avg_logprob - clean[0].avg_logprob) < 2e-2
     # decode() itself repeats a window whose check asks for it
@@ -204,7 +205,7 @@ def test_poisoned_one_launch_engine_falls_back_to_the_multi_launch_engine(tiny_c
     def poison_first(state):
         calls["n"] += 1
         if calls["n"] == 1:
-            _tail(state)[1] = 1
+            _tail(state)[N.KV_ERROR] = 1
         return real(state)
     net2.kv_cache_check = poison_first
     with warnings.catch_warnings():
@@ -228,13 +229,13 @@ def test_default_engine_for_one_sequence_is_the_one_launch_engine(tiny_case, wid
     for p in range(3):
         net.kv_cache_step(st, torch.tensor([50257 + p], device=DEV))
     assert net.kv_cache_check(st) is True
-    # the chip-wide engine's trace: its flag epoch (control word 4) = phases completed, every workgroup's flag at that epoch
-    epoch = int(_tail(st)[4])
+    # the chip-wide engine's trace: its flag epoch (control word KV_WIDE_EPOCH) = phases completed, every workgroup's flag at that epoch
+    epoch = int(_tail(st)[N.KV_WIDE_EPOCH])
     assert epoch == 3 * 8 * layers, f"flag epoch {epoch}: the chip-wide one-launch engine did not run"
-    for rep in range(8):  # (one replica of the flag array per XCC, 4 KB apart, the first 4 KB into the tail)
-        flags = _tail(st)[1024 * (rep + 1):1024 * (rep + 1) + 256]
+    for rep in range(N.KV_REPLICAS):  # (one replica of the flag array per XCC, 4 KB apart, the first 4 KB into the tail)
+        flags = _tail(st)[N.KV_FLAGS_WORD + N.KV_FLAG_STRIDE * rep:N.KV_FLAGS_WORD + N.KV_FLAG_STRIDE * rep + 256]
         assert int(flags.min()) == epoch and int(flags.max()) == epoch
-    assert int(_tail(st)[0]) == 0
+    assert int(_tail(st)[N.KV_TEAM_COUNTER]) == 0
     # forced onto the one-XCD team: its barrier counter runs instead
     N.lib().oasr_decode_set_ln_fold(2)
     try:
@@ -244,11 +245,11 @@ def test_default_engine_for_one_sequence_is_the_one_launch_engine(tiny_case, wid
         assert net.kv_cache_check(st2) is True
     finally:
         N.lib().oasr_decode_set_ln_fold(-1)
-    counter = int(_tail(st2)[0])
-    assert counter >= 3 * 8 * layers and int(_tail(st2)[4]) == 0, f"team barrier counter {counter}: the one-XCD engine did not run"
+    counter = int(_tail(st2)[N.KV_TEAM_COUNTER])
+    assert counter >= 3 * 8 * layers and int(_tail(st2)[N.KV_WIDE_EPOCH]) == 0, f"team barrier counter {counter}: the one-XCD engine did not run"
     two = net.kv_cache_begin(xa.repeat(2, 1, 1))  # two sequences: the multi-launch kernels by default (they spread over the chip)
     net.kv_cache_step(two, torch.tensor([50257, 50257], device=DEV))
-    assert net.kv_cache_check(two) is True and int(_tail(two)[0]) == 0 and int(_tail(two)[4]) == 0
+    assert net.kv_cache_check(two) is True and int(_tail(two)[N.KV_TEAM_COUNTER]) == 0 and int(_tail(two)[N.KV_WIDE_EPOCH]) == 0
 
 
 def _window(net, xa, toks, mode, fill=None):

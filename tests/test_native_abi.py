@@ -336,3 +336,29 @@ def test_chip_wide_step_engine_declines_a_vocabulary_its_logits_phase_cannot_hol
                     said_yes += 1
                     assert -(-rows // nwg) <= 64 * 8, (name, rows, nwg)
     assert said_yes > 0
+
+
+def test_kv_cache_control_tail_layout_is_declared_once(native):
+    """csrc/decode_step_core.h declares the layout of the KV cache's control tail (control words, the chip-wide engine's flag replicas, its row
+    packets and the q | k | v packets); olmoasr_amd/_native.py mirrors the part Python reads.  The mirrors equal the header's values, the
+    control words are 0 .. 4 in order, and the three areas end exactly where include/oasr.h says the tail ends."""
+    src = open(os.path.join(ROOT, "olmoasr_amd", "csrc", "decode_step_core.h")).read()
+    src = re.sub(r"//[^\n]*", "", src)
+    words = dict((k, int(v)) for k, v in re.findall(r"\b(KV_[A-Z_]+)\s*=\s*(\d+)\s*,", re.search(r"enum KvCtrl[^{]*\{(.*?)\}", src, re.S).group(1)))
+    assert words == {"KV_TEAM_COUNTER": 0, "KV_ERROR": 1, "KV_TEAM_EPOCH": 2, "KV_XCC_MASK": 3, "KV_WIDE_EPOCH": 4, "KV_CTRL_WORDS": 5}
+    consts = dict(words)
+    for name, expr in re.findall(r"constexpr int (KV_[A-Z_]+)\s*=\s*([^;]+);", src):  # each an integer expression of earlier names
+        assert re.fullmatch(r"[A-Z_0-9 +*()]+", expr), (name, expr)
+        consts[name] = eval(expr, {"__builtins__": {}}, dict(consts))
+    for name in ("KV_TEAM_COUNTER", "KV_ERROR", "KV_TEAM_EPOCH", "KV_XCC_MASK", "KV_WIDE_EPOCH", "KV_CTRL_WORDS", "KV_REPLICAS", "KV_FLAG_STRIDE",
+                 "KV_FLAGS_WORD"):
+        assert getattr(native, name) == consts[name], name
+    tail = int(re.search(r"#define\s+OASR_KV_TAIL_BYTES\s+(\d+)", open(os.path.join(ROOT, "include", "oasr.h")).read()).group(1))
+    assert native.KV_TAIL_BYTES == tail == consts["KV_TAIL_BYTES"]
+    # control words | flag replicas | packets | q k v packets: in this order, without overlap, ending at the tail's last byte
+    flags_end = consts["KV_FLAGS_WORD"] + consts["KV_REPLICAS"] * consts["KV_FLAG_STRIDE"]
+    packets_end = consts["KV_PACKETS_WORD"] + consts["KV_PACKET_VECTORS"] * consts["KV_REPLICAS"] * consts["KV_PACKET_SLOTS"] * consts["KV_PACKET_WORDS"]
+    qkv_end = consts["KV_QKV_PACKETS_WORD"] + consts["KV_REPLICAS"] * consts["KV_QKV_SLOTS"] * consts["KV_PACKET_WORDS"]
+    assert consts["KV_CTRL_WORDS"] <= consts["KV_FLAGS_WORD"] and flags_end <= consts["KV_PACKETS_WORD"]
+    assert packets_end == consts["KV_QKV_PACKETS_WORD"] and 4 * qkv_end == tail
+    assert (4 * consts["KV_PACKETS_WORD"], 4 * (packets_end - consts["KV_PACKETS_WORD"]), 4 * (qkv_end - packets_end)) == (64 << 10, 160 << 10, 96 << 10)
