@@ -541,6 +541,61 @@ int oasr_speed_perturb(const oasr_speed_args*, void* stream);
 int oasr_speed_perturb_host(const oasr_speed_args*);
 int oasr_speed_plan(const oasr_speed* policy, uint64_t seed, uint64_t clip, int n_valid, int N, int* P, int* Q, int* n_out, int* factor);
 int oasr_speed_table(int P, int Q, int32_t* out, int* H);
+/* Noise mixing: additive background noise from a bank of recordings at a drawn signal-to-noise ratio, on int16 PCM AHEAD of oasr_log_mel
+ * and after oasr_speed_perturb (csrc/noise.hip; the rule itself: csrc/noise_core.h).  Entry points only: OASR_ABI_VERSION is unchanged, and
+ * a binding checks oasr_sizeof_noise and oasr_sizeof_noise_args like oasr_sizeof_speed.  The operator is an integer function of its
+ * operands: unsigned and signed 64-bit integers only, no floating point anywhere (the host included) and no 128-bit type.
+ *
+ * Operands: pcm_in / pcm_out int16 [B, N], row strides ld_in / ld_out >= N (samples), rows at any even address; the two either do not
+ * overlap or are the same buffer with the same stride (in place).  n_valid int32 [B]: each row's leading non-padding samples.  bank int16
+ * [M, L], row stride ld_bank >= L, every row fully valid and read cyclically; it must not overlap pcm_out.  1 <= B, M <= 65535,
+ * 1 <= N, L <= 2^26.  Reports, each NULL or [B]: row_out int32, snr_out int32, gain_out int64.
+ * Policy: prob_q16 in [0, 65536] (the chance of a clip to be drawn, in 1 / 65536), snr_lo_db <= snr_hi_db whole dB inside [-10, 50].
+ *
+ * Draws per clip, with mix() and h = mix(mix(seed) ^ clip), clip = first_clip + row, as at oasr_spec_augment (the SAME h; kind 4 keeps the
+ * draws apart from the masks' kinds 1 and 2 and speed perturbation's 3), t = 4 << 16:
+ *     drawn = mix(h ^ t) % 65536 < prob_q16        m = mix(h ^ (t | 1)) % M        o = mix(h ^ (t | 2)) % L
+ *     s = snr_lo_db + mix(h ^ (t | 3)) % (snr_hi_db - snr_lo_db + 1)
+ * Amplitudes: A[s + 10] = round(10^(-s / 20) * 2^15) for s = -10 .. 50, 61 integer constants (A[0] = 103622, A[10] = 32768, A[60] = 104).
+ *
+ * Gain of a drawn clip with 1 <= n_valid <= N:   v[n] = bank[m][(o + n) % L],   Ex = sum x[n]^2,  Ev = sum v[n]^2  over n < n_valid (exact,
+ * <= 2^56);   sh = max(0, bitlength(Ex | Ev) - 31),  ex = Ex >> sh,  ev = Ev >> sh;   ex == 0 or ev == 0: the clip is not mixed; else
+ *     g0 = isqrt((ex << 32) / ev)   (Q16, below 2^31.5)        g = (g0 * A[s + 10] + 2^14) >> 15   (Q16, below 2^34)
+ * Sample:   y[n] = clamp(x[n] + ((v[n] * g + 2^15) >> 16), -32768, 32767) for n < n_valid (arithmetic shift),   y[n] = x[n] for n_valid <= n < N.
+ * A clip that is not mixed -- not drawn, n_valid outside [1, N], ex == 0 or ev == 0 -- is copied bit for bit (in place: left alone) and
+ * reports row_out = -1, snr_out = OASR_NOISE_NONE, gain_out = 0; a mixed clip reports m, s and g.
+ *
+ * oasr_noise_mix: device pointers, TWO launches on `stream` (exact per-tile energies into `workspace`, then gain and mix), never synchronises,
+ * no memset, nothing comes back to the host.  workspace: device memory of at least oasr_noise_workspace_bytes(B, N) bytes, 8-byte aligned,
+ * contents irrelevant.  The plan is evaluated on the device; lengths live there, so the host cannot refuse them.  Everything else that is
+ * wrong is OASR_EINVAL before a launch.
+ * oasr_noise_mix_host: HOST function (no GPU call, host pointers, workspace ignored), the same rule from the same text.
+ * oasr_noise_plan: HOST function: (drawn, m, o, s) of ONE clip (each output may be NULL); it needs no audio. */
+#define OASR_NOISE_NONE (-128)
+typedef struct oasr_noise {
+  int32_t prob_q16, snr_lo_db, snr_hi_db;
+} oasr_noise;
+typedef struct oasr_noise_args {
+  const int16_t* pcm_in;
+  int16_t* pcm_out;
+  const int32_t* n_valid;
+  const int16_t* bank;
+  int32_t *row_out, *snr_out;
+  int64_t* gain_out;
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t ld_in, ld_out, ld_bank;
+  uint64_t seed, first_clip;
+  int32_t B, N, M, L;
+  oasr_noise policy;
+  int32_t reserved;
+} oasr_noise_args;
+size_t oasr_sizeof_noise(void);
+size_t oasr_sizeof_noise_args(void);
+size_t oasr_noise_workspace_bytes(int B, int N);
+int oasr_noise_mix(const oasr_noise_args*, void* stream);
+int oasr_noise_mix_host(const oasr_noise_args*);
+int oasr_noise_plan(const oasr_noise* policy, uint64_t seed, uint64_t clip, int M, int L, int* drawn, int* row, int* offset, int* snr_db);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 /* The same operator with the regularisers of oasr_train_step_args (label_smoothing, z_loss: the formula there; gscale takes the place of

@@ -84,6 +84,20 @@ class SpeedArgs(C.Structure):  # include/oasr.h: oasr_speed_args
                 ("S", C.c_int32), ("ts_begin", C.c_int32), ("ts_max", C.c_int32), ("policy", Speed)]
 
 
+class Noise(C.Structure):  # include/oasr.h: oasr_noise
+    NONE = -128  # OASR_NOISE_NONE
+    SNR_MIN, SNR_MAX = -10, 50
+    _fields_ = [("prob_q16", C.c_int32), ("snr_lo_db", C.c_int32), ("snr_hi_db", C.c_int32)]
+
+
+class NoiseArgs(C.Structure):  # include/oasr.h: oasr_noise_args
+    MAX_N, MAX_ROWS = 1 << 26, 65535
+    _fields_ = [("pcm_in", C.c_void_p), ("pcm_out", C.c_void_p), ("n_valid", C.c_void_p), ("bank", C.c_void_p), ("row_out", C.c_void_p),
+                ("snr_out", C.c_void_p), ("gain_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("ld_in", C.c_int64), ("ld_out", C.c_int64), ("ld_bank", C.c_int64), ("seed", C.c_uint64), ("first_clip", C.c_uint64),
+                ("B", C.c_int32), ("N", C.c_int32), ("M", C.c_int32), ("L", C.c_int32), ("policy", Noise), ("reserved", C.c_int32)]
+
+
 class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
     _fields_ = [(n, C.c_void_p) for n in ("mel", "xa", "tokens", "targets", "text_len", "span_host", "mel_clip_max", "loss_out", "logits_out",
                                           "pred_out", "seg_events")] + \
@@ -102,6 +116,8 @@ STRUCT_SIZES = [
     ("oasr_sizeof_beam_args", BeamArgs),  # came with oasr_beam_update and oasr_decode_reorder
     ("oasr_sizeof_speed", Speed),  # came with oasr_speed_perturb
     ("oasr_sizeof_speed_args", SpeedArgs),
+    ("oasr_sizeof_noise", Noise),  # came with oasr_noise_mix
+    ("oasr_sizeof_noise_args", NoiseArgs),
     ("oasr_sizeof_train_step_args", TrainStepArgs),  # last grown by label_smoothing / z_loss / loss_parts_*
 ]
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
@@ -214,6 +230,12 @@ def _declare(lib):
         "oasr_speed_perturb_host": (i32, [C.POINTER(SpeedArgs)]),
         "oasr_speed_plan": (i32, [C.POINTER(Speed), C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "oasr_speed_table": (i32, [i32, i32, vp, C.POINTER(i32)]),
+        "oasr_sizeof_noise": (sz, []),
+        "oasr_sizeof_noise_args": (sz, []),
+        "oasr_noise_workspace_bytes": (sz, [i32, i32]),
+        "oasr_noise_mix": (i32, [C.POINTER(NoiseArgs), vp]),
+        "oasr_noise_mix_host": (i32, [C.POINTER(NoiseArgs)]),
+        "oasr_noise_plan": (i32, [C.POINTER(Noise), C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "oasr_test_argmax_rows": (i32, [vp, i32, i64, i32, i64, vp, vp, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cross_entropy_ex": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, f32, f32, vp, vp]),

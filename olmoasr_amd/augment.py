@@ -16,7 +16,17 @@ the transcript's timestamp tokens with the audio (``ops.speed_perturb``, csrc/sp
     pcm, n_out, factor = speed.apply(pcm, n_valid, seed, first_clip=stream_id_of_row_0, tokens=(text_input, text_y))
 
 It is an integer function of the samples, drawn from the same hash stream as the masks (kind 3): ``SpeedPerturb.plan`` gives a clip's ratio,
-new length and factor index without a GPU."""
+new length and factor index without a GPU.
+
+Noise mixing adds a recording from a bank at a drawn signal-to-noise ratio, after speed perturbation and ahead of ``ops.log_mel``
+(``ops.noise_mix``, csrc/noise.hip):
+
+    bank = augment.noise_bank(recordings, L=480000).to(device)   # int16 [M, L]; shorter recordings are tiled
+    noise = augment.NoiseMix(prob=0.5, snr_db=(5, 20))
+    pcm, row, snr, gain = noise.apply(pcm, n_out, bank, seed, first_clip=stream_id_of_row_0)
+
+It too is an integer function of the samples (exact energies, an integer Q16 gain, a table of 61 amplitudes), drawn from the same hash
+stream (kind 4): ``NoiseMix.plan`` gives a clip's draw without a GPU and without audio."""
 import math
 from dataclasses import dataclass
 
@@ -101,6 +111,54 @@ class SpeedPerturb:
         for b, nv in enumerate(n_valid):
             counts[self.plan(seed, (first_clip + b) & _U64, int(nv), N)[3]] += 1  # (-1, the fallback, indexes the last entry)
         return counts
+
+
+@dataclass(frozen=True)
+class NoiseMix:
+    prob: float = 0.5        # the chance of a clip to take noise (kept in 1 / 65536)
+    snr_db: tuple = (5, 20)  # (lo, hi): the SNR is drawn among the whole dB lo .. hi, inside [-10, 50]
+
+    def __post_init__(self):
+        from . import ops
+        ops.noise_policy(self.prob, self.snr_db)
+        object.__setattr__(self, "snr_db", tuple(self.snr_db))
+
+    def apply(self, pcm, n_valid, bank, seed, first_clip=0, out=None):
+        """int16 [B, N] on the GPU -> (pcm_out, row, snr, gain); row b takes stream id first_clip + b; ``out=pcm`` mixes in place."""
+        from . import ops
+        return ops.noise_mix(pcm, n_valid, bank, prob=self.prob, snr_db=self.snr_db, seed=seed, first_clip=first_clip, out=out)
+
+    def plan(self, seed, clip, M, L):
+        """(drawn, row, offset, snr_db) of stream id ``clip`` against a bank [M, L], from the library's host function: no GPU needed."""
+        from . import ops
+        return ops.noise_plan(self.prob, self.snr_db, seed, clip, M, L)
+
+    def drawn(self, seed, first_clip, B, M, L):
+        """(how many of the B clips at stream ids first_clip .. are drawn, the sum of their SNRs in dB), from the plan alone.  A drawn clip
+        that is silent, empty, or lands on a silent stretch of noise is copied all the same: that takes the audio to know."""
+        count = total = 0
+        for b in range(B):
+            d, _, _, s = self.plan(seed, (first_clip + b) & _U64, M, L)
+            if d:
+                count, total = count + 1, total + s
+        return count, total
+
+
+def noise_bank(arrays, L):
+    """int16 [M, L] on the CPU from a list of 1-D int16 recordings (tensors or arrays): each is repeated cyclically up to L samples, a longer
+    one is cut, so that every row is fully valid -- what ``ops.noise_mix`` asks of its bank."""
+    import torch
+    if not isinstance(L, int) or isinstance(L, bool) or not 1 <= L <= 1 << 26:
+        raise ValueError(f"noise_bank: L must be an integer in [1, 2^26], got {L!r}")
+    rows = [torch.as_tensor(a) for a in arrays]
+    if not 1 <= len(rows) <= 65535:
+        raise ValueError(f"noise_bank: between 1 and 65535 recordings, got {len(rows)}")
+    bank = torch.empty(len(rows), L, dtype=torch.int16)
+    for i, r in enumerate(rows):
+        if r.dtype != torch.int16 or r.dim() != 1 or r.numel() < 1:
+            raise ValueError(f"noise_bank: recording {i} must be a non-empty 1-D int16 array, got {r.dtype} {tuple(r.shape)}")
+        bank[i] = r.repeat(-(-L // r.numel()))[:L]
+    return bank
 
 
 def plan(policy: SpecAugment, seed: int, clip: int, n_mels: int = 80, T: int = 3000):

@@ -214,6 +214,11 @@ extern "C" size_t oasr_sizeof_speed(void) { return sizeof(oasr_speed); }
 extern "C" size_t oasr_sizeof_speed_args(void) { return sizeof(oasr_speed_args); }
 extern "C" int oasr_speed_perturb(const oasr_speed_args* a, void* stream) { return launch_speed_perturb(a, (hipStream_t)stream); }
 
+extern "C" size_t oasr_sizeof_noise(void) { return sizeof(oasr_noise); }
+extern "C" size_t oasr_sizeof_noise_args(void) { return sizeof(oasr_noise_args); }
+extern "C" size_t oasr_noise_workspace_bytes(int B, int N) { return (B < 1 || N < 1) ? 0 : noise_workspace_bytes(B, N); }
+extern "C" int oasr_noise_mix(const oasr_noise_args* a, void* stream) { return launch_noise_mix(a, (hipStream_t)stream); }
+
 extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                                      int64_t* targets_rows_out, int64_t* active_rows_out, void* stream) {
   OASR_REQUIRE(active_rows_out, "oasr_test_span_tables: null");

@@ -349,6 +349,13 @@ int launch_spec_augment(float* mel, int B, int n_mels, int T, const oasr_specaug
 struct oasr_speed_args;
 int launch_speed_perturb(const oasr_speed_args* a, hipStream_t s);
 
+// ---- noise mixing (noise.hip; the contract: include/oasr.h at oasr_noise_mix, the rule: noise_core.h) -------------------------------------
+// pcm_out = each drawn clip of pcm_in plus its bank row at the drawn offset and SNR (else a copy); two launches (exact per-tile energies into
+// a->workspace, then gain and mix), plan on the device
+struct oasr_noise_args;
+size_t noise_workspace_bytes(int B, int N);
+int launch_noise_mix(const oasr_noise_args* a, hipStream_t s);
+
 // ---- LoRA adapters in weight space (lora.hip) -----------------------------------------------------------------
 // out = W0 + scale * B . A  (W0 [rows][cols] fp32, A [r][cols], B [rows][r]; k sum in ascending order): exactly one of out32 (fp32, may be w0
 // itself) / out16 (bf16, the rounding of launch_cast_f32_bf16)

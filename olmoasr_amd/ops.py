@@ -815,6 +815,118 @@ def speed_table(P, Q):
     return T, H.value
 
 
+def noise_policy(prob, snr_db):
+    """The ``oasr_noise`` block of a policy, refused here (ValueError) for what the library would refuse (OASR_EINVAL): ``prob`` in [0, 1]
+    (kept as round(prob * 65536): the chance of a clip to be drawn), ``snr_db`` = (lo, hi), whole dB with -10 <= lo <= hi <= 50."""
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"noise_mix: prob must be a number in [0, 1], got {prob!r}")
+    try:
+        lo, hi = snr_db
+    except (TypeError, ValueError):
+        raise ValueError(f"noise_mix: snr_db must be a pair (lo, hi) of whole dB, got {snr_db!r}")
+    if any(not isinstance(v, int) or isinstance(v, bool) for v in (lo, hi)):
+        raise ValueError(f"noise_mix: snr_db must be a pair of integers (whole dB), got {snr_db!r}")
+    if not N.Noise.SNR_MIN <= lo <= hi <= N.Noise.SNR_MAX:
+        raise ValueError(f"noise_mix: snr_db needs {N.Noise.SNR_MIN} <= lo <= hi <= {N.Noise.SNR_MAX}, got {snr_db!r}")
+    return N.Noise(int(round(prob * 65536)), lo, hi)
+
+
+def _noise_args(pcm, n_valid, bank, prob, snr_db, seed, first_clip, out, cuda):
+    """Checks and converts the operands of ``noise_mix`` / ``noise_mix_host``: (NoiseArgs, pcm_out, row, snr, gain, keep-alive)."""
+    what = "noise_mix" if cuda else "noise_mix_host"
+
+    def rows(t, nm, shape=None):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int16 and t.dim() == 2):
+            raise ValueError(f"{what}: {nm} must be a 2-D torch.int16 tensor")
+        if t.is_cuda != cuda or t.device != pcm.device:
+            raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor on the device of pcm")
+        if shape is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {nm} must be {list(shape)}, got {tuple(t.shape)}")
+        if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"{what}: {nm} needs unit column stride and rows that do not overlap")
+        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+    if not isinstance(pcm, torch.Tensor):
+        raise ValueError(f"{what}: pcm must be a 2-D torch.int16 tensor")
+    ld_in = rows(pcm, "pcm")
+    ld_bank = rows(bank, "bank")
+    B, n = pcm.shape
+    M, L = bank.shape
+    if not (isinstance(n_valid, torch.Tensor) and n_valid.dtype == torch.int32 and n_valid.dim() == 1 and n_valid.numel() == B
+            and n_valid.is_contiguous() and n_valid.device == pcm.device):
+        raise ValueError(f"{what}: n_valid must be a contiguous int32 [{B}] on the device of pcm")
+    if not 1 <= n <= N.NoiseArgs.MAX_N or B > N.NoiseArgs.MAX_ROWS:
+        raise ValueError(f"{what}: pcm [B, N] with B <= 65535 and 1 <= N <= 2^26, got {tuple(pcm.shape)}")
+    if not (1 <= L <= N.NoiseArgs.MAX_N and 1 <= M <= N.NoiseArgs.MAX_ROWS):
+        raise ValueError(f"{what}: bank [M, L] with 1 <= M <= 65535 and 1 <= L <= 2^26, got {tuple(bank.shape)}")
+    a = N.NoiseArgs()
+    a.policy = noise_policy(prob, snr_db)
+    a.seed, a.first_clip = _u64("seed", seed, what), _u64("first_clip", first_clip, what)
+    if out is None:
+        out = torch.empty(B, n, dtype=torch.int16, device=pcm.device)
+    ld_out = rows(out, "out", (B, n))
+    if B:
+        def span(t, ld, r, c):
+            return t.data_ptr(), t.data_ptr() + 2 * ((r - 1) * ld + c)
+        (lo_i, hi_i), (lo_o, hi_o), (lo_b, hi_b) = span(pcm, ld_in, B, n), span(out, ld_out, B, n), span(bank, ld_bank, M, L)
+        if lo_i < hi_o and lo_o < hi_i and not (lo_i == lo_o and ld_in == ld_out):
+            raise ValueError(f"{what}: out overlaps pcm without being pcm itself (in place: the same tensor)")
+        if lo_b < hi_o and lo_o < hi_b:
+            raise ValueError(f"{what}: out overlaps the bank")
+    row = torch.empty(B, dtype=torch.int32, device=pcm.device)
+    snr = torch.empty(B, dtype=torch.int32, device=pcm.device)
+    gain = torch.empty(B, dtype=torch.int64, device=pcm.device)
+    a.pcm_in, a.pcm_out, a.n_valid, a.bank = pcm.data_ptr(), out.data_ptr(), n_valid.data_ptr(), bank.data_ptr()
+    a.row_out, a.snr_out, a.gain_out = row.data_ptr(), snr.data_ptr(), gain.data_ptr()
+    a.ld_in, a.ld_out, a.ld_bank, a.B, a.N, a.M, a.L = ld_in, ld_out, ld_bank, B, n, M, L
+    return a, out, row, snr, gain, (pcm, n_valid, bank)
+
+
+def noise_mix(pcm, n_valid, bank, *, prob, snr_db, seed=0, first_clip=0, out=None):
+    """Additive noise at a drawn SNR on int16 PCM on the GPU (include/oasr.h: oasr_noise_mix; the rule: csrc/noise_core.h): ``pcm`` int16
+    [B, N] (unit column stride, any row stride >= N), ``n_valid`` int32 [B] = each row's leading non-padding samples, ``bank`` int16 [M, L]
+    of noise recordings, every row fully valid (``augment.noise_bank`` tiles shorter ones).  Row ``b`` draws -- from stream id
+    ``first_clip + b`` (mod 2^64) under ``seed``, the hash stream of ``spec_augment_``, kind 4 -- whether it takes noise (``prob``), a bank
+    row, an offset into it (the row is read cyclically) and an SNR among the whole dB of ``snr_db`` = (lo, hi); the noise is scaled by an
+    integer Q16 gain from the two exact energies over the row's first ``n_valid`` samples and added with saturation.  A row that is not
+    drawn, has ``n_valid`` outside [1, N], or is silent (as is a silent stretch of noise) is copied.  Returns ``(pcm_out, row, snr, gain)``:
+    int16 [B, N] (``out``, if given: int16 [B, N] that is ``pcm`` itself -- in place -- or does not overlap it), int32 [B] bank rows (-1: not
+    mixed), int32 [B] SNRs (-128: not mixed), int64 [B] gains (0: not mixed).  Two launches on the current stream, no host read; wrong
+    dtypes, shapes or devices raise ValueError before anything is launched."""
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda):
+        raise ValueError("noise_mix: pcm must be a GPU tensor (noise_mix_host takes CPU tensors)")
+    a, out, row, snr, gain, keep = _noise_args(pcm, n_valid, bank, prob, snr_db, seed, first_clip, out, True)
+    if a.B:
+        need = N.lib().oasr_noise_workspace_bytes(a.B, a.N)
+        ws = _workspace("noise_mix", pcm.device, need)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        N.call("oasr_noise_mix", C.byref(a), N.STREAM, device=pcm.device)
+    return out, row, snr, gain
+
+
+def noise_mix_host(pcm, n_valid, bank, *, prob, snr_db, seed=0, first_clip=0, out=None):
+    """``noise_mix`` on CPU tensors through the library's host twin (oasr_noise_mix_host: the same rule from the same text, no GPU)."""
+    if not (isinstance(pcm, torch.Tensor) and not pcm.is_cuda):
+        raise ValueError("noise_mix_host: pcm must be a CPU tensor")
+    a, out, row, snr, gain, keep = _noise_args(pcm, n_valid, bank, prob, snr_db, seed, first_clip, out, False)
+    if a.B:
+        N.call("oasr_noise_mix_host", C.byref(a))
+    return out, row, snr, gain
+
+
+def noise_plan(prob, snr_db, seed, clip, M, L):
+    """What ``noise_mix`` draws for stream id ``clip`` against a bank of ``M`` rows of ``L`` samples, from the library's host function
+    (oasr_noise_plan; no GPU, no audio): ``(drawn, row, offset, snr_db)``."""
+    pol = noise_policy(prob, snr_db)
+    for nm, v, hi in (("M", M, N.NoiseArgs.MAX_ROWS), ("L", L, N.NoiseArgs.MAX_N)):
+        if not isinstance(v, int) or isinstance(v, bool) or not 1 <= v <= hi:
+            raise ValueError(f"noise_plan: {nm} must be an integer in [1, {hi}], got {v!r}")
+    d, m, o, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    N.call("oasr_noise_plan", C.byref(pol), _u64("seed", seed, "noise_plan"), _u64("clip", clip, "noise_plan"), M, L, C.byref(d), C.byref(m),
+           C.byref(o), C.byref(s))
+    return bool(d.value), m.value, o.value, s.value
+
+
 def pick_tokens(logits, mask=None, mask2=None, want_logprob=True):
     """logits fp32 [rows, V] (row stride free) -> (argmax ids int64 [rows], log_softmax at the argmax fp32 [rows] | None);
     ``mask`` / ``mask2``: additive fp32 [V] (0 / -inf)."""

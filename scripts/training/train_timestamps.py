@@ -80,7 +80,12 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     # Speed perturbation of the int16 clips of every TRAINING micro-batch, ahead of the log-mel (olmoasr_amd/augment.py, csrc/speed.hip): off |
     # 3way (each clip 0.9, 1.0 or 1.1 times its speed; the transcript's timestamp tokens move along).  --speed_factors replaces the preset's list
     # of (P, Q) pairs, P / Q times faster.  Drawn from --seed and the step counter (spec_offset), like the SpecAugment masks.
-    speed_perturb="off", speed_factors=None)
+    speed_perturb="off", speed_factors=None,
+    # Noise mixing on the int16 clips of every TRAINING micro-batch, after speed perturbation and ahead of the log-mel (olmoasr_amd/augment.py,
+    # csrc/noise.hip): --noise_bank PATH.npy (int16 [M, L], or an object array of 1-D int16 recordings, tiled to the longest) turns it on;
+    # --noise_prob (default 0.5) is a clip's chance to take noise, --noise_snr_db LO,HI (default 5,20) the whole dB the SNR is drawn among.
+    # Drawn from --seed and the step counter (spec_offset), like the masks and the speed factors.
+    noise_bank=None, noise_prob=None, noise_snr_db=None)
 ERROR_COUNTS = ("host", "device")
 SPEC_OVERRIDES = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_time_ratio", "spec_fill")
 SPEC_PRESETS = ("off", "LD", "LB")
@@ -145,6 +150,49 @@ def speed_policy(args):
         raise SystemExit(f"--speed_perturb={args.speed_perturb}: {e}")
 
 
+def noise_policy(args):
+    """--noise_bank, --noise_prob and --noise_snr_db -> augment.NoiseMix, or None without a bank (the bank itself is loaded by load_noise_bank)."""
+    if args.noise_bank is None:
+        for f in ("noise_prob", "noise_snr_db"):
+            if args[f] is not None:
+                raise SystemExit(f"--{f} given without --noise_bank: name a bank of noise recordings (PATH.npy) to mix from")
+        return None
+    if not isinstance(args.noise_bank, str) or not os.path.isfile(args.noise_bank):
+        raise SystemExit(f"--noise_bank must name an existing .npy file, got {args.noise_bank!r}")
+    over = {}
+    if args.noise_prob is not None:
+        over["prob"] = args.noise_prob
+    if args.noise_snr_db is not None:
+        snr = args.noise_snr_db
+        if not (isinstance(snr, (tuple, list)) and len(snr) == 2):
+            raise SystemExit(f"--noise_snr_db must be LO,HI in whole dB such as '5,20', got {snr!r}")
+        over["snr_db"] = tuple(snr)
+    from olmoasr_amd import augment
+    try:
+        return augment.NoiseMix(**over)
+    except ValueError as e:
+        raise SystemExit(f"--noise_prob / --noise_snr_db: {e}")
+
+
+def load_noise_bank(path):
+    """The bank of --noise_bank as int16 [M, L] on the CPU: a 2-D int16 array as it is, an object array (or list) of 1-D int16 recordings
+    tiled cyclically to the longest of them."""
+    import numpy as np
+    from olmoasr_amd import augment
+    try:
+        arr = np.load(path, allow_pickle=True)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--noise_bank {path}: {e}")
+    try:
+        if arr.dtype == np.int16 and arr.ndim == 2:
+            return augment.noise_bank(list(arr), int(arr.shape[1]))
+        if arr.dtype == object and arr.ndim == 1 and len(arr) and all(isinstance(r, np.ndarray) for r in arr):
+            return augment.noise_bank(list(arr), min(1 << 26, max(int(r.size) for r in arr)))
+    except ValueError as e:
+        raise SystemExit(f"--noise_bank {path}: {e}")
+    raise SystemExit(f"--noise_bank {path}: expected int16 [M, L] or an object array of 1-D int16 recordings, got {arr.dtype} {arr.shape}")
+
+
 def spec_offset(global_step, micro, accum, world_size, rank, train_batch_size):
     """Stream id of row 0 of micro-batch ``micro`` of the step that follows ``global_step`` completed ones, on ``rank``; row b is + b.  A
     function of the step counter, not of process lifetime: a resumed run draws the masks the uninterrupted run would have drawn, and the
@@ -201,6 +249,7 @@ def parse_args(argv=None):
     args.lora_targets = tuple(args.lora_targets)
     args.spec_policy = spec_policy(args)
     args.speed_policy = speed_policy(args)
+    args.noise_policy = noise_policy(args)
     if args.train_error_counts not in ERROR_COUNTS:
         raise SystemExit(f"--train_error_counts must be one of {' | '.join(ERROR_COUNTS)}, got {args.train_error_counts!r}")
     if args.train_error_counts == "device" and not args.span_backward:
@@ -533,6 +582,12 @@ def main(argv=None):
     if speed is not None and rank == 0:
         print(json.dumps({"event": "speed_perturb", "policy": args.speed_perturb, "factors": [list(pq) for pq in speed.factors],
                           "seed": spec_seed}), flush=True)
+    noise = args.noise_policy
+    if noise is not None:
+        noise_bank = load_noise_bank(args.noise_bank).to(dev)
+        if rank == 0:
+            print(json.dumps({"event": "noise_mix", "bank": list(noise_bank.shape), "prob": noise.prob, "snr_db": list(noise.snr_db),
+                              "seed": spec_seed}), flush=True)
     if regularised and rank == 0:
         print(json.dumps({"event": "loss_regularisers", "label_smoothing": args.label_smoothing, "z_loss": args.z_loss}), flush=True)
     device_counts = args.train_error_counts == "device"
@@ -547,6 +602,7 @@ def main(argv=None):
         preds, tgts = [], []
         spec_cells = 0  # cells masked on this rank in this step: from the host plan, no device read-back
         speed_counts = [0] * (len(speed.factors) + 1) if speed is not None else None  # this rank's clips per factor (last entry: fell back to the copy): from the host plan too
+        noise_drawn = noise_snr_sum = 0  # this rank's clips that drew noise in this step and the sum of their SNRs: from the host plan too
         for i in range(accum):
             pcm, ti, ty, tl = next(loader)
             cursor += args.train_batch_size  # (position in this rank's epoch order; a short last batch also ends the epoch)
@@ -560,8 +616,16 @@ def main(argv=None):
             if speed is not None:  # a new pcm tensor; the timestamp ids of ti / ty move in place (the token count, hence the span, stays)
                 first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
                 n_samples = int(pcm.shape[1])
-                pcm, _, _ = speed.apply(pcm, loader.last_n_valid, spec_seed, first, tokens=(ti, ty))
+                pcm, n_speed, _ = speed.apply(pcm, loader.last_n_valid, spec_seed, first, tokens=(ti, ty))
                 speed_counts = [c + d for c, d in zip(speed_counts, speed.factor_counts(spec_seed, first, loader.last_n_valid_host.tolist(), n_samples))]
+            if noise is not None:  # on the clip as the log-mel will see it: its length is what speed perturbation left (in place on that new tensor)
+                first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
+                if speed is not None:
+                    noise.apply(pcm, n_speed, noise_bank, spec_seed, first, out=pcm)
+                else:
+                    pcm = noise.apply(pcm, loader.last_n_valid, noise_bank, spec_seed, first)[0]
+                d_, s_ = noise.drawn(spec_seed, first, int(pcm.shape[0]), *noise_bank.shape)
+                noise_drawn, noise_snr_sum = noise_drawn + d_, noise_snr_sum + s_
             if policy is not None:  # masks go on the FINALIZED log-mel, so the span step takes it finalized as well (mel_clip_max=None)
                 mel, clip_max = ops.log_mel(pcm), None
                 first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
@@ -621,6 +685,8 @@ def main(argv=None):
                        "spec_masked_cells": spec_cells}
                 if speed is not None:
                     rec["speed_factor_counts"] = speed_counts
+                if noise is not None:
+                    rec.update(noise_drawn=noise_drawn, noise_snr_db_mean=round(noise_snr_sum / noise_drawn, 3) if noise_drawn else None)
                 if regularised:
                     rec.update(train_nll=parts[0] / world_size, train_lse_sq=parts[1] / world_size)
                 if preds:
