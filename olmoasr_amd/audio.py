@@ -1,6 +1,6 @@
 """Host-side mirror of ``whisper.audio`` as re-exported by the reference (olmoasr/__init__.py:21) and used at
 scripts/training/train_timestamps.py:207-214 and olmoasr/transcribe.py:11-19,148: same names, arguments and constants.
-``log_mel_spectrogram`` runs the HIP kernel (csrc/logmel.hip); there is no CPU implementation in the product."""
+``log_mel_spectrogram`` runs the HIP kernel (csrc/logmel.hip, csrc/logmel_quad.hip); there is no CPU implementation in the product."""
 from typing import Optional, Union
 
 import numpy as np

@@ -1,6 +1,6 @@
-// Quad-lane, register-resident log-mel kernel (included by logmel.hip after its cf / dft5 helpers).
+// logmel_quad: the quad-lane, register-resident log-mel kernel (round 6), the default of oasr_log_mel / oasr_log_mel_raw (logmel.hip).
 //
-// The LDS FFT kernel above (logmel_fft) keeps a frame's 200 complex points in LDS and walks them in three barrier-separated stages; with
+// The LDS FFT kernel (logmel_fft.hip) keeps a frame's 200 complex points in LDS and walks them in three barrier-separated stages; with
 // 1.6 KB of LDS per frame only 12 waves fit a CU and every stage runs at LDS round-trip latency (profiles/r03_logmel_fft.txt).  Here a frame
 // lives in the REGISTERS of four adjacent lanes (a DPP quad), 50 complex points each, and never touches LDS between its samples and its 80
 // log-mel values:
@@ -16,15 +16,15 @@
 //               m = l mod 4, takes log10 and stores
 // 64 frames per 256-thread workgroup; LDS holds only the workgroup's samples (as fp32, converted once while staging) and 7.4 KB of per-lane
 // tables: 49 KB, three workgroups per CU, no barrier after the staging one.  fp32 throughout, twiddles rounded once from double.
-#pragma once
+// The per-lane tables (QTAB_*, QLOG_SHIFT) and the filters' compile-time slot structure (QMEL_*, QW*) come with logmel_tables.h.
 #include <type_traits>
 
-#include "logmel_quad_tables.h"
+#include "logmel_common.h"
+
+namespace {
 
 constexpr int QT = 64;                              // frames per workgroup
-constexpr int QLOG_SHIFT = 16;                      // the mel weights carry 2^16: see the logarithm at the end of the mel phase
 constexpr int QNS = QT * HOP + (NFFT - HOP);        // samples of 64 frames: 10480
-constexpr int QTAB_WIN = 0, QTAB_TW200 = 400, QTAB_TW400 = 800, QTAB_MEL = 1200, QTAB = 1200 + 4 * QMEL_SLOTS;  // floats
 
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -168,10 +168,7 @@ __global__ __launch_bounds__(256, QUAD_WAVES) void logmel_quad(const PCM* __rest
     }
   } else {
     for (int s = tid; s < QNS; s += 256) {
-      long idx = s_begin + s;
-      if (idx < 0) idx = -idx;
-      if (idx >= n_samples) idx = 2L * (n_samples - 1) - idx;
-      idx = idx < 0 ? 0 : (idx >= n_samples ? n_samples - 1 : idx);
+      const long idx = reflect_index(s_begin + s, n_samples);
       if constexpr (S16) ((PCM*)samp)[s] = clip[idx];
       else samp[s] = load_pcm<PCM>(clip, idx);
     }
@@ -354,3 +351,19 @@ __global__ __launch_bounds__(256, QUAD_WAVES) void logmel_quad(const PCM* __rest
     if (m4 > -1e29f) atomicMax(clipmax + b, f2ord(m4));
   }
 }
+
+template <typename PCM>
+int launch_quad(const LogmelArgs& a) {
+  const size_t lds = quad_lds_bytes<PCM>();
+  const dim3 grid((unsigned)(cdiv(a.n_frames, QT) * a.B));
+  static LdsAttrOnce attr;
+  const int rc = ensure_dynamic_lds(attr, (const void*)logmel_quad<PCM>, (int)lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(logmel_quad<PCM>, grid, dim3(256), lds, a.stream, (const PCM*)a.pcm, a.n_samples, a.n_frames, a.tab->quad_tab, a.out, a.clipmax);
+  OASR_LAUNCH_CHECK();
+  return OASR_OK;
+}
+
+}  // namespace
+
+int launch_logmel_quad(const LogmelArgs& a) { return a.pcm_dtype == 1 ? launch_quad<int16_t>(a) : launch_quad<float>(a); }

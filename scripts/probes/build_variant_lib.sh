@@ -2,6 +2,7 @@
 # usage: build_variant_lib.sh <src.hip> <tag> [extra -D flags]   -> scratch/abl/liboasr_<tag>.so
 # <src.hip> (absolute, or relative to olmoasr_amd/csrc): a variant of one source of olmoasr_amd/csrc under that source's file name, e.g. a
 # patched attention_fwd.hip; its object replaces the product object of the same name, every other object is the product's.
+# Flags the Makefile gives that one object go with the extra flags: build_variant_lib.sh logmel_quad.hip waves4 -fno-slp-vectorize -DQUAD_WAVES=4
 set -e
 SRC=$1; TAG=$2; shift 2
 OBJ=$(basename ${SRC%.*}).o

@@ -1,6 +1,6 @@
 """Cases, float64 reference, error rule and deliberately flawed stand-ins for the log-mel front end (numpy / torch on the CPU, no GPU needed).
 
-``ops.log_mel`` (csrc/logmel.hip, csrc/logmel_quad.h) goes wrong in a FEW CELLS: one (lane, register) slot of the quad-lane FFT, one unpack
+``ops.log_mel`` (csrc/logmel.hip and its kernel files csrc/logmel_quad.hip, logmel_fft.hip, logmel_dft.hip) goes wrong in a FEW CELLS: one (lane, register) slot of the quad-lane FFT, one unpack
 partner, one filter's slot weight, one window tap, one staged sample at a block seam, a clip maximum that saw the frame whisper drops.  A
 flat tolerance on the finalised value (2e-3 where the kernel's error is 1.6e-6) cannot see any of that.  This module gives the front end
 

@@ -2,7 +2,7 @@
 shows that the same checkers reject a scaled bin, swapped partner bins, a dropped sample slot, a shifted window tap, a filter weight off in
 the fourth digit, the wrong padding and three ways of getting the per-clip floor wrong).
 
-The default kernel (the quad-lane register FFT, csrc/logmel_quad.h) runs every case in this process: the rule on the un-finalised values,
+The default kernel (the quad-lane register FFT, csrc/logmel_quad.hip) runs every case in this process: the rule on the un-finalised values,
 clip_max and the finalised tensor bit for bit against their definitions, guard bands around outputs and inputs (NaN / full-scale
 sentinels), int16 against the same samples as f32, the same clip alone / inside a batch / at an unaligned address (the scalar and the
 vector staging path feed identical arithmetic), run-to-run equality.  The three A/B kernels (OASR_LOGMEL=mfma|fft|fft32; the switch is
@@ -14,7 +14,7 @@ Measured on an MI355X (printed by the tests) at gamma = 4.2: worst |err| / bound
   OASR_LOGMEL=mfma        tone_sweep 0.552 (2.24)                               staging 0.531 (1.15)   floor 0.911 (2.71)
   OASR_LOGMEL=fft, fft32  tone_sweep 0.240 (0.99)                               staging 0.520 (0.98)   floor 0.911 (2.71)
   quiet int16 clips (a few counts) between full-scale samples, default kernel: 0.425
-Two properties of the quad kernel that these tests pin (csrc/logmel_quad.h, end of the mel phase):
+Two properties of the quad kernel that these tests pin (csrc/logmel_quad.hip, end of the mel phase):
   * whisper's clamp at 1e-10 is applied to the logarithm, so a silent cell is exactly -10 and finalises to exactly -1.5 (the product
     fl(log2(1e-10f)) * fl(log10 2) is -10.00000095, one ulp below);
   * the mel weights carry 2^16 and the conversion to log10 is one fma that takes it out again, so one ulp of the hardware log2 is 1.9e-6
