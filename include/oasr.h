@@ -596,6 +596,59 @@ size_t oasr_noise_workspace_bytes(int B, int N);
 int oasr_noise_mix(const oasr_noise_args*, void* stream);
 int oasr_noise_mix_host(const oasr_noise_args*);
 int oasr_noise_plan(const oasr_noise* policy, uint64_t seed, uint64_t clip, int M, int L, int* drawn, int* row, int* offset, int* snr_db);
+/* Reverberation: each drawn clip convolved with a room impulse response from a bank, on int16 PCM AHEAD of oasr_log_mel, after
+ * oasr_speed_perturb and before oasr_noise_mix (csrc/reverb.hip; the rule itself: csrc/reverb_core.h).  Entry points only: OASR_ABI_VERSION
+ * is unchanged, and a binding checks oasr_sizeof_reverb and oasr_sizeof_reverb_args like oasr_sizeof_noise.  The operator is an integer
+ * function of its operands: floating point enters only where the HOST builds the bank (Python: augment.rir_bank), once.
+ *
+ * Operands: pcm_in / pcm_out int16 [B, N], row strides ld_in / ld_out >= N (samples), rows at any even address; the two must not overlap (an
+ * output sample reads up to K input samples around it: in place is not offered).  n_valid int32 [B]: each row's leading non-padding samples.
+ * rir int16 [R, K]: Q15 taps, row stride ld_rir >= K; delay int32 [R]: the index of each row's direct-path tap; rir must not overlap
+ * pcm_out.  1 <= B, R <= 65535, 1 <= N <= 2^26, 1 <= K <= 8192.  Report: row_out int32 [B], or NULL.
+ * Policy: prob_q16 in [0, 65536] (the chance of a clip to be drawn, in 1 / 65536).
+ *
+ * Draws per clip, with mix() and h = mix(mix(seed) ^ clip), clip = first_clip + row, as at oasr_spec_augment (the SAME h; kind 5 keeps the
+ * draws apart from the masks' kinds 1 and 2, speed perturbation's 3 and noise mixing's 4), t = 5 << 16:
+ *     drawn = mix(h ^ t) % 65536 < prob_q16        r = mix(h ^ (t | 1)) % R
+ * Sample of a drawn clip with 1 <= n_valid <= N:
+ *     tap(k) = clamp(rir[r][k], -32639, 32639)     d = clamp(delay[r], 0, K - 1)     x(i) = pcm_in[row][i] for 0 <= i < n_valid, else 0
+ *     S[n]   = sum_{k = 0}^{K - 1} tap(k) * x(n + d - k)                             (exact; |S| < 2^44)
+ *     y[n]   = clamp((S[n] + 2^14) >> 15, -32768, 32767) for n < n_valid (arithmetic shift),     y[n] = pcm_in[row][n] for n_valid <= n < N
+ * The output is shifted back by the direct-path delay and cut at n_valid, so lengths and timestamp tokens do not change.  Both clamps make
+ * the rule total over whatever the bank's memory holds (the host cannot inspect it); 32639 = 127 * 256 + 127 is the largest magnitude whose
+ * two byte digits both fit a signed byte, which is how the device computes S on the matrix cores.
+ * A clip that is not drawn, or whose n_valid is outside [1, N], is copied bit for bit and reports row_out = -1; a reverberated clip reports r.
+ *
+ * oasr_reverb: device pointers, TWO launches on `stream` (the bank's rows expanded into `workspace` as matrix-core operands, then the
+ * convolution), never synchronises, no memset, nothing comes back to the host.  workspace: device memory of at least
+ * oasr_reverb_workspace_bytes(R, K) bytes, 16-byte aligned, contents irrelevant.  The plan is evaluated on the device; lengths, taps and
+ * delays live there, so the host cannot refuse them.  Everything else that is wrong is OASR_EINVAL before a launch.
+ * oasr_reverb_host: HOST function (no GPU call, host pointers, workspace ignored), the same rule from the same text.
+ * oasr_reverb_plan: HOST function: (drawn, r) of ONE clip (each output may be NULL); it needs no audio. */
+struct oasr_reverb { /* the policy; no typedef: in C and C++ alike the plain name oasr_reverb is the entry point below, the policy is `struct oasr_reverb` */
+  int32_t prob_q16;
+};
+typedef struct oasr_reverb_args {
+  const int16_t* pcm_in;
+  int16_t* pcm_out;
+  const int32_t* n_valid;
+  const int16_t* rir;
+  const int32_t* delay;
+  int32_t* row_out;
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t ld_in, ld_out, ld_rir;
+  uint64_t seed, first_clip;
+  int32_t B, N, R, K;
+  struct oasr_reverb policy;
+  int32_t reserved;
+} oasr_reverb_args;
+size_t oasr_sizeof_reverb(void);
+size_t oasr_sizeof_reverb_args(void);
+size_t oasr_reverb_workspace_bytes(int R, int K);
+int oasr_reverb(const oasr_reverb_args*, void* stream);
+int oasr_reverb_host(const oasr_reverb_args*);
+int oasr_reverb_plan(const struct oasr_reverb* policy, uint64_t seed, uint64_t clip, int R, int* drawn, int* row);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 /* The same operator with the regularisers of oasr_train_step_args (label_smoothing, z_loss: the formula there; gscale takes the place of

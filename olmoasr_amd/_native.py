@@ -98,6 +98,18 @@ class NoiseArgs(C.Structure):  # include/oasr.h: oasr_noise_args
                 ("B", C.c_int32), ("N", C.c_int32), ("M", C.c_int32), ("L", C.c_int32), ("policy", Noise), ("reserved", C.c_int32)]
 
 
+class Reverb(C.Structure):  # include/oasr.h: struct oasr_reverb
+    _fields_ = [("prob_q16", C.c_int32)]
+
+
+class ReverbArgs(C.Structure):  # include/oasr.h: oasr_reverb_args
+    MAX_N, MAX_ROWS, MAX_K, TAP_MAX = 1 << 26, 65535, 8192, 32639
+    _fields_ = [("pcm_in", C.c_void_p), ("pcm_out", C.c_void_p), ("n_valid", C.c_void_p), ("rir", C.c_void_p), ("delay", C.c_void_p),
+                ("row_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("ld_in", C.c_int64), ("ld_out", C.c_int64),
+                ("ld_rir", C.c_int64), ("seed", C.c_uint64), ("first_clip", C.c_uint64), ("B", C.c_int32), ("N", C.c_int32), ("R", C.c_int32),
+                ("K", C.c_int32), ("policy", Reverb), ("reserved", C.c_int32)]
+
+
 class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
     _fields_ = [(n, C.c_void_p) for n in ("mel", "xa", "tokens", "targets", "text_len", "span_host", "mel_clip_max", "loss_out", "logits_out",
                                           "pred_out", "seg_events")] + \
@@ -118,6 +130,8 @@ STRUCT_SIZES = [
     ("oasr_sizeof_speed_args", SpeedArgs),
     ("oasr_sizeof_noise", Noise),  # came with oasr_noise_mix
     ("oasr_sizeof_noise_args", NoiseArgs),
+    ("oasr_sizeof_reverb", Reverb),  # came with oasr_reverb
+    ("oasr_sizeof_reverb_args", ReverbArgs),
     ("oasr_sizeof_train_step_args", TrainStepArgs),  # last grown by label_smoothing / z_loss / loss_parts_*
 ]
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
@@ -236,6 +250,12 @@ def _declare(lib):
         "oasr_noise_mix": (i32, [C.POINTER(NoiseArgs), vp]),
         "oasr_noise_mix_host": (i32, [C.POINTER(NoiseArgs)]),
         "oasr_noise_plan": (i32, [C.POINTER(Noise), C.c_uint64, C.c_uint64, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "oasr_sizeof_reverb": (sz, []),
+        "oasr_sizeof_reverb_args": (sz, []),
+        "oasr_reverb_workspace_bytes": (sz, [i32, i32]),
+        "oasr_reverb": (i32, [C.POINTER(ReverbArgs), vp]),
+        "oasr_reverb_host": (i32, [C.POINTER(ReverbArgs)]),
+        "oasr_reverb_plan": (i32, [C.POINTER(Reverb), C.c_uint64, C.c_uint64, i32, C.POINTER(i32), C.POINTER(i32)]),
         "oasr_test_argmax_rows": (i32, [vp, i32, i64, i32, i64, vp, vp, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cross_entropy_ex": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, f32, f32, vp, vp]),

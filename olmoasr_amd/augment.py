@@ -26,7 +26,18 @@ Noise mixing adds a recording from a bank at a drawn signal-to-noise ratio, afte
     pcm, row, snr, gain = noise.apply(pcm, n_out, bank, seed, first_clip=stream_id_of_row_0)
 
 It too is an integer function of the samples (exact energies, an integer Q16 gain, a table of 61 amplitudes), drawn from the same hash
-stream (kind 4): ``NoiseMix.plan`` gives a clip's draw without a GPU and without audio."""
+stream (kind 4): ``NoiseMix.plan`` gives a clip's draw without a GPU and without audio.
+
+Reverberation convolves a clip with a room impulse response from a bank, between the two (the far-field recipe: speed, reverb, additive noise;
+``ops.reverb``, csrc/reverb.hip):
+
+    bank, delay = augment.rir_bank(responses)                     # float responses -> int16 [R, K] Q15 unit-energy taps, int32 [R]
+    reverb = augment.Reverb(prob=0.5)
+    pcm, row = reverb.apply(pcm, n_out, bank.to(device), delay.to(device), seed, first_clip=stream_id_of_row_0)
+
+The bank is the only place floating point enters, on the host, once; the convolution is an exact integer sum (on the int8 matrix cores),
+shifted back by the direct-path delay and cut at the clip's length, so lengths and timestamps stay.  It draws from the same hash stream
+(kind 5): ``Reverb.plan`` gives a clip's draw without a GPU and without audio."""
 import math
 from dataclasses import dataclass
 
@@ -142,6 +153,65 @@ class NoiseMix:
             if d:
                 count, total = count + 1, total + s
         return count, total
+
+
+@dataclass(frozen=True)
+class Reverb:
+    prob: float = 0.5  # the chance of a clip to be reverberated (kept in 1 / 65536)
+
+    def __post_init__(self):
+        from . import ops
+        ops.reverb_policy(self.prob)
+
+    def apply(self, pcm, n_valid, bank, delay, seed, first_clip=0, out=None):
+        """int16 [B, N] on the GPU -> (pcm_out, row), out of place; row b takes stream id first_clip + b; ``bank`` int16 [R, K] and ``delay``
+        int32 [R] as ``rir_bank`` builds them, on the device of ``pcm``."""
+        from . import ops
+        return ops.reverb(pcm, n_valid, bank, delay, prob=self.prob, seed=seed, first_clip=first_clip, out=out)
+
+    def plan(self, seed, clip, R):
+        """(drawn, row) of stream id ``clip`` against a bank of R responses, from the library's host function: no GPU needed."""
+        from . import ops
+        return ops.reverb_plan(self.prob, seed, clip, R)
+
+    def drawn(self, seed, first_clip, B, R):
+        """How many of the B clips at stream ids first_clip .. are drawn, from the plan alone.  A drawn clip whose length is outside [1, N] is
+        copied all the same: that takes the lengths to know."""
+        return sum(self.plan(seed, (first_clip + b) & _U64, R)[0] for b in range(B))
+
+
+def rir_bank(arrays, K=None):
+    """(int16 [R, K] Q15 taps, int32 [R] direct-path delays) on the CPU from a list of 1-D float impulse responses at the clips' sample rate
+    (tensors or arrays) -- what ``ops.reverb`` asks of its bank.  Per response: ``delay`` is the index of the largest ``|h|`` (the first of
+    equal ones) and must lie below K; the taps are cut or zero-padded to K and scaled in double precision to unit energy,
+    ``round(h / sqrt(sum h^2) * 2^15)``, clamped to +-32639.  K defaults to min(8192, the longest response)."""
+    import numpy as np
+    import torch
+    rows = [np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a) for a in arrays]
+    if not 1 <= len(rows) <= 65535:
+        raise ValueError(f"rir_bank: between 1 and 65535 responses, got {len(rows)}")
+    for i, h in enumerate(rows):
+        if h.ndim != 1 or h.size < 1 or h.dtype.kind != "f":
+            raise ValueError(f"rir_bank: response {i} must be a non-empty 1-D float array, got {h.dtype} {tuple(h.shape)}")
+    if K is None:
+        K = min(8192, max(int(h.size) for h in rows))
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= 8192:
+        raise ValueError(f"rir_bank: K must be an integer in [1, 8192], got {K!r}")
+    bank, delay = np.zeros((len(rows), K), dtype=np.int16), np.zeros(len(rows), dtype=np.int32)
+    for i, h in enumerate(rows):
+        h = h.astype(np.float64)
+        if not np.isfinite(h).all():
+            raise ValueError(f"rir_bank: response {i} holds a value that is not finite")
+        d = int(np.argmax(np.abs(h)))
+        if h[d] == 0.0:
+            raise ValueError(f"rir_bank: response {i} is all zero")
+        if d >= K:
+            raise ValueError(f"rir_bank: response {i} has its direct path at tap {d}, at or behind K = {K}")
+        h = h[:K]
+        q = np.rint(h / math.sqrt(float(np.sum(h * h))) * 32768.0)
+        bank[i, :h.size] = np.clip(q, -32639, 32639).astype(np.int16)
+        delay[i] = d
+    return torch.from_numpy(bank), torch.from_numpy(delay)
 
 
 def noise_bank(arrays, L):

@@ -219,6 +219,13 @@ extern "C" size_t oasr_sizeof_noise_args(void) { return sizeof(oasr_noise_args);
 extern "C" size_t oasr_noise_workspace_bytes(int B, int N) { return (B < 1 || N < 1) ? 0 : noise_workspace_bytes(B, N); }
 extern "C" int oasr_noise_mix(const oasr_noise_args* a, void* stream) { return launch_noise_mix(a, (hipStream_t)stream); }
 
+extern "C" size_t oasr_sizeof_reverb(void) { return sizeof(struct oasr_reverb); }
+extern "C" size_t oasr_sizeof_reverb_args(void) { return sizeof(oasr_reverb_args); }
+extern "C" size_t oasr_reverb_workspace_bytes(int R, int K) {
+  return (R < 1 || R > 65535 || K < 1 || K > 8192) ? 0 : reverb_workspace_bytes(R, K);
+}
+extern "C" int oasr_reverb(const oasr_reverb_args* a, void* stream) { return launch_reverb(a, (hipStream_t)stream); }
+
 extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                                      int64_t* targets_rows_out, int64_t* active_rows_out, void* stream) {
   OASR_REQUIRE(active_rows_out, "oasr_test_span_tables: null");

@@ -356,6 +356,13 @@ struct oasr_noise_args;
 size_t noise_workspace_bytes(int B, int N);
 int launch_noise_mix(const oasr_noise_args* a, hipStream_t s);
 
+// ---- reverberation (reverb.hip; the contract: include/oasr.h at oasr_reverb, the rule: reverb_core.h) -------------------------------------
+// pcm_out = each drawn clip of pcm_in convolved with its bank row on the int8 matrix cores (else a copy); two launches (the bank expanded into
+// a->workspace as MFMA operands, then the convolution), plan on the device
+struct oasr_reverb_args;
+size_t reverb_workspace_bytes(int R, int K);
+int launch_reverb(const oasr_reverb_args* a, hipStream_t s);
+
 // ---- LoRA adapters in weight space (lora.hip) -----------------------------------------------------------------
 // out = W0 + scale * B . A  (W0 [rows][cols] fp32, A [r][cols], B [rows][r]; k sum in ascending order): exactly one of out32 (fp32, may be w0
 // itself) / out16 (bf16, the rounding of launch_cast_f32_bf16)

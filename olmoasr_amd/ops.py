@@ -927,6 +927,107 @@ def noise_plan(prob, snr_db, seed, clip, M, L):
     return bool(d.value), m.value, o.value, s.value
 
 
+def reverb_policy(prob):
+    """The ``oasr_reverb`` block of a policy, refused here (ValueError) for what the library would refuse (OASR_EINVAL): ``prob`` in [0, 1]
+    (kept as round(prob * 65536): the chance of a clip to be drawn)."""
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"reverb: prob must be a number in [0, 1], got {prob!r}")
+    return N.Reverb(int(round(prob * 65536)))
+
+
+def _reverb_args(pcm, n_valid, bank, delay, prob, seed, first_clip, out, cuda):
+    """Checks and converts the operands of ``reverb`` / ``reverb_host``: (ReverbArgs, pcm_out, row, keep-alive)."""
+    what = "reverb" if cuda else "reverb_host"
+
+    def rows(t, nm, shape=None):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int16 and t.dim() == 2):
+            raise ValueError(f"{what}: {nm} must be a 2-D torch.int16 tensor")
+        if t.is_cuda != cuda or t.device != pcm.device:
+            raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor on the device of pcm")
+        if shape is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {nm} must be {list(shape)}, got {tuple(t.shape)}")
+        if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"{what}: {nm} needs unit column stride and rows that do not overlap")
+        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+    if not isinstance(pcm, torch.Tensor):
+        raise ValueError(f"{what}: pcm must be a 2-D torch.int16 tensor")
+    ld_in = rows(pcm, "pcm")
+    ld_rir = rows(bank, "bank")
+    B, n = pcm.shape
+    R, K = bank.shape
+    for t, nm, rows_ in ((n_valid, "n_valid", B), (delay, "delay", R)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == rows_ and t.is_contiguous()
+                and t.device == pcm.device):
+            raise ValueError(f"{what}: {nm} must be a contiguous int32 [{rows_}] on the device of pcm")
+    if not 1 <= n <= N.ReverbArgs.MAX_N or B > N.ReverbArgs.MAX_ROWS:
+        raise ValueError(f"{what}: pcm [B, N] with B <= 65535 and 1 <= N <= 2^26, got {tuple(pcm.shape)}")
+    if not (1 <= K <= N.ReverbArgs.MAX_K and 1 <= R <= N.ReverbArgs.MAX_ROWS):
+        raise ValueError(f"{what}: bank [R, K] with 1 <= R <= 65535 and 1 <= K <= 8192, got {tuple(bank.shape)}")
+    a = N.ReverbArgs()
+    a.policy = reverb_policy(prob)
+    a.seed, a.first_clip = _u64("seed", seed, what), _u64("first_clip", first_clip, what)
+    if out is None:
+        out = torch.empty(B, n, dtype=torch.int16, device=pcm.device)
+    ld_out = rows(out, "out", (B, n))
+    if B:
+        def span(t, ld, r, c):
+            return t.data_ptr(), t.data_ptr() + 2 * ((r - 1) * ld + c)
+        (lo_i, hi_i), (lo_o, hi_o), (lo_b, hi_b) = span(pcm, ld_in, B, n), span(out, ld_out, B, n), span(bank, ld_rir, R, K)
+        if lo_i < hi_o and lo_o < hi_i:
+            raise ValueError(f"{what}: out overlaps pcm (the operator works out of place)")
+        if lo_b < hi_o and lo_o < hi_b:
+            raise ValueError(f"{what}: out overlaps the bank")
+    row = torch.empty(B, dtype=torch.int32, device=pcm.device)
+    a.pcm_in, a.pcm_out, a.n_valid, a.rir, a.delay, a.row_out = (pcm.data_ptr(), out.data_ptr(), n_valid.data_ptr(), bank.data_ptr(),
+                                                                 delay.data_ptr(), row.data_ptr())
+    a.ld_in, a.ld_out, a.ld_rir, a.B, a.N, a.R, a.K = ld_in, ld_out, ld_rir, B, n, R, K
+    return a, out, row, (pcm, n_valid, bank, delay)
+
+
+def reverb(pcm, n_valid, bank, delay, *, prob, seed=0, first_clip=0, out=None):
+    """Reverberation of int16 PCM on the GPU (include/oasr.h: oasr_reverb; the rule: csrc/reverb_core.h): ``pcm`` int16 [B, N] (unit column
+    stride, any row stride >= N), ``n_valid`` int32 [B] = each row's leading non-padding samples, ``bank`` int16 [R, K] of Q15 impulse
+    responses with K <= 8192 and ``delay`` int32 [R] the index of each one's direct-path tap (``augment.rir_bank`` builds both).  Row ``b``
+    draws -- from stream id ``first_clip + b`` (mod 2^64) under ``seed``, the hash stream of ``spec_augment_``, kind 5 -- whether it is
+    reverberated (``prob``) and a bank row; its first ``n_valid`` samples become the exact convolution with that row, shifted back by the
+    direct-path delay, rounded to Q0 and saturated, so that lengths and timestamps stay.  Taps are read clamped to +-32639 and delays to
+    [0, K - 1].  A row that is not drawn or has ``n_valid`` outside [1, N] is copied.  Returns ``(pcm_out, row)``: int16 [B, N] (``out``, if
+    given: int16 [B, N] that does not overlap ``pcm``) and int32 [B] bank rows (-1: copied).  Two launches on the current stream (the bank
+    expanded into int8 matrix-core operands, then the convolution), no host read; wrong dtypes, shapes or devices raise ValueError before
+    anything is launched."""
+    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda):
+        raise ValueError("reverb: pcm must be a GPU tensor (reverb_host takes CPU tensors)")
+    a, out, row, keep = _reverb_args(pcm, n_valid, bank, delay, prob, seed, first_clip, out, True)
+    if a.B:
+        need = N.lib().oasr_reverb_workspace_bytes(a.R, a.K)
+        ws = _workspace("reverb", pcm.device, need)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        N.call("oasr_reverb", C.byref(a), N.STREAM, device=pcm.device)
+    return out, row
+
+
+def reverb_host(pcm, n_valid, bank, delay, *, prob, seed=0, first_clip=0, out=None):
+    """``reverb`` on CPU tensors through the library's host twin (oasr_reverb_host: the same rule from the same text, no GPU)."""
+    if not (isinstance(pcm, torch.Tensor) and not pcm.is_cuda):
+        raise ValueError("reverb_host: pcm must be a CPU tensor")
+    a, out, row, keep = _reverb_args(pcm, n_valid, bank, delay, prob, seed, first_clip, out, False)
+    if a.B:
+        N.call("oasr_reverb_host", C.byref(a))
+    return out, row
+
+
+def reverb_plan(prob, seed, clip, R):
+    """What ``reverb`` draws for stream id ``clip`` against a bank of ``R`` responses, from the library's host function (oasr_reverb_plan; no
+    GPU, no audio): ``(drawn, row)``."""
+    pol = reverb_policy(prob)
+    if not isinstance(R, int) or isinstance(R, bool) or not 1 <= R <= N.ReverbArgs.MAX_ROWS:
+        raise ValueError(f"reverb_plan: R must be an integer in [1, {N.ReverbArgs.MAX_ROWS}], got {R!r}")
+    d, r = C.c_int(), C.c_int()
+    N.call("oasr_reverb_plan", C.byref(pol), _u64("seed", seed, "reverb_plan"), _u64("clip", clip, "reverb_plan"), R, C.byref(d), C.byref(r))
+    return bool(d.value), r.value
+
+
 def pick_tokens(logits, mask=None, mask2=None, want_logprob=True):
     """logits fp32 [rows, V] (row stride free) -> (argmax ids int64 [rows], log_softmax at the argmax fp32 [rows] | None);
     ``mask`` / ``mask2``: additive fp32 [V] (0 / -inf)."""

@@ -85,7 +85,12 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     # csrc/noise.hip): --noise_bank PATH.npy (int16 [M, L], or an object array of 1-D int16 recordings, tiled to the longest) turns it on;
     # --noise_prob (default 0.5) is a clip's chance to take noise, --noise_snr_db LO,HI (default 5,20) the whole dB the SNR is drawn among.
     # Drawn from --seed and the step counter (spec_offset), like the masks and the speed factors.
-    noise_bank=None, noise_prob=None, noise_snr_db=None)
+    noise_bank=None, noise_prob=None, noise_snr_db=None,
+    # Reverberation of the int16 clips of every TRAINING micro-batch, after speed perturbation and ahead of noise mixing (the far-field recipe;
+    # olmoasr_amd/augment.py, csrc/reverb.hip): --rir_bank PATH.npy (room impulse responses at 16 kHz: a 2-D float array, one response per
+    # row, or an object array of 1-D float responses) turns it on; --reverb_prob (default 0.5) is a clip's chance to be reverberated.  Drawn
+    # from --seed and the step counter (spec_offset), like the masks, the speed factors and the noise.
+    rir_bank=None, reverb_prob=None)
 ERROR_COUNTS = ("host", "device")
 SPEC_OVERRIDES = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_time_ratio", "spec_fill")
 SPEC_PRESETS = ("off", "LD", "LB")
@@ -174,6 +179,40 @@ def noise_policy(args):
         raise SystemExit(f"--noise_prob / --noise_snr_db: {e}")
 
 
+def reverb_policy(args):
+    """--rir_bank and --reverb_prob -> augment.Reverb, or None without a bank (the bank itself is loaded by load_rir_bank)."""
+    if args.rir_bank is None:
+        if args.reverb_prob is not None:
+            raise SystemExit("--reverb_prob given without --rir_bank: name a bank of room impulse responses (PATH.npy) to convolve with")
+        return None
+    if not isinstance(args.rir_bank, str) or not os.path.isfile(args.rir_bank):
+        raise SystemExit(f"--rir_bank must name an existing .npy file, got {args.rir_bank!r}")
+    from olmoasr_amd import augment
+    try:
+        return augment.Reverb(**({} if args.reverb_prob is None else {"prob": args.reverb_prob}))
+    except ValueError as e:
+        raise SystemExit(f"--reverb_prob: {e}")
+
+
+def load_rir_bank(path):
+    """The bank of --rir_bank as (int16 [R, K] Q15 taps, int32 [R] direct-path delays) on the CPU, from a 2-D float array (one response per
+    row) or an object array (or list) of 1-D float responses: augment.rir_bank scales each to unit energy, K = min(8192, the longest)."""
+    import numpy as np
+    from olmoasr_amd import augment
+    try:
+        arr = np.load(path, allow_pickle=True)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--rir_bank {path}: {e}")
+    try:
+        if arr.dtype.kind == "f" and arr.ndim == 2 and arr.shape[0]:
+            return augment.rir_bank(list(arr))
+        if arr.dtype == object and arr.ndim == 1 and len(arr) and all(isinstance(r, np.ndarray) for r in arr):
+            return augment.rir_bank(list(arr))
+    except ValueError as e:
+        raise SystemExit(f"--rir_bank {path}: {e}")
+    raise SystemExit(f"--rir_bank {path}: expected a float [R, K] array or an object array of 1-D float responses, got {arr.dtype} {arr.shape}")
+
+
 def load_noise_bank(path):
     """The bank of --noise_bank as int16 [M, L] on the CPU: a 2-D int16 array as it is, an object array (or list) of 1-D int16 recordings
     tiled cyclically to the longest of them."""
@@ -250,6 +289,7 @@ def parse_args(argv=None):
     args.spec_policy = spec_policy(args)
     args.speed_policy = speed_policy(args)
     args.noise_policy = noise_policy(args)
+    args.reverb_policy = reverb_policy(args)
     if args.train_error_counts not in ERROR_COUNTS:
         raise SystemExit(f"--train_error_counts must be one of {' | '.join(ERROR_COUNTS)}, got {args.train_error_counts!r}")
     if args.train_error_counts == "device" and not args.span_backward:
@@ -588,6 +628,11 @@ def main(argv=None):
         if rank == 0:
             print(json.dumps({"event": "noise_mix", "bank": list(noise_bank.shape), "prob": noise.prob, "snr_db": list(noise.snr_db),
                               "seed": spec_seed}), flush=True)
+    reverb = args.reverb_policy
+    if reverb is not None:
+        rir_bank, rir_delay = (t.to(dev) for t in load_rir_bank(args.rir_bank))
+        if rank == 0:
+            print(json.dumps({"event": "reverb", "bank": list(rir_bank.shape), "prob": reverb.prob, "seed": spec_seed}), flush=True)
     if regularised and rank == 0:
         print(json.dumps({"event": "loss_regularisers", "label_smoothing": args.label_smoothing, "z_loss": args.z_loss}), flush=True)
     device_counts = args.train_error_counts == "device"
@@ -603,6 +648,7 @@ def main(argv=None):
         spec_cells = 0  # cells masked on this rank in this step: from the host plan, no device read-back
         speed_counts = [0] * (len(speed.factors) + 1) if speed is not None else None  # this rank's clips per factor (last entry: fell back to the copy): from the host plan too
         noise_drawn = noise_snr_sum = 0  # this rank's clips that drew noise in this step and the sum of their SNRs: from the host plan too
+        reverb_drawn = 0  # this rank's clips that drew a room response in this step: from the host plan too
         for i in range(accum):
             pcm, ti, ty, tl = next(loader)
             cursor += args.train_batch_size  # (position in this rank's epoch order; a short last batch also ends the epoch)
@@ -618,12 +664,17 @@ def main(argv=None):
                 n_samples = int(pcm.shape[1])
                 pcm, n_speed, _ = speed.apply(pcm, loader.last_n_valid, spec_seed, first, tokens=(ti, ty))
                 speed_counts = [c + d for c, d in zip(speed_counts, speed.factor_counts(spec_seed, first, loader.last_n_valid_host.tolist(), n_samples))]
-            if noise is not None:  # on the clip as the log-mel will see it: its length is what speed perturbation left (in place on that new tensor)
+            n_cur, ours = (n_speed, True) if speed is not None else (loader.last_n_valid, False)  # the clips' lengths; is pcm a tensor of this step's
+            if reverb is not None:  # out of place: a new pcm tensor; the length speed perturbation left stays, and so do the timestamps
                 first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
-                if speed is not None:
-                    noise.apply(pcm, n_speed, noise_bank, spec_seed, first, out=pcm)
+                pcm, ours = reverb.apply(pcm, n_cur, rir_bank, rir_delay, spec_seed, first)[0], True
+                reverb_drawn += reverb.drawn(spec_seed, first, int(pcm.shape[0]), int(rir_bank.shape[0]))
+            if noise is not None:  # on the clip as the log-mel will see it: its length is what speed perturbation left (in place on a new tensor)
+                first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
+                if ours:
+                    noise.apply(pcm, n_cur, noise_bank, spec_seed, first, out=pcm)
                 else:
-                    pcm = noise.apply(pcm, loader.last_n_valid, noise_bank, spec_seed, first)[0]
+                    pcm = noise.apply(pcm, n_cur, noise_bank, spec_seed, first)[0]
                 d_, s_ = noise.drawn(spec_seed, first, int(pcm.shape[0]), *noise_bank.shape)
                 noise_drawn, noise_snr_sum = noise_drawn + d_, noise_snr_sum + s_
             if policy is not None:  # masks go on the FINALIZED log-mel, so the span step takes it finalized as well (mel_clip_max=None)
@@ -687,6 +738,8 @@ def main(argv=None):
                     rec["speed_factor_counts"] = speed_counts
                 if noise is not None:
                     rec.update(noise_drawn=noise_drawn, noise_snr_db_mean=round(noise_snr_sum / noise_drawn, 3) if noise_drawn else None)
+                if reverb is not None:
+                    rec["reverb_drawn"] = reverb_drawn
                 if regularised:
                     rec.update(train_nll=parts[0] / world_size, train_lse_sq=parts[1] / world_size)
                 if preds:
