@@ -425,6 +425,56 @@ typedef struct oasr_edit_args {
 size_t oasr_sizeof_edit_args(void);
 int oasr_edit_counts(const oasr_edit_args*, void* stream);
 int oasr_edit_counts_host(const oasr_edit_args*);
+/* Teacher-forced scoring, forward only (csrc/score.hip; the reduce rule itself: csrc/score_core.h): per position the negative log-likelihood
+ * of the target and the argmax prediction, per sample their totals -- a held-out loss, a token accuracy, or a model-based quality score of
+ * an (audio, transcript) pair, without fp32 logits, without a gradient write and without a host read.  Entry points only: OASR_ABI_VERSION
+ * is unchanged, and a binding checks oasr_sizeof_score_args like oasr_sizeof_edit_args.
+ *
+ * oasr_score_rows: logits [B * S, ld] of `dtype` (OASR_DTYPE_BF16 / OASR_DTYPE_F32), row (b, s) at row b * S + s; V <= ld columns are valid;
+ * targets i64 [B, S]; span i32 [B]; row_nll f32 [B, S]; pred i32 [B, S]; all on the device, contiguous.  Row (b, s):
+ *     s >= span[b]   row_nll = 0, pred = -1, and the row is NOT READ (it may hold anything)
+ *     s <  span[b]   pred = argmax over c < V, the lowest index among equal maxima (columns [V, ld) are never candidates; a row with no
+ *                    column above -inf gives 0); for a valid target (0 <= t < V and t != ignore) row_nll = logsumexp(x[:V]) - x_t with
+ *                    fp32 statistics, otherwise row_nll = 0 exactly.
+ * Each active row is read once when rows are 16-byte aligned (ld a multiple of 8 bf16 / 4 fp32 columns) and V <= 57344; otherwise column by
+ * column.  One launch; null pointers, B or S < 1, V < 1 or ld < V: OASR_EINVAL before it.
+ *
+ * oasr_score_reduce: row (b, s) is COUNTED when s < min(span[b], S) and its target is valid.  Per sample over its counted rows:
+ *     nll_sum f32 [B]  row_nll added in ascending s into a double, rounded once      nll_max f32 [B]  the largest row_nll, 0 if none
+ *     n_tok   i32 [B]  the number of counted rows                                     n_hit   i32 [B]  those with pred == target
+ * One launch, one wave per sample.  oasr_score_reduce_host: HOST function (no GPU call, host pointers), the same rule from the same text;
+ * the two agree bit for bit.  Null pointers or B, S, V < 1: OASR_EINVAL before anything is written.
+ *
+ * oasr_score: the inference forward exactly as oasr_forward runs it (from mel, or the decoder alone from given audio features xa in the
+ * compute dtype, as oasr_decode_logits), then the two launches above on the engine's own logits in the compute dtype with V = n_vocab + 1
+ * and ignore = 51864.  text_len may be NULL (no padding mask), as for oasr_forward; every other pointer is required, exactly one of mel and
+ * xa.  Workspace: OASR_MODE_INFER bytes -- row_nll and pred are the caller's so that plan does not grow.  Reads the compute copies of the
+ * weights only: no gradient, no saved activation, no optimizer state is touched, whatever the context is bound to.  Every refusal (null
+ * pointers, both or neither of mel and xa, B < 1, S outside (0, n_text_ctx], a workspace that is too small: OASR_EINVAL; an unbound
+ * context: OASR_ESTATE) comes before anything is launched or dereferenced. */
+typedef struct oasr_score_args {
+  const float* mel; /* f32 [B, n_mels, 2*n_audio_ctx] */
+  const void* xa;   /* compute dtype [B, n_audio_ctx, n_audio_state]; exactly one of mel and xa */
+  const int64_t* tokens;
+  const int64_t* targets; /* i64 [B, S] each */
+  const int32_t* text_len;
+  const int32_t* span; /* i32 [B] each, device */
+  float* row_nll;
+  int32_t* pred; /* [B, S], caller owned, required */
+  float* nll_sum;
+  float* nll_max;
+  int32_t* n_tok;
+  int32_t* n_hit; /* [B] */
+  int32_t B, S;
+} oasr_score_args;
+size_t oasr_sizeof_score_args(void);
+int oasr_score(oasr_ctx*, const oasr_score_args*, void* workspace, size_t workspace_bytes, void* stream);
+int oasr_score_rows(const void* logits, int dtype, int64_t ld, int V, const int64_t* targets, const int32_t* span, int B, int S, int64_t ignore,
+                    float* row_nll, int32_t* pred, void* stream);
+int oasr_score_reduce(const float* row_nll, const int32_t* pred, const int64_t* targets, const int32_t* span, int B, int S, int V, int64_t ignore,
+                      float* nll_sum, float* nll_max, int32_t* n_tok, int32_t* n_hit, void* stream);
+int oasr_score_reduce_host(const float* row_nll, const int32_t* pred, const int64_t* targets, const int32_t* span, int B, int S, int V,
+                           int64_t ignore, float* nll_sum, float* nll_max, int32_t* n_tok, int32_t* n_hit);
 /* Device-resident beam search (csrc/beam.hip; the rule itself: csrc/beam_core.h): whisper's BeamSearchDecoder.update for every audio window
  * of a batch in one launch, and rearrange_kv_cache as one in-place launch.  Entry points only: OASR_ABI_VERSION is unchanged, and a binding
  * checks oasr_sizeof_beam_args like oasr_sizeof_edit_args.

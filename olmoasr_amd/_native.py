@@ -63,6 +63,11 @@ class EditArgs(C.Structure):  # include/oasr.h: oasr_edit_args
                 ("ld_hyp", C.c_int64), ("ld_ref", C.c_int64), ("B", C.c_int32), ("Lh", C.c_int32), ("Lr", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ScoreArgs(C.Structure):  # include/oasr.h: oasr_score_args
+    _fields_ = [(n, C.c_void_p) for n in ("mel", "xa", "tokens", "targets", "text_len", "span", "row_nll", "pred", "nll_sum", "nll_max", "n_tok",
+                                          "n_hit")] + [("B", C.c_int32), ("S", C.c_int32)]
+
+
 class BeamArgs(C.Structure):  # include/oasr.h: oasr_beam_args
     MAX_BEAM = 15  # OASR_BEAM_MAX
     NOT_FULL = 0x7fffffff  # OASR_BEAM_NOT_FULL
@@ -133,6 +138,7 @@ STRUCT_SIZES = [
     ("oasr_sizeof_reverb", Reverb),  # came with oasr_reverb
     ("oasr_sizeof_reverb_args", ReverbArgs),
     ("oasr_sizeof_train_step_args", TrainStepArgs),  # last grown by label_smoothing / z_loss / loss_parts_*
+    ("oasr_sizeof_score_args", ScoreArgs),  # came with oasr_score, oasr_score_rows and oasr_score_reduce
 ]
 ABI_VERSION = 216  # include/oasr.h: OASR_ABI_VERSION (216: one fused training step, oasr_train_step(oasr_train_step_args), in place of the six positional fused-step entries; 215: oasr_test_* unit operators of the glue kernels, include/oasr_testing.h; 214: staged autograd entries, oasr_train_encode / _decode / _dec_fwd_bwd; 213: LoRA adapters, oasr_create_ex3; 212: oasr_set_trainable; 211: the KV cache's control tail is OASR_KV_TAIL_BYTES; 210: OASR_ERETRY from oasr_decode_check)
 KV_TAIL_BYTES = 327680  # include/oasr.h: OASR_KV_TAIL_BYTES
@@ -233,6 +239,11 @@ def _declare(lib):
         "oasr_sizeof_edit_args": (sz, []),
         "oasr_edit_counts": (i32, [C.POINTER(EditArgs), vp]),
         "oasr_edit_counts_host": (i32, [C.POINTER(EditArgs)]),
+        "oasr_sizeof_score_args": (sz, []),
+        "oasr_score": (i32, [vp, C.POINTER(ScoreArgs), vp, sz, vp]),
+        "oasr_score_rows": (i32, [vp, i32, i64, i32, vp, vp, i32, i32, i64, vp, vp, vp]),
+        "oasr_score_reduce": (i32, [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp]),
+        "oasr_score_reduce_host": (i32, [vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp]),
         "oasr_sizeof_beam_args": (sz, []),
         "oasr_beam_update": (i32, [C.POINTER(BeamArgs), vp]),
         "oasr_beam_update_host": (i32, [C.POINTER(BeamArgs)]),

@@ -208,6 +208,18 @@ extern "C" int oasr_spec_augment(float* mel, int B, int n_mels, int T, const oas
 
 extern "C" int oasr_edit_counts(const oasr_edit_args* a, void* stream) { return launch_edit_counts(a, (hipStream_t)stream); }
 
+extern "C" int oasr_score_rows(const void* logits, int dtype, int64_t ld, int V, const int64_t* targets, const int32_t* span, int B, int S,
+                               int64_t ignore, float* row_nll, int32_t* pred, void* stream) {
+  OASR_REQUIRE(dtype == OASR_DTYPE_BF16 || dtype == OASR_DTYPE_F32, "oasr_score_rows: dtype %d (0 = bf16, 1 = fp32 logits)", dtype);
+  if (dtype == OASR_DTYPE_BF16)
+    return launch_score_rows((const bf16_t*)logits, (long)ld, V, targets, span, B, S, (long)ignore, row_nll, pred, (hipStream_t)stream);
+  return launch_score_rows((const float*)logits, (long)ld, V, targets, span, B, S, (long)ignore, row_nll, pred, (hipStream_t)stream);
+}
+extern "C" int oasr_score_reduce(const float* row_nll, const int32_t* pred, const int64_t* targets, const int32_t* span, int B, int S, int V,
+                                 int64_t ignore, float* nll_sum, float* nll_max, int32_t* n_tok, int32_t* n_hit, void* stream) {
+  return launch_score_reduce(row_nll, pred, targets, span, B, S, V, (long)ignore, nll_sum, nll_max, n_tok, n_hit, (hipStream_t)stream);
+}
+
 extern "C" int oasr_beam_update(const oasr_beam_args* a, void* stream) { return launch_beam_update(a, (hipStream_t)stream); }
 
 extern "C" size_t oasr_sizeof_speed(void) { return sizeof(oasr_speed); }

@@ -39,6 +39,33 @@ extern "C" int oasr_forward(oasr_ctx* c, const float* mel, const int64_t* tokens
   return OASR_BY_DTYPE(c, oasr_forward_impl, c, mel, tokens, text_len, B, S, logits_out, xa_out, workspace, workspace_bytes, stream);
 }
 
+// ---- teacher-forced scoring (oasr_score; the contract: include/oasr.h at oasr_score_args): oasr_forward's forward, then score.hip's two
+// launches on the logits in the compute dtype.  Every refusal, before anything is launched or dereferenced:
+static int score_check(const oasr_ctx* c, const oasr_score_args* a, const void* workspace, size_t workspace_bytes) {
+  RC(check_bound(c, false));
+  OASR_REQUIRE(a, "oasr_score: null args");
+  OASR_REQUIRE(!a->mel != !a->xa, "oasr_score: exactly one of mel and xa is required (mel: the whole forward; xa: the decoder alone on given features)");
+  OASR_REQUIRE(a->tokens && a->targets && a->span && workspace, "oasr_score: bad args (tokens, targets, span and workspace are required)");
+  OASR_REQUIRE(a->row_nll && a->pred && a->nll_sum && a->nll_max && a->n_tok && a->n_hit,
+               "oasr_score: bad args (row_nll, pred [B, S] and nll_sum, nll_max, n_tok, n_hit [B] are required)");
+  OASR_REQUIRE(a->B > 0 && a->S > 0 && a->S <= c->S_max, "oasr_score: B=%d must be positive and S=%d inside (0, n_text_ctx=%d]", a->B, a->S, c->S_max);
+  OASR_REQUIRE(workspace_bytes >= oasr_workspace_bytes(c, a->B, a->S, OASR_MODE_INFER), "oasr_score: workspace too small");
+  return OASR_OK;
+}
+template <typename T>
+static int oasr_score_impl(oasr_ctx* c, const oasr_score_args& a, void* workspace, size_t workspace_bytes, void* stream) {
+  Step<T> s(c, workspace, workspace_bytes, stream, a.B, a.S, a.text_len, false);
+  if (a.xa) RC(copy_xa<T>(c, s.p.xa, a.xa, a.B, s.r.st));
+  else RC(s.r.encoder_fwd(s.p, a.mel));
+  RC(s.r.decoder_fwd(s.p, a.tokens));
+  RC(launch_score_rows(s.p.logits, c->Vp, c->V, a.targets, a.span, a.B, a.S, PAD_ID, a.row_nll, a.pred, s.r.st));
+  return launch_score_reduce(a.row_nll, a.pred, a.targets, a.span, a.B, a.S, c->V, PAD_ID, a.nll_sum, a.nll_max, a.n_tok, a.n_hit, s.r.st);
+}
+extern "C" int oasr_score(oasr_ctx* c, const oasr_score_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  RC(score_check(c, a, workspace, workspace_bytes));
+  return OASR_BY_DTYPE(c, oasr_score_impl, c, *a, workspace, workspace_bytes, stream);
+}
+
 // AudioEncoder.forward (olmoasr/model.py:571-623): mel -> xa bf16 [B, n_audio_ctx, d]
 template <typename T>
 static int oasr_encode_impl(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {

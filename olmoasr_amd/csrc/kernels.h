@@ -339,6 +339,17 @@ int launch_argmax_rows(const bf16_t* logits, long ld, int V, long n_rows, const 
 int launch_argmax_rows(const float* logits, long ld, int V, long n_rows, const int32_t* rows, const int32_t* span, int B, int S, int32_t* pred,
                        hipStream_t s);
 
+// ---- teacher-forced scoring (score.hip; the contract: include/oasr.h at oasr_score, the reduce rule: score_core.h) ----------------------
+// row (b, s) of logits [B * S][ld]: s >= span[b]: (row_nll, pred) = (0, -1), row not read; else pred = argmax_c<V (lowest index among equal
+// maxima) and row_nll = logsumexp(x[:V]) - x_t for a valid target (0 <= t < V, t != ignore), exactly 0 otherwise.  Reads each active row once.
+int launch_score_rows(const bf16_t* logits, long ld, int V, const int64_t* targets, const int32_t* span, int B, int S, long ignore, float* row_nll,
+                      int32_t* pred, hipStream_t s);
+int launch_score_rows(const float* logits, long ld, int V, const int64_t* targets, const int32_t* span, int B, int S, long ignore, float* row_nll,
+                      int32_t* pred, hipStream_t s);
+// per sample: nll_sum (double sum in ascending s, rounded once), nll_max, n_tok, n_hit over the counted rows; one wave per sample
+int launch_score_reduce(const float* row_nll, const int32_t* pred, const int64_t* targets, const int32_t* span, int B, int S, int V, long ignore,
+                        float* nll_sum, float* nll_max, int32_t* n_tok, int32_t* n_hit, hipStream_t s);
+
 // ---- SpecAugment (specaug.hip; the policy block and the rule: include/oasr.h, specaug_core.h) ------------------------------------
 // mel fp32 [B, n_mels, T] in place: the seeded masks of clips first_clip .. first_clip + B - 1 set to policy->fill, nothing else written
 struct oasr_specaug;

@@ -1,7 +1,7 @@
 """Token error counts of a training or evaluation step without a host loop: the sequences ``gen_pred`` scores
 (scripts/training/train_timestamps.py, after the reference's gen_pred / calc_pred_wer, train_timestamps.py:1077-1180) cut out of the
 prediction and target matrices by index arithmetic on their own device, and ``ops.edit_counts`` on them.  Nothing here reads the device
-except ``ErrorCounter.counts()``."""
+except ``ErrorCounter.counts()`` and ``ValidationTotals.record()``."""
 import torch
 
 from . import ops
@@ -80,3 +80,46 @@ class ErrorCounter:
     def rate(self):
         errs, n = self.fraction(self.counts())
         return errs / max(1, n)
+
+
+class ValidationTotals:
+    """Running totals of ``OLMoASR.score`` results over a held-out set, kept on ``device``: ``nll`` float64 [1] (the sum of nll_sum) and
+    ``counts`` int64 [3] = (tokens, hits, samples).  ``add`` sums a batch on the device, ``merge`` adds another instance's totals,
+    ``packed()`` / ``load_packed()`` carry the whole state as ONE float64 [4] tensor for an all-reduce (the counts are far below 2^53, so
+    float64 holds them exactly), and ``record()`` is the only host read.  ``val_loss`` is the token-weighted mean, sum nll_sum / sum n_tok: it
+    does not depend on how the set was cut into batches (a mean of per-batch means would)."""
+
+    def __init__(self, device="cpu"):
+        self.nll = torch.zeros(1, dtype=torch.float64, device=device)
+        self.counts = torch.zeros(3, dtype=torch.int64, device=device)
+
+    def reset(self):
+        self.nll.zero_()
+        self.counts.zero_()
+
+    def add(self, score):
+        """One batch: a ``Score`` (or anything with ``nll_sum``, ``n_tok`` and ``n_hit`` tensors [B])."""
+        dev = self.nll.device
+        self.nll += score.nll_sum.to(torch.float64).sum().to(dev)
+        self.counts[:2] += torch.stack([score.n_tok.to(torch.int64).sum(), score.n_hit.to(torch.int64).sum()]).to(dev)
+        self.counts[2] += score.n_tok.numel()
+        return self
+
+    def merge(self, other):
+        self.nll += other.nll.to(self.nll.device)
+        self.counts += other.counts.to(self.counts.device)
+        return self
+
+    def packed(self):
+        return torch.cat([self.nll, self.counts.to(torch.float64)])
+
+    def load_packed(self, t):
+        self.nll.copy_(t[:1])
+        self.counts.copy_(t[1:].round().to(torch.int64))
+        return self
+
+    def record(self):
+        """{"val_loss", "val_token_acc", "val_n_tokens", "val_n_samples"} as Python numbers: the one device-to-host copy."""
+        nll, tok, hit, n = self.packed().cpu().tolist()
+        tok, hit, n = int(round(tok)), int(round(hit)), int(round(n))
+        return {"val_loss": nll / max(1, tok), "val_token_acc": hit / max(1, tok), "val_n_tokens": tok, "val_n_samples": n}

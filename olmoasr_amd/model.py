@@ -17,7 +17,7 @@ There is no CPU fallback: constructing the model without a HIP device raises.
 """
 import ctypes as C
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import warnings
@@ -29,6 +29,18 @@ from . import _native as N
 from .config.model_dims import ModelDimensions
 
 PAD_ID = 51864
+
+
+class Score(NamedTuple):
+    """What ``OLMoASR.score`` returns, all on the model's device: per sample ``nll_sum`` f32 [B] (the sum of its rows' NLL, accumulated in a
+    double in ascending position and rounded once), ``nll_max`` f32 [B], ``n_tok`` int32 [B] (valid targets below the span), ``n_hit`` int32 [B]
+    (those predicted right); per position ``row_nll`` f32 [B, S] and ``pred`` int32 [B, S] (0 and -1 at or past the span)."""
+    nll_sum: Tensor
+    nll_max: Tensor
+    n_tok: Tensor
+    n_hit: Tensor
+    row_nll: Tensor
+    pred: Tensor
 
 
 def sinusoids(length, channels, max_timescale=10000):
@@ -899,6 +911,68 @@ class OLMoASR(nn.Module):
         shape = (B, self._n_rows) if last_only else (B, S, self._n_rows)
         out = torch.empty(*shape, device=tokens.device, dtype=torch.float32)
         N.call("oasr_decode_logits", self._ctx, tokens, xa, text_len, B, S, int(last_only), out, ws, ws.numel(), N.STREAM)
+        return out
+
+    @torch.no_grad()
+    def score(self, mel: Optional[Tensor], tokens: Tensor, targets: Tensor, text_len: Optional[Tensor], *, audio_features: Optional[Tensor] = None,
+              span: Optional[Tensor] = None) -> Score:
+        """Teacher-forced score of (audio, transcript) pairs, forward only (``oasr_score``): the inference forward of ``model(mel, tokens,
+        text_len)`` in ``eval()``, then per position the negative log-likelihood ``logsumexp(x) - x_t`` of its target over the n_vocab + 1
+        classes and the argmax prediction, read once from the logits in the compute dtype, and per sample their totals (``Score``).  No fp32
+        logits exist, nothing is written to the gradient arena or the optimizer state, and there is no host synchronisation: every result is
+        a device tensor.  It runs the inference forward whatever ``model.training`` says, and reads the same compute copies of the weights as
+        ``forward`` (LoRA adapters included).
+
+        ``tokens`` / ``targets`` int [B, S] for any S <= n_text_ctx (trimming is the caller's job, as with ``forward``); a target of 51864
+        (or outside [0, n_vocab]) is ignored.  ``text_len`` int [B] or None: the key padding mask, as ``forward``'s.  ``span`` int [B] on the
+        device: rows at or past ``span[b]`` are neither read nor counted (``row_nll`` 0, ``pred`` -1); None derives 1 + the last valid target
+        position on the device.  ``audio_features`` (with ``mel=None``): the decoder alone on ``embed_audio``'s output."""
+        if (mel is None) == (audio_features is None):
+            raise ValueError("score: pass exactly one of mel and audio_features (mel=None with audio_features)")
+        for t, nm in ((tokens, "tokens"), (targets, "targets")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and not t.dtype.is_floating_point):
+                raise ValueError(f"score: {nm} must be an integer GPU tensor [B, S]")
+        B, S = tokens.shape
+        if tuple(targets.shape) != (B, S) or B < 1 or not (1 <= S <= self.dims.n_text_ctx):
+            raise ValueError(f"score: tokens {tuple(tokens.shape)} and targets {tuple(targets.shape)} must both be [B >= 1, 1 <= S <= "
+                             f"{self.dims.n_text_ctx}]")
+        dev = tokens.device
+        a = N.ScoreArgs()
+        if mel is not None:
+            N.require_gpu(mel, "mel")
+            if tuple(mel.shape) != (B, self.dims.n_mels, 2 * self.dims.n_audio_ctx):
+                raise ValueError(f"score: mel {tuple(mel.shape)} must be [{B}, {self.dims.n_mels}, {2 * self.dims.n_audio_ctx}]")
+            src = mel.float().contiguous()
+            a.mel = src.data_ptr()
+        else:
+            N.require_gpu(audio_features, "audio_features")
+            if tuple(audio_features.shape) != (B, self.dims.n_audio_ctx, self.dims.n_audio_state):
+                raise ValueError(f"score: audio_features {tuple(audio_features.shape)} must be [{B}, {self.dims.n_audio_ctx}, "
+                                 f"{self.dims.n_audio_state}]")
+            src = audio_features.detach().to(self._act_dtype).contiguous()
+            a.xa = src.data_ptr()
+        tokens = tokens.to(torch.int64).contiguous()
+        targets = targets.to(torch.int64).contiguous()
+        if text_len is not None:
+            if not (isinstance(text_len, torch.Tensor) and text_len.numel() == B):
+                raise ValueError(f"score: text_len must be a tensor [B = {B}] or None")
+            text_len = text_len.to(device=dev, dtype=torch.int32).contiguous()
+        if span is None:
+            valid = (targets != PAD_ID) & (targets >= 0) & (targets <= self.dims.n_vocab)
+            span = torch.where(valid, torch.arange(1, S + 1, device=dev), 0).amax(dim=1)
+        elif not (isinstance(span, torch.Tensor) and span.numel() == B and not span.dtype.is_floating_point):
+            raise ValueError(f"score: span must be an integer tensor [B = {B}] or None")
+        span = span.to(device=dev, dtype=torch.int32).contiguous()
+        out = Score(torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
+                    torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                    torch.empty(B, S, dtype=torch.float32, device=dev), torch.empty(B, S, dtype=torch.int32, device=dev))
+        a.tokens, a.targets, a.span = tokens.data_ptr(), targets.data_ptr(), span.data_ptr()
+        a.text_len = text_len.data_ptr() if text_len is not None else None
+        a.nll_sum, a.nll_max, a.n_tok, a.n_hit = (t.data_ptr() for t in out[:4])
+        a.row_nll, a.pred = out.row_nll.data_ptr(), out.pred.data_ptr()
+        a.B, a.S = B, S
+        ws = self._ws(B, S, N.MODE_INFER)
+        N.call("oasr_score", self._ctx, C.byref(a), ws, ws.numel(), N.STREAM, device=dev)
         return out
 
     # ---- cached decoding (the reference's install_kv_cache_hooks + one decoder step per token) ------------------------

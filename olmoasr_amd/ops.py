@@ -454,6 +454,88 @@ def edit_counts_host(hyp, hyp_len, ref, ref_len):
     return out
 
 
+SCORE_IGNORE = 51864  # the training layout's pad id (csrc/engine_ctx.h: PAD_ID)
+
+
+def _score_targets(what, targets, span, cuda):
+    """Checks and converts ``targets`` [B, S] / ``span`` [B] (None: every row) of the score operators: (targets i64, span i32, B, S)."""
+    if not (isinstance(targets, torch.Tensor) and targets.dim() == 2 and targets.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"{what}: targets must be an int32 / int64 tensor [B, S]")
+    B, S = targets.shape
+    if B < 1 or S < 1:
+        raise ValueError(f"{what}: targets {tuple(targets.shape)}: B and S must be positive")
+    if targets.is_cuda != cuda:
+        raise ValueError(f"{what}: targets must be a {'GPU' if cuda else 'CPU'} tensor")
+    if span is None:
+        span = torch.full((B,), S, dtype=torch.int32, device=targets.device)
+    if not (isinstance(span, torch.Tensor) and span.dtype in (torch.int32, torch.int64) and span.dim() == 1 and span.numel() == B):
+        raise ValueError(f"{what}: span must be an int32 / int64 tensor [B = {B}]")
+    if span.device != targets.device:
+        raise ValueError(f"{what}: targets on {targets.device}, span on {span.device}")
+    return targets.to(torch.int64).contiguous(), span.to(torch.int32).contiguous(), B, S
+
+
+def score_rows(logits, V, targets, span=None, ignore=SCORE_IGNORE):
+    """Per-row negative log-likelihood and argmax of computed logits in one read of each row (include/oasr.h: oasr_score_rows).
+
+    ``logits`` bf16 / fp32 [B * S, ld] or [B, S, ld] on the GPU (unit column stride, rows ld apart), of which the first ``V`` columns are
+    valid; ``targets`` int [B, S]; ``span`` int [B] or None (every row).  Returns (row_nll f32 [B, S], pred int32 [B, S]): rows at or past
+    the span hold (0, -1) and are not read; the others hold the argmax over c < V (lowest index among equal maxima) and, for a valid target
+    (0 <= t < V, t != ignore), logsumexp(x[:V]) - x_t, else exactly 0.  One launch on the current stream, no host read."""
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in (BF, torch.float32)):
+        raise ValueError("score_rows: logits must be a bf16 / fp32 GPU tensor")
+    targets, span, B, S = _score_targets("score_rows", targets, span, True)
+    if logits.dim() == 3:
+        if logits.shape[:2] != (B, S) or (B > 1 and logits.stride(0) != S * logits.stride(1)):
+            raise ValueError(f"score_rows: logits {tuple(logits.shape)} must be [B = {B}, S = {S}, ld] with evenly spaced rows")
+        ld, width, unit = logits.stride(1), logits.shape[2], logits.stride(2)
+    elif logits.dim() == 2 and logits.shape[0] == B * S:
+        ld, width, unit = logits.stride(0), logits.shape[1], logits.stride(1)
+    else:
+        raise ValueError(f"score_rows: logits {tuple(logits.shape)} must be [B * S = {B * S}, ld] or [B, S, ld]")
+    V = int(V)
+    if not (1 <= V <= width) or (width > 1 and unit != 1) or (B * S > 1 and ld < width):
+        raise ValueError(f"score_rows: need 1 <= V = {V} <= {width} columns, unit column stride and a row stride >= the row width")
+    if targets.device != logits.device:
+        raise ValueError("score_rows: logits and targets on different devices")
+    row_nll = torch.empty(B, S, dtype=torch.float32, device=logits.device)
+    pred = torch.empty(B, S, dtype=torch.int32, device=logits.device)
+    N.call("oasr_score_rows", logits, 0 if logits.dtype == BF else 1, ld if B * S > 1 else width, V, targets, span, B, S, int(ignore), row_nll,
+           pred, N.STREAM)
+    return row_nll, pred
+
+
+def _score_reduce(what, row_nll, pred, targets, span, V, ignore, cuda):
+    targets, span, B, S = _score_targets(what, targets, span, cuda)
+    for t, nm, dt in ((row_nll, "row_nll", torch.float32), (pred, "pred", torch.int32)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == (B, S) and t.device == targets.device):
+            raise ValueError(f"{what}: {nm} must be a {dt} tensor [B = {B}, S = {S}] on the targets' device")
+    if int(V) < 1:
+        raise ValueError(f"{what}: V = {V} must be positive")
+    dev = targets.device
+    out = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
+           torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    args = (row_nll.contiguous(), pred.contiguous(), targets, span, B, S, int(V), int(ignore)) + out
+    if cuda:
+        N.call("oasr_score_reduce", *args, N.STREAM)
+    else:
+        N.call("oasr_score_reduce_host", *args)
+    return out
+
+
+def score_reduce(row_nll, pred, targets, span=None, *, V, ignore=SCORE_IGNORE):
+    """Per-sample totals of ``score_rows``' output (include/oasr.h: oasr_score_reduce; the rule: csrc/score_core.h): over the rows with
+    s < span[b] and a valid target, (nll_sum f32 [B]: a double sum in ascending s rounded once, nll_max f32 [B]: 0 if none, n_tok int32 [B],
+    n_hit int32 [B]: pred == target).  GPU tensors, one launch on the current stream, no host read."""
+    return _score_reduce("score_reduce", row_nll, pred, targets, span, V, ignore, True)
+
+
+def score_reduce_host(row_nll, pred, targets, span=None, *, V, ignore=SCORE_IGNORE):
+    """``score_reduce`` on CPU tensors through the library's host twin (oasr_score_reduce_host: the same rule from the same text, no GPU);
+    the two agree bit for bit."""
+    return _score_reduce("score_reduce_host", row_nll, pred, targets, span, V, ignore, False)
+
+
 class BeamState:
     """What a device-resident beam search keeps between steps (include/oasr.h at oasr_beam_update), on one device -- the GPU, or the CPU
     for ``beam_update_host``: the two ``[n, n_ctx]`` int64 token buffers a step alternates between (``tokens`` is the current one, ``len``

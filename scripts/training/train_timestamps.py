@@ -90,7 +90,14 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     # olmoasr_amd/augment.py, csrc/reverb.hip): --rir_bank PATH.npy (room impulse responses at 16 kHz: a 2-D float array, one response per
     # row, or an object array of 1-D float responses) turns it on; --reverb_prob (default 0.5) is a clip's chance to be reverberated.  Drawn
     # from --seed and the step counter (spec_offset), like the masks, the speed factors and the noise.
-    rir_bank=None, reverb_prob=None)
+    rir_bank=None, reverb_prob=None,
+    # Held-out loss (OLMoASR.score, csrc/score.hip: forward only, no fp32 logits, no gradient write).  --val_freq N (0 = off: step and log
+    # records unchanged) scores a validation set every N optimizer steps, after the step: with --synthetic the --n_val indices
+    # n_synthetic + 8 + i (disjoint from every training shard and from evaluate()'s clips), else the shards under --val_samples_dicts_dir
+    # (its first --n_val samples).  Validation clips are never augmented; each rank scores ddp.shard_indices of the set in batches of
+    # --val_batch_size (default: train_batch_size) trimmed to the batch's largest span rounded up to 64, the totals are all-reduced as one
+    # tensor and rank 0 prints {"event": "val", val_loss (token-weighted), val_token_acc, val_n_tokens, val_subs / val_dels / val_ins}.
+    val_freq=0, val_samples_dicts_dir=None, n_val=256, val_batch_size=None)
 ERROR_COUNTS = ("host", "device")
 SPEC_OVERRIDES = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_time_ratio", "spec_fill")
 SPEC_PRESETS = ("off", "LD", "LB")
@@ -294,7 +301,22 @@ def parse_args(argv=None):
         raise SystemExit(f"--train_error_counts must be one of {' | '.join(ERROR_COUNTS)}, got {args.train_error_counts!r}")
     if args.train_error_counts == "device" and not args.span_backward:
         raise SystemExit("--train_error_counts=device takes the predictions from the span step: it needs --span_backward=True")
+    if args.val_batch_size is None:
+        args.val_batch_size = args.train_batch_size
+    for flag, low in (("val_freq", 0), ("n_val", 1), ("val_batch_size", 1)):
+        v = args[flag]
+        if isinstance(v, bool) or not isinstance(v, int) or v < low:
+            raise SystemExit(f"--{flag} must be an integer >= {low}, got {v!r}")
+    if args.val_samples_dicts_dir and not args.val_freq:
+        raise SystemExit("--val_samples_dicts_dir names a validation set but --val_freq is 0: pass --val_freq N to score it every N steps")
+    if args.val_freq and not args.synthetic and not args.val_samples_dicts_dir:
+        raise SystemExit("--val_freq with --synthetic False needs --val_samples_dicts_dir (the held-out shards)")
     return args
+
+
+def val_indices(args):
+    """The synthetic validation set: --n_val indices past the training range [0, n_synthetic) and past evaluate()'s eight held-out clips."""
+    return [int(args.n_synthetic) + 8 + i for i in range(int(args.n_val))]
 
 
 class GradScalerState:
@@ -512,6 +534,37 @@ def evaluate(net, indices, dev, timestamps=False, sample_len=32, batch=8, error_
     return token_error_rate(preds, tgts)
 
 
+def validate(net, dev, rank, world_size, batch, *, indices=None, shards=None, timestamps=False):
+    """One pass over the validation set (``indices``: synthetic sample ids; else the first samples of ``shards``): this rank scores
+    ddp.shard_indices of it with ``net.score``, never augmented.  Returns ONE float64 device tensor [8] = ValidationTotals.packed() followed
+    by the (S, D, I, H) counts of the teacher-forced predictions, summed over the ranks; nothing is read here."""
+    from olmoasr_amd import ddp, metrics, validation
+    n = len(indices) if indices is not None else len(shards)
+    mine = ddp.shard_indices(n, rank, world_size)
+
+    def fetch(pos):  # positions in this rank's share -> a host batch
+        if indices is not None:
+            return validation.synthetic_batch([indices[mine[j]] for j in pos], timestamps)
+        return validation.shard_batch(shards, [mine[j] for j in pos])
+    totals, counter = metrics.ValidationTotals(dev), metrics.ErrorCounter(dev)
+    for _ in validation.score_set(net, len(mine), fetch, dev, batch, totals, counter):
+        pass
+    t = torch.cat([totals.packed(), counter.total.double()])
+    if world_size > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
+def val_record(t, global_step):
+    """The "val" log record from ``validate``'s tensor: the one device-to-host copy of a validation pass."""
+    from olmoasr_amd import metrics
+    t = t.cpu()
+    rec = metrics.ValidationTotals().load_packed(t[:4]).record()
+    sdih = [int(round(v)) for v in t[4:].tolist()]
+    return {"event": "val", "global_step": global_step, "val_loss": rec["val_loss"], "val_token_acc": rec["val_token_acc"],
+            "val_n_tokens": rec["val_n_tokens"], "val_n_samples": rec["val_n_samples"], "val_subs": sdih[0], "val_dels": sdih[1], "val_ins": sdih[2]}
+
+
 def host_cores():
     n = len(os.sched_getaffinity(0))
     try:
@@ -613,6 +666,14 @@ def main(argv=None):
         per_rank = len(mine)
         loader = SynthLoader(batch_order(cursor), dev, workers=workers, depth=max(1, int(args.prefetch_factor)), timestamps=bool(args.timestamps))
     held_out = [args.n_synthetic + i for i in range(8)]  # evaluate(): clips outside every rank's training shard (never masked)
+    val_set = {}
+    if args.val_freq:
+        if args.val_samples_dicts_dir:
+            from olmoasr_amd import data
+            val_samples = data.load_samples_dicts(args.val_samples_dicts_dir)[:int(args.n_val)]
+            val_set = dict(shards=data.AudioTextShards(val_samples))
+        else:
+            val_set = dict(indices=val_indices(args), timestamps=bool(args.timestamps))
     policy, spec_seed = args.spec_policy, int(args.seed) & ((1 << 64) - 1)
     if policy is not None and rank == 0:
         print(json.dumps({"event": "spec_augment", "policy": args.spec_augment, "freq_masks": policy.freq_masks, "freq_width": policy.freq_width,
@@ -747,6 +808,13 @@ def main(argv=None):
                 if scored:
                     errs, n_ref = metrics.ErrorCounter.fraction(sdih)
                     rec.update(train_token_error_rate=round(errs / max(1, n_ref), 4), train_subs=sdih[0], train_dels=sdih[1], train_ins=sdih[2])
+                log.append(rec)
+                print(json.dumps(rec), flush=True)
+        if args.val_freq and global_step % int(args.val_freq) == 0:
+            t_val = time.time()
+            rec = val_record(validate(net, dev, rank, world_size, int(args.val_batch_size), **val_set), global_step)
+            if rank == 0:
+                rec["val_seconds"] = round(time.time() - t_val, 4)
                 log.append(rec)
                 print(json.dumps(rec), flush=True)
         if args.run_eval and args.eval_freq and global_step % int(args.eval_freq) == 0 and rank == 0:
