@@ -20,12 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/oasr.h"
-
-#if defined(__HIPCC__)
-#define BEAM_HD __host__ __device__ __forceinline__
-#else
-#define BEAM_HD inline
-#endif
+#include "core_hd.h"
 
 #define BEAM_MAX 15                             // beams per window: the selection kernel returns K = B + 1 <= 16 candidates per row
 #define BEAM_MAX_CAND (BEAM_MAX * (BEAM_MAX + 1))  // 240 candidates per window
@@ -38,16 +33,16 @@ struct BeamWalk {
   int16_t fin[BEAM_MAX];  // at most one eot entry per distinct prefix
 };
 
-BEAM_HD double beam_score(float sum, float logprob) { return (double)sum + (double)logprob; }
+OASR_HD double beam_score(float sum, float logprob) { return (double)sum + (double)logprob; }
 
 // eq: B x B bytes, eq[j1 * B + j2] = the prefixes of rows j1 and j2 are equal over all `len` tokens
-BEAM_HD bool beam_same_key(int c1, int c2, int B, const int64_t* tok, const uint8_t* eq) {
+OASR_HD bool beam_same_key(int c1, int c2, int B, const int64_t* tok, const uint8_t* eq) {
   const int K = B + 1;
   return tok[c1] == tok[c2] && eq[(c1 / K) * B + c2 / K] != 0;
 }
 
 // Is candidate c the first occurrence of its key?  Then *last = the last occurrence (whose score and origin the entry takes).
-BEAM_HD bool beam_resolve(int c, int B, const int64_t* tok, const uint8_t* eq, int* last) {
+OASR_HD bool beam_resolve(int c, int B, const int64_t* tok, const uint8_t* eq, int* last) {
   const int n = B * (B + 1);
   for (int p = 0; p < c; ++p)
     if (beam_same_key(p, c, B, tok, eq)) return false;
@@ -59,7 +54,7 @@ BEAM_HD bool beam_resolve(int c, int B, const int64_t* tok, const uint8_t* eq, i
 }
 
 // rank of entry c: how many entries precede it.  first[p] != 0 marks the entries, score[p] is an entry's (resolved) score.
-BEAM_HD int beam_rank(int c, int n, const uint8_t* first, const double* score) {
+OASR_HD int beam_rank(int c, int n, const uint8_t* first, const double* score) {
   const double s = score[c];
   int r = 0;
   for (int p = 0; p < n; ++p)
@@ -68,7 +63,7 @@ BEAM_HD int beam_rank(int c, int n, const uint8_t* first, const double* score) {
 }
 
 // order[r] = the entry of rank r, or -1.  room = what the pool still takes (C - count, not below 0).
-BEAM_HD void beam_walk(const int16_t* order, int n, const int64_t* tok, int64_t eot, int B, int room, BeamWalk* w) {
+OASR_HD void beam_walk(const int16_t* order, int n, const int64_t* tok, int64_t eot, int B, int room, BeamWalk* w) {
   w->n_cont = 0, w->n_fin = 0;
   for (int r = 0; r < n; ++r) {
     const int c = order[r];
@@ -83,7 +78,7 @@ BEAM_HD void beam_walk(const int16_t* order, int n, const int64_t* tok, int64_t 
 }
 
 // is a step at prefix length `len` latched?  (pool_full_len: int32 [n_audio])
-BEAM_HD bool beam_latched(const int32_t* pool_full_len, int n_audio, int len) {
+OASR_HD bool beam_latched(const int32_t* pool_full_len, int n_audio, int len) {
   for (int a = 0; a < n_audio; ++a)
     if (pool_full_len[a] >= len) return false;
   return true;
@@ -104,7 +99,7 @@ inline const char* beam_args_error(const oasr_beam_args* a) {
 
 // row j of a reorder continues row sources[j]: every source must lie in its destination's group of `group` rows (beams never cross
 // windows: the cross-attention K/V do not move).  -1 = fine, else the first offending row.
-BEAM_HD int beam_sources_error(const int32_t* sources, int B, int group) {
+OASR_HD int beam_sources_error(const int32_t* sources, int B, int group) {
   for (int j = 0; j < B; ++j) {
     const int lo = j / group * group;
     if (sources[j] < lo || sources[j] >= lo + group) return j;

@@ -41,6 +41,12 @@ void oasr_set_error(const char* fmt, ...);
     }                            \
   } while (0)
 
+// the caller's workspace of an argument block a: null, not `align`-byte aligned or below `need` bytes is OASR_EINVAL (entry, sizer: the
+// names of the entry point and of its workspace-size function, as string literals)
+#define OASR_REQUIRE_WORKSPACE(a, align, need, entry, sizer)                                                         \
+  OASR_REQUIRE((a)->workspace && ((uintptr_t)(a)->workspace & ((align) - 1)) == 0 && (a)->workspace_bytes >= (need), \
+               entry ": workspace null, not %d-byte aligned or below " sizer " (%zu < %zu bytes)", (int)(align), (a)->workspace_bytes, (size_t)(need))
+
 #define OASR_LAUNCH_CHECK() OASR_CHECK_HIP(hipGetLastError())
 
 // Experiment / A-B switches read from the environment (OASR_PP_*, OASR_GEMM_*, OASR_LOGMEL, OASR_PROF_SHAPES, OASR_XCD_FLAGS) are part of the

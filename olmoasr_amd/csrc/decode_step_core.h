@@ -6,11 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define DEC_HD __host__ __device__ __forceinline__
-#else
-#define DEC_HD inline
-#endif
+#include "core_hd.h"
 
 // ---- element offsets of one decoder layer: w* into the bf16 shadow, bqkv_aux into the aux region, the rest into the fp32 parameter arena -----
 // The one-launch kernels take layer 0's by value in their arguments (the field order is kernel-argument layout) and derive layer l from two
@@ -28,7 +24,7 @@ static_assert(sizeof(long) == sizeof(int64_t), "DecLayerOffsets holds arena offs
 namespace dec {
 
 // layer l = layer 0 + l * lstride; bqkv_aux, the one field that lives in the aux region, strides by astride
-DEC_HD DecLayerOffsets layer_at(const DecLayerOffsets& l0, int l, long lstride, long astride) {
+OASR_HD DecLayerOffsets layer_at(const DecLayerOffsets& l0, int l, long lstride, long astride) {
   DecLayerOffsets y = l0;
   const long s = (long)l * lstride;
   y.ln1g += s, y.ln1b += s, y.wqkv += s, y.wo += s, y.bo += s, y.lncg += s, y.lncb += s, y.wcq += s, y.bcq += s, y.wco += s, y.bco += s;
@@ -40,7 +36,7 @@ DEC_HD DecLayerOffsets layer_at(const DecLayerOffsets& l0, int l, long lstride, 
 // ---- cached keys are processed in segments of <= SEG_KEYS (decode_shared.h: the scores of a segment live in LDS) ------------------------------
 constexpr int SEG_KEYS = 768;
 constexpr int MAX_SEG = 2;  // Tk <= 1536
-DEC_HD int n_segments(int Tk) { return (Tk + SEG_KEYS - 1) / SEG_KEYS; }
+OASR_HD int n_segments(int Tk) { return (Tk + SEG_KEYS - 1) / SEG_KEYS; }
 
 // ---- the KV cache's control tail (the last OASR_KV_TAIL_BYTES of the cache, zeroed by oasr_decode_begin), in 32-bit words -----------------------
 enum KvCtrl : int {

@@ -38,13 +38,13 @@ constexpr int wmu() {  // ceil(units of the workgroup at most / compute waves); 
 }
 
 // Work split: a projection's N output rows are dealt out in contiguous runs of R = wide_rows(N, nwg) rows per workgroup
-DEC_HD int wide_rows(int N, int nwg) { return 2 * ((N + 2 * nwg - 1) / (2 * nwg)); }
+OASR_HD int wide_rows(int N, int nwg) { return 2 * ((N + 2 * nwg - 1) / (2 * nwg)); }
 // Units (row r of the workgroup's run, 512-element K span j), numbered u = r J + j, are dealt to the compute waves in contiguous runs of
 // upw = ceil(U / WC): one division per wave and phase, then (r, j) by stepping.
 struct WUnits {
   int U, upw, u0, r0, j0, J, KC;
 };
-DEC_HD WUnits units_of(int K, int N, int R, int wg, int wave) {  // an [N x K] projection, R rows per workgroup
+OASR_HD WUnits units_of(int K, int N, int R, int wg, int wave) {  // an [N x K] projection, R rows per workgroup
   WUnits q;
   q.KC = K >> 3, q.J = (q.KC + 63) >> 6;
   int rows = N - wg * R;

@@ -17,12 +17,12 @@ struct XGeom {
   int nkb_d, nkb_4d;  // ring blocks per wave and tile
   int cnt_qkv, cnt_d, cnt_4d, cnt_it;  // tiles of this workgroup in a phase of 3d/32, d/32, 4d/32 tiles; cross-attention items
 };
-DEC_HD int cnt_of(int n, int wg, int team) {  // tiles t = wg, wg + team, ... < n (a short loop instead of a division)
+OASR_HD int cnt_of(int n, int wg, int team) {  // tiles t = wg, wg + team, ... < n (a short loop instead of a division)
   int c = 0;
   for (int t = wg; t < n; t += team) ++c;
   return c;
 }
-DEC_HD XGeom make_geom(int d, int H, int Te, int M, int L, int team, int wg) {
+OASR_HD XGeom make_geom(int d, int H, int Te, int M, int L, int team, int wg) {
   XGeom g;
   g.d = d, g.H = H, g.Te = Te, g.M = M, g.team = team, g.wg = wg, g.L = L;
   g.ns = Te > dec::SEG_KEYS ? 2 : 1;
@@ -35,13 +35,13 @@ DEC_HD XGeom make_geom(int d, int H, int Te, int M, int L, int team, int wg) {
   return g;
 }
 // tiles (items for segment 3) of this workgroup in streamed segment `seg` (selects, not a table: the cursors live in SGPRs)
-DEC_HD int seg_cnt(const XGeom& g, int seg) { return seg == 0 ? g.cnt_qkv : seg == 3 ? g.cnt_it : seg == 5 ? g.cnt_4d : g.cnt_d; }
+OASR_HD int seg_cnt(const XGeom& g, int seg) { return seg == 0 ? g.cnt_qkv : seg == 3 ? g.cnt_it : seg == 5 ? g.cnt_4d : g.cnt_d; }
 struct XItem {
   int b, h, sg, n, kvb;  // sequence, head, key segment, keys in it, ring blocks per K (or V) stream
 };
 // (no integer division anywhere near the cursors: hipcc expands a 32-bit division through VALU float reciprocals, whose result -- and
 // everything computed from it, i.e. the whole block bookkeeping -- then lives in VGPRs under exec-mask branches instead of SGPRs)
-DEC_HD XItem item_of(const XGeom& g, int idx) {
+OASR_HD XItem item_of(const XGeom& g, int idx) {
   const int id = g.wg + g.team * idx;
   const int hn = g.H * g.ns;
   XItem it;
@@ -62,12 +62,12 @@ struct XCur {
 #else
 #define XU(x) (x)
 #endif
-DEC_HD int nsub_of(const XGeom& g, int seg, int idx) {
+OASR_HD int nsub_of(const XGeom& g, int seg, int idx) {
   if (seg == 3) return 2 * item_of(g, idx).kvb;
   return seg == 6 ? g.nkb_4d : g.nkb_d;
 }
 // skip empty segments; returns false past the last layer
-DEC_HD bool cur_normalise(const XGeom& g, XCur& c) {
+OASR_HD bool cur_normalise(const XGeom& g, XCur& c) {
   while (c.layer < g.L && c.idx >= seg_cnt(g, c.seg)) {
     c.idx = 0;
     if (++c.seg == NSEG) c.seg = 0, ++c.layer;
@@ -75,13 +75,13 @@ DEC_HD bool cur_normalise(const XGeom& g, XCur& c) {
   return c.layer < g.L;
 }
 // the cursor's sub already points one past the unit's last full block: roll over into the next tile / item / segment if the unit ends there
-DEC_HD bool cur_advance_from(const XGeom& g, XCur& c) {
+OASR_HD bool cur_advance_from(const XGeom& g, XCur& c) {
   if (c.sub >= nsub_of(g, c.seg, c.idx)) c.sub = 0, ++c.idx;
   const bool more = cur_normalise(g, c);
   c.layer = XU(c.layer), c.seg = XU(c.seg), c.idx = XU(c.idx), c.sub = XU(c.sub);
   return more;
 }
-DEC_HD bool cur_advance(const XGeom& g, XCur& c) {
+OASR_HD bool cur_advance(const XGeom& g, XCur& c) {
   if (++c.sub >= nsub_of(g, c.seg, c.idx)) c.sub = 0, ++c.idx;
   const bool more = cur_normalise(g, c);
   c.layer = XU(c.layer), c.seg = XU(c.seg), c.idx = XU(c.idx), c.sub = XU(c.sub);

@@ -17,12 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/oasr.h"
-
-#if defined(__HIPCC__)
-#define ED_HD __host__ __device__ __forceinline__
-#else
-#define ED_HD inline
-#endif
+#include "core_hd.h"
 
 #define ED_MAX_LEN 1023  // cost, S and D each fit 10 bits
 
@@ -30,12 +25,12 @@
 #define ED_STEP_DEL ((1u << 20) | 1u)
 #define ED_STEP_INS (1u << 20)
 
-ED_HD uint32_t ed_row0(int j) { return ((uint32_t)j << 20) | (uint32_t)j; }  // (0, j): j deletions
-ED_HD uint32_t ed_col0(int i) { return (uint32_t)i << 20; }                   // (i, 0): i insertions
-ED_HD uint32_t ed_cost(uint32_t c) { return c >> 20; }
+OASR_HD uint32_t ed_row0(int j) { return ((uint32_t)j << 20) | (uint32_t)j; }  // (0, j): j deletions
+OASR_HD uint32_t ed_col0(int i) { return (uint32_t)i << 20; }                   // (i, 0): i insertions
+OASR_HD uint32_t ed_cost(uint32_t c) { return c >> 20; }
 
 // diag = (i-1, j-1), left = (i, j-1), up = (i-1, j); neq = hyp[i-1] != ref[j-1]
-ED_HD uint32_t ed_cell(uint32_t diag, uint32_t left, uint32_t up, bool neq) {
+OASR_HD uint32_t ed_cell(uint32_t diag, uint32_t left, uint32_t up, bool neq) {
   const uint32_t cd = ed_cost(diag) + (neq ? 1u : 0u), cl = ed_cost(left) + 1u, cu = ed_cost(up) + 1u;
   if (cd <= cl && cd <= cu) return diag + (neq ? ED_STEP_SUB : 0u);
   if (cl <= cu) return left + ED_STEP_DEL;
@@ -43,13 +38,13 @@ ED_HD uint32_t ed_cell(uint32_t diag, uint32_t left, uint32_t up, bool neq) {
 }
 
 // out[0 .. 4) = (S, D, I, H) of the final cell
-ED_HD void ed_unpack(uint32_t c, int ref_len, int32_t* out) {
+OASR_HD void ed_unpack(uint32_t c, int ref_len, int32_t* out) {
   const int s = (int)((c >> 10) & 1023u), d = (int)(c & 1023u);
   out[0] = s, out[1] = d, out[2] = (int)ed_cost(c) - s - d, out[3] = ref_len - s - d;
 }
 
 // a length the contract allows for a row of `width` tokens
-ED_HD bool ed_len_ok(int len, int64_t width) { return len >= 0 && len <= ED_MAX_LEN && (int64_t)len <= width; }
+OASR_HD bool ed_len_ok(int len, int64_t width) { return len >= 0 && len <= ED_MAX_LEN && (int64_t)len <= width; }
 
 // what both entry points refuse without looking at the lengths (which the device entry cannot read on the host); null = fine
 inline const char* ed_args_error(const oasr_edit_args* a) {

@@ -3,21 +3,16 @@
 // widths run an odd-even transposition sort, W rounds of neighbour exchanges.  Plain C++ so that a host program can check the networks
 // exhaustively (0/1 principle: a network that selects the median of every 0/1 input selects it for every input).
 #pragma once
+#include "core_hd.h"
 
-#if defined(__HIPCC__)
-#define MED_HD __host__ __device__ __forceinline__
-#else
-#define MED_HD inline
-#endif
-
-MED_HD void med_cx(float& a, float& b) {  // a <= b afterwards
+OASR_HD void med_cx(float& a, float& b) {  // a <= b afterwards
   const float lo = a < b ? a : b, hi = a < b ? b : a;
   a = lo;
   b = hi;
 }
 
 template <int W>
-MED_HD float median_net(float (&p)[W]) {
+OASR_HD float median_net(float (&p)[W]) {
   static_assert(W % 2 == 1 && W >= 1 && W <= 15, "odd widths up to 15");
   if (W == 1) return p[0];
 #if defined(__HIPCC__)
@@ -32,14 +27,14 @@ MED_HD float median_net(float (&p)[W]) {
   return p[W / 2];
 }
 template <>
-MED_HD float median_net<3>(float (&p)[3]) {
+OASR_HD float median_net<3>(float (&p)[3]) {
   med_cx(p[0], p[1]);
   med_cx(p[1], p[2]);
   med_cx(p[0], p[1]);
   return p[1];
 }
 template <>
-MED_HD float median_net<7>(float (&p)[7]) {
+OASR_HD float median_net<7>(float (&p)[7]) {
   med_cx(p[0], p[5]);
   med_cx(p[0], p[3]);
   med_cx(p[1], p[6]);

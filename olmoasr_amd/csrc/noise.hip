@@ -1,12 +1,11 @@
 // Noise mixing of int16 PCM (include/oasr.h at oasr_noise_mix; the rule: noise_core.h): a bank row added at a drawn offset and SNR, in two
 // launches -- exact energies, then gain and mix -- with no host round trip, no memset and no atomics.
 //
-// A tile is NOISE_TILE = 2048 consecutive samples of one clip, laid on the 16-byte grid of the OUTPUT row's address (a row may start at any
-// even address), thread t of 256 holding samples 8 t .. 8 t + 7 of it: every store is one aligned 16-byte store but for a row's first and last
-// few samples.  The clip and the bank row sit at other offsets from that grid (the bank's depends on the drawn offset o), so their eight
-// samples are read by one 16-byte load that is only 2-byte aligned -- global memory takes it as it comes, and a wave still covers one contiguous
-// kilobyte; samples go one by one only at a row's ends and where the bank row wraps.  Every workgroup evaluates the clip's plan itself from
-// (seed, clip) -- four hashes of scalar work -- as speed.hip does.
+// A tile is NOISE_TILE = 2048 consecutive samples of one clip on the 16-byte grid of the output row (pcm_tile.h), thread t of 256 holding
+// samples 8 t .. 8 t + 7 of it.  The bank row sits at an offset from that grid that depends on the drawn offset o, so its eight samples come
+// like the clip's, by one 16-byte load that is only 2-byte aligned; samples go one by one only at a row's ends and where the bank row wraps.
+// Every workgroup evaluates the clip's plan itself from (seed, clip) -- four hashes of scalar work (draw_core.h) -- so nothing comes back to
+// the host.
 //   energy   one workgroup per tile that holds samples below n_valid of a drawn clip: the exact sums of x^2 and v^2 over its samples go to
 //            workspace[clip][tile] as two u64.  Other workgroups return at once and write nothing.
 //   mix      one workgroup per NOISE_MIX_TILES = 4 tiles.  It sums the clip's partials (only the tiles the energy launch wrote), computes the
@@ -18,6 +17,7 @@
 #include "kernels.h"
 #include "../../include/oasr.h"
 #include "noise_core.h"
+#include "pcm_tile.h"
 
 static_assert(OASR_NOISE_NONE == NOISE_NONE, "include/oasr.h and noise_core.h disagree");
 
@@ -29,18 +29,6 @@ static_assert(OASR_NOISE_NONE == NOISE_NONE, "include/oasr.h and noise_core.h di
 
 static inline long noise_tiles(int N) { return ((long)N + 7 + NOISE_TILE - 1) / NOISE_TILE; }  // a row's tiles, whatever its address
 size_t noise_workspace_bytes(int B, int N) { return (size_t)B * (size_t)noise_tiles(N) * 2 * sizeof(uint64_t); }
-
-// samples [n0, n0 + 8) of a row where 0 <= n < hi, zero elsewhere (row + n0 is 2-byte aligned only)
-__device__ __forceinline__ s16x8_t noise_load8(const int16_t* row, int n0, int hi) {
-  s16x8_t v;
-  if (n0 >= 0 && n0 + 8 <= hi) {
-    __builtin_memcpy(&v, row + n0, sizeof(v));
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (n0 + e >= 0 && n0 + e < hi) ? row[n0 + e] : (int16_t)0;
-  }
-  return v;
-}
 
 // the noise under samples [n0, n0 + 8) of a clip: brow[(o + n) % L] where 0 <= n < hi, zero elsewhere; n0 >= -7, o < L
 __device__ __forceinline__ s16x8_t noise_bank8(const int16_t* __restrict__ brow, int o, int L, int n0, int hi) {
@@ -59,17 +47,6 @@ __device__ __forceinline__ s16x8_t noise_bank8(const int16_t* __restrict__ brow,
       if (++p == L) p = 0;
     }
   return v;
-}
-
-// samples [n0, n0 + 8) of a row as one aligned 16-byte store where all eight exist, else one by one (y + n0 is 16-byte aligned)
-__device__ __forceinline__ void noise_store8(int16_t* y, int n0, int N, s16x8_t v) {
-  if (n0 >= 0 && n0 + 8 <= N) {
-    *(s16x8_t*)(y + n0) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (n0 + e >= 0 && n0 + e < N) y[n0 + e] = v[e];
-  }
 }
 
 // the workgroup's sums of (ex, ev), in every thread; s_part: NOISE_WAVES x 2 words of LDS (all threads of the workgroup call this)
@@ -95,11 +72,11 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_energy_kernel(oasr_noise_
   const int16_t* x = a.pcm_in + (size_t)b * (size_t)a.ld_in;
   const int16_t* y = a.pcm_out + (size_t)b * (size_t)a.ld_out;
   const int16_t* brow = a.bank + (size_t)pl.m * (size_t)a.ld_bank;
-  const int lead = (int)(((uintptr_t)y >> 1) & 7);        // samples between the 16-byte boundary at or before y and y
+  const int lead = pcm_lead(y);
   const long n_lo = (long)blockIdx.x * NOISE_TILE - lead;  // the tile covers [n_lo, n_lo + TILE) of the row
   if (n_lo >= nv) return;
   const int n0 = (int)n_lo + NOISE_PER_THREAD * tid;
-  const s16x8_t x8 = noise_load8(x, n0, nv), v8 = noise_bank8(brow, pl.o, a.L, n0, nv);
+  const s16x8_t x8 = pcm_load8(x, n0, nv), v8 = noise_bank8(brow, pl.o, a.L, n0, nv);
   uint64_t ex = 0, ev = 0;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -120,7 +97,7 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_mix_kernel(oasr_noise_arg
   const NoisePlan pl = noise_plan(a.seed, a.first_clip + (uint64_t)b, a.policy.prob_q16, a.policy.snr_lo_db, a.policy.snr_hi_db, a.M, a.L);
   const int16_t* x = a.pcm_in + (size_t)b * (size_t)a.ld_in;  // (x may be y: no __restrict__)
   int16_t* y = a.pcm_out + (size_t)b * (size_t)a.ld_out;
-  const int lead = (int)(((uintptr_t)y >> 1) & 7);
+  const int lead = pcm_lead(y);
   int64_t g = 0;
   bool mixed = false;
   if (pl.drawn && nv >= 1 && nv <= N) {  // (the same for every thread of the workgroup)
@@ -144,22 +121,20 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_mix_kernel(oasr_noise_arg
     const long n_lo = ((long)blockIdx.x * NOISE_MIX_TILES + k) * NOISE_TILE - lead;
     if (n_lo >= N) return;
     const int n0 = (int)n_lo + NOISE_PER_THREAD * tid;
-    s16x8_t y8 = noise_load8(x, n0, N);
+    s16x8_t y8 = pcm_load8(x, n0, N);
     if (n0 < hi_v) {
       const s16x8_t v8 = noise_bank8(brow, pl.o, a.L, n0, hi_v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) y8[e] = noise_sample(y8[e], v8[e], g);
     }
-    noise_store8(y, n0, N, y8);
+    pcm_store8(y, n0, N, y8);
   }
 }
 
 int launch_noise_mix(const oasr_noise_args* a, hipStream_t st) {
   const char* why = noise_args_error(a);
   OASR_REQUIRE(!why, "oasr_noise_mix: %s", why);
-  const size_t need = noise_workspace_bytes(a->B, a->N);
-  OASR_REQUIRE(a->workspace && ((uintptr_t)a->workspace & 7) == 0 && a->workspace_bytes >= need,
-               "oasr_noise_mix: workspace null, not 8-byte aligned or below oasr_noise_workspace_bytes (%zu < %zu bytes)", a->workspace_bytes, need);
+  OASR_REQUIRE_WORKSPACE(a, 8, noise_workspace_bytes(a->B, a->N), "oasr_noise_mix", "oasr_noise_workspace_bytes");
   const long tiles = noise_tiles(a->N);
   hipLaunchKernelGGL(noise_energy_kernel, dim3((unsigned)tiles, (unsigned)a->B), dim3(NOISE_THREADS), 0, st, *a, tiles);
   OASR_LAUNCH_CHECK();

@@ -1,8 +1,6 @@
 // The host half of noise mixing (include/oasr.h at oasr_noise_mix): oasr_noise_plan and oasr_noise_mix_host -- the twin of noise.hip from the
 // same text (noise_core.h).  Plain C++ (no HIP, no GPU call), so it serves where there is no device and builds alone under a host sanitizer
 // (tools/noise_host_check.cpp).
-#include <string.h>
-
 #include "../../include/oasr.h"
 #include "noise_core.h"
 
@@ -16,7 +14,7 @@ extern "C" int oasr_noise_plan(const oasr_noise* p, uint64_t seed, uint64_t clip
     oasr_set_error("oasr_noise_plan: %s", why);
     return OASR_EINVAL;
   }
-  if (M < 1 || M > NOISE_MAX_ROWS || L < 1 || L > NOISE_MAX_N) {
+  if (M < 1 || M > PCM_MAX_ROWS || L < 1 || L > PCM_MAX_N) {
     oasr_set_error("oasr_noise_plan: M = %d outside [1, 65535] or L = %d outside [1, 2^26]", M, L);
     return OASR_EINVAL;
   }
@@ -55,14 +53,14 @@ extern "C" int oasr_noise_mix_host(const oasr_noise_args* a) {
     if (a->snr_out) a->snr_out[b] = mixed ? pl.s : NOISE_NONE;
     if (a->gain_out) a->gain_out[b] = g;
     if (!mixed) {
-      if (y != x) memcpy(y, x, sizeof(int16_t) * (size_t)a->N);
+      pcm_copy_row(y, x, 0, a->N);
       continue;
     }
     for (int n = 0, p = pl.o; n < nv; ++n) {
       y[n] = noise_sample(x[n], v[p], g);
       if (++p == a->L) p = 0;
     }
-    if (y != x) memcpy(y + nv, x + nv, sizeof(int16_t) * (size_t)(a->N - nv));
+    pcm_copy_row(y, x, nv, a->N);
   }
   return OASR_OK;
 }

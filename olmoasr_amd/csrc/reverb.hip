@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "../../include/oasr.h"
 #include "reverb_core.h"
+#include "pcm_tile.h"
 
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 
@@ -59,18 +60,6 @@ __global__ __launch_bounds__(64) void reverb_expand_kernel(oasr_reverb_args a, i
   img[lane] = hi, img[64 + lane] = lo;
 }
 
-// samples [i0, i0 + 8) of a row where 0 <= i < hi, zero elsewhere (row + i0 is 2-byte aligned only)
-__device__ __forceinline__ s16x8_t reverb_load8(const int16_t* row, long i0, int hi) {
-  s16x8_t v;
-  if (i0 >= 0 && i0 + 8 <= hi) {
-    __builtin_memcpy(&v, row + i0, sizeof(v));
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (i0 + e >= 0 && i0 + e < hi) ? row[i0 + e] : (int16_t)0;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(REVERB_THREADS) void reverb_kernel(oasr_reverb_args a, int NS) {
   __shared__ __attribute__((aligned(16))) unsigned char s_xh[REVERB_MAX_WIN], s_xs[REVERB_MAX_WIN];
   const int tid = threadIdx.x, b = blockIdx.y, N = a.N;
@@ -90,7 +79,7 @@ __global__ __launch_bounds__(REVERB_THREADS) void reverb_kernel(oasr_reverb_args
   const int back = 16 * (4 * NS - 1), win = back + REVERB_WG_OUT;  // win <= REVERB_MAX_WIN: NS <= REVERB_MAX_KSTEPS (the launcher's)
   const long w0 = (long)n0 + d - back;                            // the sample at byte 0 of both planes
   for (int p = 8 * tid; p < win; p += 8 * REVERB_THREADS) {       // (win is a multiple of 16)
-    const s16x8_t v = reverb_load8(x, w0 + p, nv);
+    const s16x8_t v = pcm_load8(x, w0 + p, nv);
     u32x2_t h = {0, 0}, l = {0, 0};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -133,7 +122,7 @@ __global__ __launch_bounds__(REVERB_THREADS) void reverb_kernel(oasr_reverb_args
     for (int q = 0; q < 4; ++q) {  // D[row 4 g + q][column col]: output 16 col + 4 g + q of the tile
       const int n = n0 + tb + REVERB_TILE * t + 16 * col + 4 * g + q;
       if (n < nv)
-        y[n] = reverb_round(reverb_combine(p_hh[t][q], p_mid[t][q], p_ll[t][q], tap_sum));
+        y[n] = pcm_round_q15(reverb_combine(p_hh[t][q], p_mid[t][q], p_ll[t][q], tap_sum));
       else if (n < N)
         y[n] = x[n];
     }
@@ -142,9 +131,7 @@ __global__ __launch_bounds__(REVERB_THREADS) void reverb_kernel(oasr_reverb_args
 int launch_reverb(const oasr_reverb_args* a, hipStream_t st) {
   const char* why = reverb_args_error(a);
   OASR_REQUIRE(!why, "oasr_reverb: %s", why);
-  const size_t need = reverb_workspace_bytes(a->R, a->K);
-  OASR_REQUIRE(a->workspace && ((uintptr_t)a->workspace & 15) == 0 && a->workspace_bytes >= need,
-               "oasr_reverb: workspace null, not 16-byte aligned or below oasr_reverb_workspace_bytes (%zu < %zu bytes)", a->workspace_bytes, need);
+  OASR_REQUIRE_WORKSPACE(a, 16, reverb_workspace_bytes(a->R, a->K), "oasr_reverb", "oasr_reverb_workspace_bytes");
   const int NS = reverb_ksteps(a->K);
   static_assert(REVERB_MAX_K == 8192 && REVERB_MAX_KSTEPS == ((8192 + 14) / 16 + 1 + 3) / 4, "REVERB_MAX_KSTEPS is reverb_ksteps(REVERB_MAX_K)");
   hipLaunchKernelGGL(reverb_expand_kernel, dim3((unsigned)NS + 1, (unsigned)a->R), dim3(64), 0, st, *a, NS);

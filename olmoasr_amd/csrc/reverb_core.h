@@ -3,21 +3,19 @@
 // HIP header is needed to include this file.
 //
 // The operator is an integer function of its input: int16 samples, Q15 int16 taps clamped to +-32639, an exact sum below 2^44, one rounding
-// shift per sample.  What a clip draws is a pure function of (seed, clip stream id, prob_q16, R), from the stream of hashes SpecAugment draws
-// its masks from (specaug_core.h), under a kind of its own.
+// shift per sample (pcm_round_q15).  What a clip draws is a pure function of (seed, clip stream id, prob_q16, R), from the clip's stream
+// (draw_core.h) under the kind DRAW_REVERB.  The PCM row contract is pcm_core.h's.
 //
 // The device evaluates the sum on the matrix cores from signed BYTE digits of both operands (reverb_tap_lo / _hi, reverb_x_hi / _lo and
 // reverb_combine below are that identity; the host check holds it to the plain product over every tap against the extremes of x).
 #pragma once
 #include <stdint.h>
 
-#include "specaug_core.h"
+#include "draw_core.h"
+#include "pcm_core.h"
 
-#define REVERB_MAX_N (1 << 26)
-#define REVERB_MAX_ROWS 65535  // B and R
 #define REVERB_MAX_K 8192      // 0.512 s at 16 kHz: |S| <= 8192 * 32639 * 32768 < 2^44
 #define REVERB_TAP_MAX 32639   // 127 * 256 + 127: both byte digits of a clamped tap fit a signed byte
-enum { REVERB_KIND = 5 };      // SpecAugment's masks use kinds 1 and 2 of the same hash stream, speed perturbation 3, noise mixing 4
 
 struct ReverbPlan {
   bool drawn;  // the clip is reverberated (if its n_valid lies in [1, N])
@@ -25,39 +23,31 @@ struct ReverbPlan {
 };
 
 // what a clip draws (include/oasr.h: "Draws per clip"); 1 <= R, prob_q16 in [0, 65536]
-SPECAUG_HD ReverbPlan reverb_plan(uint64_t seed, uint64_t clip, int prob_q16, int R) {
-  const uint64_t h = specaug_clip_hash(seed, clip), t = (uint64_t)REVERB_KIND << 16;
+OASR_HD ReverbPlan reverb_plan(uint64_t seed, uint64_t clip, int prob_q16, int R) {
+  const uint64_t h = draw_clip_hash(seed, clip);
   ReverbPlan pl;
-  pl.drawn = specaug_mix(h ^ t) % 65536u < (uint64_t)prob_q16;
-  pl.r = (int)(specaug_mix(h ^ (t | 1)) % (uint64_t)R);
+  pl.drawn = draw_chance(h, DRAW_REVERB, 0, prob_q16);
+  pl.r = draw_below(h, DRAW_REVERB, 1, R);
   return pl;
 }
 
 // the contract's two clamps: they make the rule total over whatever the bank's memory holds
-SPECAUG_HD int reverb_tap(int raw) { return raw < -REVERB_TAP_MAX ? -REVERB_TAP_MAX : raw > REVERB_TAP_MAX ? REVERB_TAP_MAX : raw; }
-SPECAUG_HD int reverb_delay(int raw, int K) { return raw < 0 ? 0 : raw > K - 1 ? K - 1 : raw; }
-
-// y = clamp((S + 2^14) >> 15) (an arithmetic shift: floor)
-SPECAUG_HD int16_t reverb_round(int64_t S) {
-  int64_t y = (S + 16384) >> 15;
-  y = y < -32768 ? -32768 : y;
-  y = y > 32767 ? 32767 : y;
-  return (int16_t)y;
-}
+OASR_HD int reverb_tap(int raw) { return raw < -REVERB_TAP_MAX ? -REVERB_TAP_MAX : raw > REVERB_TAP_MAX ? REVERB_TAP_MAX : raw; }
+OASR_HD int reverb_delay(int raw, int K) { return raw < 0 ? 0 : raw > K - 1 ? K - 1 : raw; }
 
 // the byte digits: tap = 256 hi + lo with both in [-127, 127] (|tap| <= 32639);  x = 256 hi + lo + 128 with both in [-128, 127]
-SPECAUG_HD int reverb_tap_lo(int tap) { return ((tap + 128) & 255) - 128; }
-SPECAUG_HD int reverb_tap_hi(int tap) { return (tap - reverb_tap_lo(tap)) >> 8; }
-SPECAUG_HD int reverb_x_hi(int x) { return x >> 8; }
-SPECAUG_HD int reverb_x_lo(int x) { return (x & 255) - 128; }
+OASR_HD int reverb_tap_lo(int tap) { return ((tap + 128) & 255) - 128; }
+OASR_HD int reverb_tap_hi(int tap) { return (tap - reverb_tap_lo(tap)) >> 8; }
+OASR_HD int reverb_x_hi(int x) { return x >> 8; }
+OASR_HD int reverb_x_lo(int x) { return (x & 255) - 128; }
 // S from the digit products p_hh = sum hi(tap) hi(x), p_mid = sum lo(tap) hi(x) + hi(tap) lo(x), p_ll = sum lo(tap) lo(x) (each below 2^29 in
 // magnitude at K = 8192) and tap_sum = sum tap
-SPECAUG_HD int64_t reverb_combine(int32_t p_hh, int32_t p_mid, int32_t p_ll, int64_t tap_sum) {
+OASR_HD int64_t reverb_combine(int32_t p_hh, int32_t p_mid, int32_t p_ll, int64_t tap_sum) {
   return (int64_t)p_hh * 65536 + (int64_t)p_mid * 256 + (int64_t)p_ll + 128 * tap_sum;
 }
 
 // one output sample, the rule as written: S[n] = sum_k tap(k) x(n + d - k), x = 0 outside [0, n_valid); 0 <= n < n_valid <= N, d clamped
-SPECAUG_HD int64_t reverb_sum(const int16_t* x, int n_valid, const int16_t* taps, int K, int d, int n) {
+OASR_HD int64_t reverb_sum(const int16_t* x, int n_valid, const int16_t* taps, int K, int d, int n) {
   // 0 <= n + d - k < n_valid  <=>  n + d - n_valid < k <= n + d
   const int k_lo = n + d - n_valid + 1 > 0 ? n + d - n_valid + 1 : 0, k_hi = n + d < K - 1 ? n + d : K - 1;
   int64_t S = 0;
@@ -69,21 +59,13 @@ SPECAUG_HD int64_t reverb_sum(const int16_t* x, int n_valid, const int16_t* taps
 // oasr_reverb_args; a template so that this file needs no include/oasr.h)
 template <class A>
 inline const char* reverb_args_error(const A* a) {
-  if (!a) return "null argument block";
+  if (const char* why = pcm_args_error(a, false, &A::rir)) return why;
   if (!a->pcm_in || !a->pcm_out || !a->n_valid || !a->rir || !a->delay) return "null pcm_in, pcm_out, n_valid, rir or delay";
-  if (a->B < 1 || a->B > REVERB_MAX_ROWS) return "B outside [1, 65535]";
-  if (a->N < 1 || a->N > REVERB_MAX_N) return "N outside [1, 2^26]";
-  if (a->R < 1 || a->R > REVERB_MAX_ROWS) return "R outside [1, 65535]";
+  if (a->R < 1 || a->R > PCM_MAX_ROWS) return "R outside [1, 65535]";
   if (a->K < 1 || a->K > REVERB_MAX_K) return "K outside [1, 8192]";
-  if (a->ld_in < a->N || a->ld_out < a->N) return "a PCM row stride below N";
   if (a->ld_rir < a->K) return "a bank row stride below K";
-  if (((uintptr_t)a->pcm_in | (uintptr_t)a->pcm_out | (uintptr_t)a->rir) & 1) return "PCM or bank that is not 2-byte aligned";
   if (((uintptr_t)a->n_valid | (uintptr_t)a->delay | (uintptr_t)a->row_out) & 3) return "an int32 operand that is not 4-byte aligned";
-  const uintptr_t in0 = (uintptr_t)a->pcm_in, in1 = in0 + 2 * ((uintptr_t)(a->B - 1) * (uintptr_t)a->ld_in + (uintptr_t)a->N);
-  const uintptr_t out0 = (uintptr_t)a->pcm_out, out1 = out0 + 2 * ((uintptr_t)(a->B - 1) * (uintptr_t)a->ld_out + (uintptr_t)a->N);
-  const uintptr_t rir0 = (uintptr_t)a->rir, rir1 = rir0 + 2 * ((uintptr_t)(a->R - 1) * (uintptr_t)a->ld_rir + (uintptr_t)a->K);
-  if (in0 < out1 && out0 < in1) return "pcm_in and pcm_out overlap (the operator works out of place)";
-  if (rir0 < out1 && out0 < rir1) return "rir and pcm_out overlap";
+  if (pcm_overlaps_out(a, a->rir, a->R, a->K, a->ld_rir)) return "rir and pcm_out overlap";
   if (a->policy.prob_q16 < 0 || a->policy.prob_q16 > 65536) return "prob_q16 outside [0, 65536]";
   return nullptr;
 }

@@ -2,8 +2,6 @@
 // same text (reverb_core.h).  Plain C++ (no HIP, no GPU call), so it serves where there is no device and builds alone under a host sanitizer
 // (tools/reverb_host_check.cpp).  It evaluates the sum as the rule writes it, tap by sample in 64-bit integers: the byte digits are the
 // device's way to the same number.
-#include <string.h>
-
 #include "../../include/oasr.h"
 #include "reverb_core.h"
 
@@ -14,7 +12,7 @@ extern "C" int oasr_reverb_plan(const struct oasr_reverb* p, uint64_t seed, uint
     oasr_set_error("oasr_reverb_plan: %s", p ? "prob_q16 outside [0, 65536]" : "null policy");
     return OASR_EINVAL;
   }
-  if (R < 1 || R > REVERB_MAX_ROWS) {
+  if (R < 1 || R > PCM_MAX_ROWS) {
     oasr_set_error("oasr_reverb_plan: R = %d outside [1, 65535]", R);
     return OASR_EINVAL;
   }
@@ -38,13 +36,13 @@ extern "C" int oasr_reverb_host(const oasr_reverb_args* a) {
     const bool wet = pl.drawn && nv >= 1 && nv <= a->N;
     if (a->row_out) a->row_out[b] = wet ? pl.r : -1;
     if (!wet) {
-      memcpy(y, x, sizeof(int16_t) * (size_t)a->N);
+      pcm_copy_row(y, x, 0, a->N);
       continue;
     }
     const int16_t* taps = a->rir + (size_t)pl.r * (size_t)a->ld_rir;
     const int d = reverb_delay(a->delay[pl.r], a->K);
-    for (int n = 0; n < nv; ++n) y[n] = reverb_round(reverb_sum(x, nv, taps, a->K, d, n));
-    memcpy(y + nv, x + nv, sizeof(int16_t) * (size_t)(a->N - nv));
+    for (int n = 0; n < nv; ++n) y[n] = pcm_round_q15(reverb_sum(x, nv, taps, a->K, d, n));
+    pcm_copy_row(y, x, nv, a->N);
   }
   return OASR_OK;
 }

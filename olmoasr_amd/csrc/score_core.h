@@ -11,19 +11,15 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define SC_HD __host__ __device__ __forceinline__
-#else
-#define SC_HD inline
-#endif
+#include "core_hd.h"
 
 // the validity rule of ce_kernel and count_valid_kernel (loss.hip): an id outside [0, V) counts as ignored
-SC_HD bool sc_valid(int64_t t, int V, int64_t ignore) { return t != ignore && t >= 0 && t < (int64_t)V; }
+OASR_HD bool sc_valid(int64_t t, int V, int64_t ignore) { return t != ignore && t >= 0 && t < (int64_t)V; }
 
 #define SC_COUNTED 1u
 #define SC_HIT 2u
 // what a row adds: bit 0 = counted, bit 1 = counted and predicted right (the caller has already tested s against the span)
-SC_HD uint32_t sc_flags(int64_t t, int32_t pred, int V, int64_t ignore) {
+OASR_HD uint32_t sc_flags(int64_t t, int32_t pred, int V, int64_t ignore) {
   if (!sc_valid(t, V, ignore)) return 0u;
   return SC_COUNTED | ((int64_t)pred == t ? SC_HIT : 0u);
 }
@@ -33,23 +29,23 @@ struct ScoreAcc {
   float mx;
   int32_t n_tok, n_hit;
 };
-SC_HD void sc_init(ScoreAcc& a) { a.sum = 0.0, a.mx = 0.f, a.n_tok = 0, a.n_hit = 0; }
+OASR_HD void sc_init(ScoreAcc& a) { a.sum = 0.0, a.mx = 0.f, a.n_tok = 0, a.n_hit = 0; }
 // one row, in ascending s
-SC_HD void sc_add(ScoreAcc& a, float nll, uint32_t flags) {
+OASR_HD void sc_add(ScoreAcc& a, float nll, uint32_t flags) {
   if (!(flags & SC_COUNTED)) return;
   a.sum += (double)nll;
   if (a.n_tok == 0 || nll > a.mx) a.mx = nll;
   a.n_tok += 1;
   a.n_hit += (flags & SC_HIT) ? 1 : 0;
 }
-SC_HD void sc_finish(const ScoreAcc& a, float* nll_sum, float* nll_max, int32_t* n_tok, int32_t* n_hit) {
+OASR_HD void sc_finish(const ScoreAcc& a, float* nll_sum, float* nll_max, int32_t* n_tok, int32_t* n_hit) {
   *nll_sum = (float)a.sum;
   *nll_max = a.n_tok ? a.mx : 0.f;
   *n_tok = a.n_tok;
   *n_hit = a.n_hit;
 }
 // rows of sample b that can count: span clipped to [0, S]
-SC_HD int sc_rows(int32_t span, int S) { return span < 0 ? 0 : (span > S ? S : span); }
+OASR_HD int sc_rows(int32_t span, int S) { return span < 0 ? 0 : (span > S ? S : span); }
 
 // what both reduce entries refuse; null = fine
 inline const char* sc_reduce_args_error(const void* row_nll, const void* pred, const void* targets, const void* span, int B, int S, int V,

@@ -1,8 +1,9 @@
 // SpecAugment on the finalized log-mel tensor (include/oasr.h at oasr_spec_augment): seeded frequency / time masks, in place, one launch.
 //
 // One 256-thread workgroup per (clip, mel bin) row of mel f32 [B, n_mels, T].  Its first freq_masks + time_masks threads each derive one
-// interval of the clip from the hashes of specaug_core.h (64-bit integer VALU math; the two 64-bit remainders per interval are the only
-// expensive instructions and run once per workgroup, not per element) and leave it in LDS.  A row whose bin lies in a frequency mask is
+// interval of the clip by the rule of specaug_core.h from the clip's draw stream, draw_core.h (64-bit integer VALU math; the two 64-bit
+// remainders per interval are the only expensive instructions and run once per workgroup, not per element) and leave it in LDS.  A row
+// whose bin lies in a frequency mask is
 // filled as a whole; any other row gets only its time intervals.  The kernel never loads from mel and stores to masked cells only, so every
 // other cell keeps its bits.  There is no mask tensor and nothing comes from the host but the policy, the seed and the first stream id.
 #include "common.h"
@@ -34,12 +35,12 @@ __global__ __launch_bounds__(SPECAUG_THREADS) void spec_augment_kernel(float* __
   const int b = blockIdx.x / n_mels, bin = blockIdx.x - b * n_mels;
   const int nf = pol.freq_masks, nt = pol.time_masks;
   if (tid < nf + nt) {
-    const uint64_t h = specaug_clip_hash(seed, first_clip + (uint64_t)b);
+    const uint64_t h = draw_clip_hash(seed, first_clip + (uint64_t)b);
     int start, width;
     if (tid < nf)
-      specaug_interval(h, SPECAUG_FREQ, tid, pol.freq_width, n_mels, &start, &width);
+      specaug_interval(h, DRAW_FREQ_MASK, tid, pol.freq_width, n_mels, &start, &width);
     else
-      specaug_interval(h, SPECAUG_TIME, tid - nf, pol.time_width, T, &start, &width);
+      specaug_interval(h, DRAW_TIME_MASK, tid - nf, pol.time_width, T, &start, &width);
     s_start[tid] = start, s_width[tid] = width;
   }
   __syncthreads();

@@ -24,15 +24,15 @@ extern "C" int oasr_spec_augment_plan(const oasr_specaug* p, uint64_t seed, uint
     oasr_set_error("oasr_spec_augment_plan: n_mels = %d and T = %d must be >= 1", n_mels, T);
     return OASR_EINVAL;
   }
-  const uint64_t h = specaug_clip_hash(seed, clip);
+  const uint64_t h = draw_clip_hash(seed, clip);
   for (int i = 0; i < p->freq_masks; ++i) {
     int start, width;
-    specaug_interval(h, SPECAUG_FREQ, i, p->freq_width, n_mels, &start, &width);
+    specaug_interval(h, DRAW_FREQ_MASK, i, p->freq_width, n_mels, &start, &width);
     freq_iv[2 * i] = start, freq_iv[2 * i + 1] = width;
   }
   for (int i = 0; i < p->time_masks; ++i) {
     int start, width;
-    specaug_interval(h, SPECAUG_TIME, i, p->time_width, T, &start, &width);
+    specaug_interval(h, DRAW_TIME_MASK, i, p->time_width, T, &start, &width);
     time_iv[2 * i] = start, time_iv[2 * i + 1] = width;
   }
   return OASR_OK;

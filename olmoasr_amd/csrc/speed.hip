@@ -2,9 +2,9 @@
 // of place, with the transcript's timestamp tokens moved along -- one launch.
 //
 // One 256-thread workgroup owns SPEED_TILE = 2048 consecutive output samples of one clip.  Every workgroup evaluates the clip's plan itself
-// from (seed, clip, n_valid) -- three hashes and one 64-bit remainder of scalar work -- so nothing comes back to the host.  Tiles are laid on
-// the 16-byte grid of the OUTPUT row's address (a row may start at any even address), so each thread's 8 samples leave as one aligned
-// 16-byte store; only the row's first and last few samples go out one by one.
+// from (seed, clip, n_valid) -- three hashes and one 64-bit remainder of scalar work (draw_core.h) -- so nothing comes back to the host.
+// Tiles are laid on the 16-byte grid of the output row (pcm_tile.h), so each thread's 8 samples leave as one aligned 16-byte store.  The two
+// staging loads below stay explicit ALIGNED loads on the input row's own grid rather than pcm_load8: that choice was measured.
 //   identity row   a vector copy of the whole row
 //   tile >= n_out  zeros are stored, nothing is read
 //   otherwise      the ratio's Q x 2H table (row stride 2H + 1 words: the 32 lanes of a ds_read_b32 group hold consecutive n, hence
@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "../../include/oasr.h"
 #include "speed_core.h"
+#include "pcm_tile.h"
 
 static_assert(OASR_SPEED_MAX_FACTORS == SPEED_MAX_FACTORS, "include/oasr.h and speed_core.h disagree");
 
@@ -42,17 +43,6 @@ struct SpeedTables {  // device copies of the policy's tables (nullptr / 0 for a
   int32_t H[SPEED_MAX_FACTORS];
 };
 
-// samples [n0, n0 + 8) of a row as one aligned 16-byte store where all eight exist, else one by one (y + n0 is 16-byte aligned)
-__device__ __forceinline__ void speed_store8(int16_t* __restrict__ y, int n0, int N, s16x8_t v) {
-  if (n0 >= 0 && n0 + 8 <= N) {
-    *(s16x8_t*)(y + n0) = v;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (n0 + e >= 0 && n0 + e < N) y[n0 + e] = v[e];
-  }
-}
-
 __global__ __launch_bounds__(SPEED_THREADS) void speed_perturb_kernel(oasr_speed_args a, SpeedTables tabs) {
   __shared__ __attribute__((aligned(16))) int32_t s_x[SPEED_XBUF];
   __shared__ __attribute__((aligned(16))) int16_t s_y[SPEED_TILE];
@@ -69,7 +59,7 @@ __global__ __launch_bounds__(SPEED_THREADS) void speed_perturb_kernel(oasr_speed
   P = pl.P, Q = pl.Q;
   const int16_t* __restrict__ x = a.pcm_in + (size_t)b * (size_t)a.ld_in;
   int16_t* __restrict__ y = a.pcm_out + (size_t)b * (size_t)a.ld_out;
-  const int lead = (int)(((uintptr_t)y >> 1) & 7);      // samples between the 16-byte boundary at or before y and y
+  const int lead = pcm_lead(y);
   const int n_lo = (int)blockIdx.x * SPEED_TILE - lead;  // the tile covers [n_lo, n_lo + TILE) of the row; y + n_lo is 16-byte aligned
   if (n_lo >= N) return;
   const int n_hi = n_lo + SPEED_TILE < N ? n_lo + SPEED_TILE : N;
@@ -98,7 +88,7 @@ __global__ __launch_bounds__(SPEED_THREADS) void speed_perturb_kernel(oasr_speed
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (n0 + e >= 0 && n0 + e < N) ? x[n0 + e] : (int16_t)0;
     }
-    speed_store8(y, n0, N, v);
+    pcm_store8(y, n0, N, v);
     return;
   }
 
@@ -106,7 +96,7 @@ __global__ __launch_bounds__(SPEED_THREADS) void speed_perturb_kernel(oasr_speed
   const int n_end = n_hi < pl.n_out ? n_hi : pl.n_out;  // samples [n_beg, n_end) of the tile carry audio
   if (n_beg >= n_end) {                                 // at or past n_out: zeros, and nothing is read
     const s16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-    speed_store8(y, n0, N, z);
+    pcm_store8(y, n0, N, z);
     return;
   }
 
@@ -118,7 +108,7 @@ __global__ __launch_bounds__(SPEED_THREADS) void speed_perturb_kernel(oasr_speed
   // the window [w0, w1] of the input that the tile's samples read, staged from the 16-byte boundary g0 at or before w0
   const int m_first = (int)(((int64_t)n_beg * P) / Q), m_last = (int)(((int64_t)(n_end - 1) * P) / Q);
   const int w0 = m_first - H + 1, w1 = m_last + H;
-  const int in_lead = (int)(((uintptr_t)x >> 1) & 7);
+  const int in_lead = pcm_lead(x);
   const int g0 = w0 - ((w0 + in_lead) & 7);
   const int n_vec = (w1 - g0 + 8) >> 3;  // <= SPEED_XBUF / 8 (the static_assert above)
   for (int v = tid; v < n_vec; v += SPEED_THREADS) {
@@ -150,14 +140,14 @@ __global__ __launch_bounds__(SPEED_THREADS) void speed_perturb_kernel(oasr_speed
       const int32_t* ts = s_T + r * tstride;
       int64_t acc = 0;
       for (int j = 0; j < taps; ++j) acc += (int64_t)xs[j] * ts[j];
-      out = speed_round(acc);
+      out = pcm_round_q15(acc);
     }
     s_y[v] = out;
     m += dm, r += dr;
     if (r >= Q) r -= Q, ++m;
   }
   __syncthreads();
-  speed_store8(y, n0, N, *(const s16x8_t*)(s_y + SPEED_PER_THREAD * tid));
+  pcm_store8(y, n0, N, *(const s16x8_t*)(s_y + SPEED_PER_THREAD * tid));
 }
 
 // the device copy of a ratio's table on the current device: uploaded on first use (like the log-mel tables), kept for the process

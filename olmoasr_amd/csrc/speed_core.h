@@ -4,22 +4,22 @@
 //
 // The operator is an integer function of its input: int16 samples, Q15 integer taps that sum to 2^15 per phase, an exact 64-bit sum, one
 // rounding shift.  Floating point (double) enters only where the HOST builds a (P, Q) tap table, once; the kernel and the host twin read
-// the same integers.  The factor a clip takes is a pure function of (seed, clip stream id, policy, n_valid, N), drawn from the stream of
-// hashes SpecAugment draws its masks from (specaug_core.h), under a kind of its own.
+// the same integers.  The factor a clip takes is a pure function of (seed, clip stream id, policy, n_valid, N), drawn from the clip's
+// stream (draw_core.h) under the kind DRAW_SPEED.  The PCM row contract is pcm_core.h's.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
-#include "specaug_core.h"
+#include "draw_core.h"
+#include "pcm_core.h"
 
 #define SPEED_MAX_FACTORS 8  // == OASR_SPEED_MAX_FACTORS (include/oasr.h)
 #define SPEED_MAX_PQ 32      // 1 <= P, Q <= 32
 #define SPEED_MAX_H 34       // H = floor(16 / fc) + 1 with fc >= 0.95 / 2 (P <= 2 Q)
-#define SPEED_MAX_N (1 << 26)  // n * P and n_valid * Q stay below 2^31
-enum { SPEED_KIND = 3 };     // SpecAugment's masks use kinds 1 and 2 of the same hash stream
+static_assert((int64_t)PCM_MAX_N * SPEED_MAX_PQ <= (int64_t)1 << 31, "n * P and n_valid * Q stay below 2^31");
 
 // what is wrong with a policy, or nullptr
-SPECAUG_HD const char* speed_policy_error(int n_factors, const int32_t* P, const int32_t* Q) {
+OASR_HD const char* speed_policy_error(int n_factors, const int32_t* P, const int32_t* Q) {
   if (n_factors < 1 || n_factors > SPEED_MAX_FACTORS) return "n_factors outside [1, OASR_SPEED_MAX_FACTORS (8)]";
   for (int i = 0; i < n_factors; ++i) {
     const int p = P[i], q = Q[i];
@@ -43,13 +43,12 @@ struct SpeedPlan {
 };
 
 // the index of the factor a clip draws (include/oasr.h: "Choice per clip")
-SPECAUG_HD int speed_choice(uint64_t seed, uint64_t clip, int n_factors) {
-  const uint64_t h = specaug_clip_hash(seed, clip);
-  return (int)(specaug_mix(h ^ ((uint64_t)SPEED_KIND << 16)) % (uint64_t)n_factors);
+OASR_HD int speed_choice(uint64_t seed, uint64_t clip, int n_factors) {
+  return draw_below(draw_clip_hash(seed, clip), DRAW_SPEED, 0, n_factors);
 }
 
 // the plan of a clip that drew factor i = P / Q
-SPECAUG_HD SpeedPlan speed_plan_of(int i, int P, int Q, int n_valid, int N) {
+OASR_HD SpeedPlan speed_plan_of(int i, int P, int Q, int n_valid, int N) {
   SpeedPlan pl;
   if (n_valid < 0 || n_valid > N) {
     pl.P = pl.Q = 1, pl.factor = -1, pl.valid = false;
@@ -66,21 +65,13 @@ SPECAUG_HD SpeedPlan speed_plan_of(int i, int P, int Q, int n_valid, int N) {
   return pl;
 }
 
-SPECAUG_HD SpeedPlan speed_plan(int n_factors, const int32_t* P, const int32_t* Q, uint64_t seed, uint64_t clip, int n_valid, int N) {
+OASR_HD SpeedPlan speed_plan(int n_factors, const int32_t* P, const int32_t* Q, uint64_t seed, uint64_t clip, int n_valid, int N) {
   const int i = speed_choice(seed, clip, n_factors);
   return speed_plan_of(i, P[i], Q[i], n_valid, N);
 }
 
-// y = clamp((acc + 2^14) >> 15) of the exact sum (an arithmetic shift: floor)
-SPECAUG_HD int16_t speed_round(int64_t acc) {
-  int64_t v = (acc + 16384) >> 15;
-  v = v < -32768 ? -32768 : v;
-  v = v > 32767 ? 32767 : v;
-  return (int16_t)v;
-}
-
 // a timestamp token under the ratio P / Q; every other token as it is
-SPECAUG_HD int64_t speed_token(int64_t t, int64_t ts_begin, int64_t ts_max, int P, int Q) {
+OASR_HD int64_t speed_token(int64_t t, int64_t ts_begin, int64_t ts_max, int P, int Q) {
   if (t < ts_begin || t > ts_begin + ts_max) return t;
   const int64_t k = (2 * (t - ts_begin) * Q + P) / (2 * P);
   return ts_begin + (k < ts_max ? k : ts_max);
@@ -126,16 +117,9 @@ const int32_t* speed_table_cached(int P, int Q, int* H);
 // file needs no include/oasr.h)
 template <class A>
 inline const char* speed_args_error(const A* a) {
-  if (!a) return "null argument block";
+  if (const char* why = pcm_args_error(a, false)) return why;
   if (!a->pcm_in || !a->pcm_out || !a->n_valid) return "null pcm_in, pcm_out or n_valid";
-  if (a->B < 1 || a->B > 65535) return "B outside [1, 65535]";
-  if (a->N < 1 || a->N > SPEED_MAX_N) return "N outside [1, 2^26]";
-  if (a->ld_in < a->N || a->ld_out < a->N) return "a PCM row stride below N";
-  if (((uintptr_t)a->pcm_in | (uintptr_t)a->pcm_out) & 1) return "PCM that is not 2-byte aligned";
   if (((uintptr_t)a->n_valid | (uintptr_t)a->n_out | (uintptr_t)a->factor_out) & 3) return "an int32 operand that is not 4-byte aligned";
-  const uintptr_t in0 = (uintptr_t)a->pcm_in, in1 = in0 + 2 * ((uintptr_t)(a->B - 1) * (uintptr_t)a->ld_in + (uintptr_t)a->N);
-  const uintptr_t out0 = (uintptr_t)a->pcm_out, out1 = out0 + 2 * ((uintptr_t)(a->B - 1) * (uintptr_t)a->ld_out + (uintptr_t)a->N);
-  if (in0 < out1 && out0 < in1) return "pcm_in and pcm_out overlap (the operator works out of place)";
   if (a->tokens_a || a->tokens_b) {
     if (a->S < 1) return "tokens with S < 1";
     if ((a->tokens_a && a->ld_tokens_a < a->S) || (a->tokens_b && a->ld_tokens_b < a->S)) return "a token row stride below S";
@@ -146,7 +130,7 @@ inline const char* speed_args_error(const A* a) {
 }
 
 // one output sample of a resampled row (include/oasr.h: "Sample"): x zero outside [0, n_valid), T the ratio's table
-SPECAUG_HD int16_t speed_sample(const int16_t* x, int n_valid, const int32_t* T, int H, int P, int Q, int n) {
+OASR_HD int16_t speed_sample(const int16_t* x, int n_valid, const int32_t* T, int H, int P, int Q, int n) {
   const int m = (int)(((int64_t)n * P) / Q), r = (int)(((int64_t)n * P) % Q);
   const int32_t* row = T + (size_t)r * 2 * H;
   int64_t acc = 0;
@@ -154,5 +138,5 @@ SPECAUG_HD int16_t speed_sample(const int16_t* x, int n_valid, const int32_t* T,
     const int i = m + j - H + 1;
     if (i >= 0 && i < n_valid) acc += (int64_t)x[i] * row[j];
   }
-  return speed_round(acc);
+  return pcm_round_q15(acc);
 }

@@ -52,7 +52,7 @@ extern "C" int oasr_speed_plan(const oasr_speed* p, uint64_t seed, uint64_t clip
     oasr_set_error("oasr_speed_plan: %s", why);
     return OASR_EINVAL;
   }
-  if (N < 1 || N > SPEED_MAX_N || n_valid < 0 || n_valid > N) {
+  if (N < 1 || N > PCM_MAX_N || n_valid < 0 || n_valid > N) {
     oasr_set_error("oasr_speed_plan: N = %d outside [1, 2^26] or n_valid = %d outside [0, N]", N, n_valid);
     return OASR_EINVAL;
   }
@@ -82,7 +82,7 @@ extern "C" int oasr_speed_perturb_host(const oasr_speed_args* a) {
     if (a->n_out) a->n_out[b] = pl.n_out;
     if (a->factor_out) a->factor_out[b] = pl.factor;
     if (pl.P == pl.Q) {
-      memcpy(y, x, sizeof(int16_t) * (size_t)a->N);
+      pcm_copy_row(y, x, 0, a->N);
       continue;
     }
     int H = 0;

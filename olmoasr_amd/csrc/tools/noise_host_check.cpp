@@ -4,30 +4,13 @@
 // in heap buffers of exactly the size the call may touch (the sanitizer guards their ends), out of place and in place, holds the 61
 // amplitudes to their defining inequality in integers, checks known answers and the extremes of the gain, and checks that bad arguments
 // are refused before anything is written.  Exit status 0 = everything agreed.
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <vector>
 
 #include "../../../include/oasr.h"
+#include "host_check.h"
 #include "../noise_core.h"
-
-void oasr_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-
-static uint64_t mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 static uint64_t newton_isqrt(uint64_t v) {  // floor(sqrt(v)) for v < 2^63, by Newton's iteration from above
   if (v < 2) return v;
@@ -35,9 +18,6 @@ static uint64_t newton_isqrt(uint64_t v) {  // floor(sqrt(v)) for v < 2^63, by N
   while ((q = (r + v / r) / 2) < r) r = q;
   return r;
 }
-
-static uint64_t rng_state = 12345;
-static int16_t rnd16(int amp) { return (int16_t)((int64_t)(mix(++rng_state) % (uint64_t)(2 * amp + 1)) - amp); }
 
 struct Case {
   int B, N, M, L, ld_in, ld_out, ld_bank;
@@ -112,6 +92,7 @@ static int run(const Case& c, const std::vector<int32_t>& nv, int amp_x, int amp
 }
 
 int main() {
+  rng_state = 12345;
   int bad = 0, rows = 0, mixed = 0;
   static const int Ns[] = {1, 37, 4096, 4099}, Ls[] = {1, 7, 1000, 4099, 9000};
   static const oasr_noise pols[] = {{65536, -10, 50}, {32768, 5, 20}, {0, 0, 0}, {65536, 0, 0}, {65536, 50, 50}, {65536, -10, -10}};

@@ -5,33 +5,13 @@
 // their ends); holds the byte-digit identity the device computes by to the plain product for every tap value against the digit boundaries of
 // x; checks known answers and both sides of the clamp, and that bad arguments are refused before anything is written.  Exit status 0 =
 // everything agreed.
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <vector>
 
 #include "../../../include/oasr.h"
+#include "host_check.h"
 #include "../reverb_core.h"
-
-void oasr_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-
-static uint64_t mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-static uint64_t rng_state = 4321;
-static int16_t rnd16(int amp) { return (int16_t)((int64_t)(mix(++rng_state) % (uint64_t)(2 * amp + 1)) - amp); }
 
 struct Case {
   int B, N, R, K, ld_in, ld_out, ld_rir, prob_q16;
@@ -90,6 +70,7 @@ static int run(const Case& c, const std::vector<int32_t>& nv, int amp_x, int amp
 }
 
 int main() {
+  rng_state = 4321;
   int bad = 0, rows = 0, wet = 0;
   static const int Ns[] = {1, 37, 600, 1031}, Ks[] = {1, 15, 16, 17, 81, 300};
   static const int probs[] = {65536, 32768, 0};
@@ -126,9 +107,9 @@ int main() {
   int wrong = 0;
   wrong += reverb_tap(32767) != 32639 || reverb_tap(-32768) != -32639 || reverb_tap(32639) != 32639 || reverb_tap(-5) != -5;
   wrong += reverb_delay(-5, 100) != 0 || reverb_delay(105, 100) != 99 || reverb_delay(42, 100) != 42 || reverb_delay(3, 1) != 0;
-  wrong += reverb_round(0) != 0 || reverb_round(16383) != 0 || reverb_round(16384) != 1 || reverb_round(-16384) != 0 || reverb_round(-16385) != -1;
-  wrong += reverb_round((int64_t)8192 * 32639 * 32767) != 32767 || reverb_round(-(int64_t)8192 * 32639 * 32768) != -32768;
-  wrong += reverb_round((int64_t)32767 << 15) != 32767 || reverb_round(-((int64_t)32768 << 15)) != -32768;
+  wrong += pcm_round_q15(0) != 0 || pcm_round_q15(16383) != 0 || pcm_round_q15(16384) != 1 || pcm_round_q15(-16384) != 0 || pcm_round_q15(-16385) != -1;
+  wrong += pcm_round_q15((int64_t)8192 * 32639 * 32767) != 32767 || pcm_round_q15(-(int64_t)8192 * 32639 * 32768) != -32768;
+  wrong += pcm_round_q15((int64_t)32767 << 15) != 32767 || pcm_round_q15(-((int64_t)32768 << 15)) != -32768;
   {
     const int16_t x[4] = {100, -200, 300, -400}, taps[3] = {16384, 32767, -16384};  // 0.5, (clamped) 32639 / 32768, -0.5
     // d = 1: S[n] = taps[0] x[n + 1] + taps[1] x[n] + taps[2] x[n - 1]

@@ -2,28 +2,10 @@
 // -fsanitize=address,undefined by `make specaug-host-check`.  It compares oasr_spec_augment_plan with the rule written out again here and
 // with known answers, over a sweep of shapes, policies, seeds and stream ids, into interval lists of exactly the size the call may write
 // (the sanitizer guards their ends), and checks that bad arguments are refused.  Exit status 0 = everything agreed.
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include <memory>
 
 #include "../../../include/oasr.h"
-
-void oasr_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-
-static uint64_t mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+#include "host_check.h"
 
 // the rule of include/oasr.h for one kind, written from its text
 static void expect(uint64_t h, uint64_t kind, int n, int64_t W, int64_t L, int32_t* iv) {

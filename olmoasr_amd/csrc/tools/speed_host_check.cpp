@@ -4,29 +4,12 @@
 // buffers of exactly the size the calls may touch (the sanitizer guards their ends), and checks that bad arguments are refused before
 // anything is written.  Exit status 0 = everything agreed.
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <vector>
 
 #include "../../../include/oasr.h"
-
-void oasr_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-
-static uint64_t mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+#include "host_check.h"
 
 static uint64_t lcg(uint64_t& s) { return s = s * 6364136223846793005ull + 1442695040888963407ull; }
 

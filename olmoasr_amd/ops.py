@@ -716,7 +716,7 @@ def specaug_policy(freq_masks, freq_width, time_masks, time_width, fill=0.0):
     return N.SpecAug(freq_masks, freq_width, time_masks, time_width, float(fill))
 
 
-def _u64(name, v, who="spec_augment"):
+def _u64(name, v, who):
     if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= _U64:
         raise ValueError(f"{who}: {name} must be an integer in [0, 2^64), got {v!r}")
     return v
@@ -736,7 +736,7 @@ def spec_augment_(mel, *, freq_masks, freq_width, time_masks, time_width, fill=0
     if not mel.is_contiguous():
         raise ValueError("spec_augment: mel must be contiguous (it is modified in place; a copy would take the masks with it)")
     pol = specaug_policy(freq_masks, freq_width, time_masks, time_width, fill)
-    seed, first_clip = _u64("seed", seed), _u64("first_clip", first_clip)
+    seed, first_clip = _u64("seed", seed, "spec_augment"), _u64("first_clip", first_clip, "spec_augment")
     B = mel.shape[0] if mel.dim() == 3 else 1
     n_mels, T = mel.shape[-2:]
     if B == 0:
@@ -754,7 +754,7 @@ def spec_augment_plan(*, freq_masks, freq_width, time_masks, time_width, seed=0,
     if not (isinstance(n_mels, int) and isinstance(T, int) and 1 <= n_mels < 2 ** 31 and 1 <= T < 2 ** 31):
         raise ValueError(f"spec_augment: n_mels = {n_mels!r} and T = {T!r} must be integers in [1, 2^31)")
     f_iv, t_iv = (C.c_int32 * (2 * max(1, freq_masks)))(), (C.c_int32 * (2 * max(1, time_masks)))()
-    N.call("oasr_spec_augment_plan", C.byref(pol), _u64("seed", seed), _u64("clip", clip), n_mels, T, f_iv, t_iv)
+    N.call("oasr_spec_augment_plan", C.byref(pol), _u64("seed", seed, "spec_augment"), _u64("clip", clip, "spec_augment"), n_mels, T, f_iv, t_iv)
     return ([(f_iv[2 * i], f_iv[2 * i + 1]) for i in range(freq_masks)], [(t_iv[2 * i], t_iv[2 * i + 1]) for i in range(time_masks)])
 
 
@@ -783,39 +783,97 @@ def speed_policy(factors):
     return pol
 
 
+def _prob_q16(who, prob):
+    """``prob`` in [0, 1] as the library keeps it: round(prob * 65536), the chance of a clip to be drawn."""
+    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"{who}: prob must be a number in [0, 1], got {prob!r}")
+    return int(round(prob * 65536))
+
+
+# ---- the PCM operators (speed_perturb, noise_mix, reverb): what their operand checks and their entry points have in common -------------
+def _rows_ld(what, t, nm, pcm, cuda, dtype=torch.int16, shape=None):
+    """The row stride of ``t``: a 2-D ``dtype`` matrix (of ``shape``, if given) with unit column stride and rows that do not overlap, on
+    the device of ``pcm``."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == 2):
+        raise ValueError(f"{what}: {nm} must be a 2-D {dtype} tensor")
+    if t.is_cuda != cuda or t.device != pcm.device:
+        raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor on the device of pcm")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {nm} must be {list(shape)}, got {tuple(t.shape)}")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{what}: {nm} needs unit column stride and rows that do not overlap")
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _i32_vec(what, t, nm, n, pcm):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+            and t.device == pcm.device):
+        raise ValueError(f"{what}: {nm} must be a contiguous int32 [{n}] on the device of pcm")
+
+
+def _pcm_in(what, pcm, n_valid, cuda):
+    """Checks ``pcm`` int16 [B, N] and ``n_valid`` int32 [B]: (ld_in, B, N)."""
+    if not isinstance(pcm, torch.Tensor) or pcm.is_cuda != cuda:
+        raise ValueError(f"{what}: pcm must be a GPU tensor ({what}_host takes CPU tensors)" if cuda else f"{what}: pcm must be a CPU tensor")
+    ld_in = _rows_ld(what, pcm, "pcm", pcm, cuda)
+    B, n = pcm.shape
+    _i32_vec(what, n_valid, "n_valid", B, pcm)
+    if not 1 <= n <= N.SpeedArgs.MAX_N or B > N.NoiseArgs.MAX_ROWS:
+        raise ValueError(f"{what}: pcm [B, N] with B <= 65535 and 1 <= N <= 2^26, got {tuple(pcm.shape)}")
+    return ld_in, B, n
+
+
+def _span(t, ld):
+    """The bytes [lo, hi) of an int16 matrix with row stride ``ld``."""
+    return t.data_ptr(), t.data_ptr() + 2 * ((t.shape[0] - 1) * ld + t.shape[1])
+
+
+def _pcm_out(what, pcm, ld_in, out, cuda, in_place=False, bank=None, ld_bank=0):
+    """``out`` (allocated if None) as the int16 [B, N] result of ``pcm``: it may not overlap ``pcm`` -- unless ``in_place`` and it is
+    ``pcm`` itself -- or the ``bank``: (out, ld_out)."""
+    if out is None:
+        out = torch.empty(pcm.shape, dtype=torch.int16, device=pcm.device)
+    ld_out = _rows_ld(what, out, "out", pcm, cuda, shape=pcm.shape)
+    if pcm.shape[0]:
+        (lo_i, hi_i), (lo_o, hi_o) = _span(pcm, ld_in), _span(out, ld_out)
+        if lo_i < hi_o and lo_o < hi_i:
+            if not in_place:
+                raise ValueError(f"{what}: out overlaps pcm (the operator works out of place)")
+            if not (lo_i == lo_o and ld_in == ld_out):
+                raise ValueError(f"{what}: out overlaps pcm without being pcm itself (in place: the same tensor)")
+        if bank is not None:
+            lo_b, hi_b = _span(bank, ld_bank)
+            if lo_b < hi_o and lo_o < hi_b:
+                raise ValueError(f"{what}: out overlaps the bank")
+    return out, ld_out
+
+
+def _pcm_call(entry, a, pcm, cuda, workspace_bytes=None):
+    """Runs ``oasr_<entry>`` on the current stream, or ``oasr_<entry>_host``, on a checked block; an empty batch calls nothing."""
+    if not a.B:
+        return
+    if not cuda:
+        N.call(f"oasr_{entry}_host", C.byref(a))
+        return
+    if workspace_bytes is not None:
+        ws = _workspace(entry, pcm.device, workspace_bytes())
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    N.call(f"oasr_{entry}", C.byref(a), N.STREAM, device=pcm.device)
+
+
 def _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_max, out, cuda):
     """Checks and converts the operands of ``speed_perturb`` / ``speed_perturb_host``: (SpeedArgs, pcm_out, n_out, factor, keep-alive)."""
     what = "speed_perturb" if cuda else "speed_perturb_host"
     tokens = tuple(tokens)
     if len(tokens) > 2:
         raise ValueError(f"{what}: at most two token tensors, got {len(tokens)}")
-
-    def rows(t, nm, dtype, width=None):
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == 2):
-            raise ValueError(f"{what}: {nm} must be a 2-D {dtype} tensor")
-        if t.is_cuda != cuda or t.device != pcm.device:
-            raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor on the device of pcm")
-        if width is not None and tuple(t.shape) != (pcm.shape[0], width):
-            raise ValueError(f"{what}: {nm} must be [{pcm.shape[0]}, {width}], got {tuple(t.shape)}")
-        if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-            raise ValueError(f"{what}: {nm} needs unit column stride and rows that do not overlap")
-        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
-
-    if not isinstance(pcm, torch.Tensor):
-        raise ValueError(f"{what}: pcm must be a 2-D torch.int16 tensor")
-    ld_in = rows(pcm, "pcm", torch.int16)
-    B, n = pcm.shape
-    if not (isinstance(n_valid, torch.Tensor) and n_valid.dtype == torch.int32 and n_valid.dim() == 1 and n_valid.numel() == B
-            and n_valid.is_contiguous() and n_valid.device == pcm.device):
-        raise ValueError(f"{what}: n_valid must be a contiguous int32 [{B}] on the device of pcm")
-    if not 1 <= n <= N.SpeedArgs.MAX_N or B > 65535:
-        raise ValueError(f"{what}: pcm [B, N] with B <= 65535 and 1 <= N <= 2^26, got {tuple(pcm.shape)}")
+    ld_in, B, n = _pcm_in(what, pcm, n_valid, cuda)
     a = N.SpeedArgs()
     a.policy = speed_policy(factors)
     a.seed, a.first_clip = _u64("seed", seed, what), _u64("first_clip", first_clip, what)
     if tokens:
         S = tokens[0].shape[1] if isinstance(tokens[0], torch.Tensor) and tokens[0].dim() == 2 else 0
-        lds = [rows(t, f"tokens[{i}]", torch.int64, S) for i, t in enumerate(tokens)]
+        lds = [_rows_ld(what, t, f"tokens[{i}]", pcm, cuda, torch.int64, (B, S)) for i, t in enumerate(tokens)]
         if S < 1:
             raise ValueError(f"{what}: tokens must be [B, S] with S >= 1")
         for nm, v, hi in (("ts_begin", ts_begin, 2 ** 31 - 1), ("ts_max", ts_max, 1 << 24)):
@@ -825,14 +883,7 @@ def _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_ma
         a.tokens_a, a.ld_tokens_a = tokens[0].data_ptr(), lds[0]
         if len(tokens) == 2:
             a.tokens_b, a.ld_tokens_b = tokens[1].data_ptr(), lds[1]
-    if out is None:
-        out = torch.empty(B, n, dtype=torch.int16, device=pcm.device)
-    ld_out = rows(out, "out", torch.int16, n)
-    if B:
-        lo_i, lo_o = pcm.data_ptr(), out.data_ptr()
-        hi_i, hi_o = lo_i + 2 * ((B - 1) * ld_in + n), lo_o + 2 * ((B - 1) * ld_out + n)
-        if lo_i < hi_o and lo_o < hi_i:
-            raise ValueError(f"{what}: out overlaps pcm (the operator works out of place)")
+    out, ld_out = _pcm_out(what, pcm, ld_in, out, cuda)
     n_out = torch.empty(B, dtype=torch.int32, device=pcm.device)
     factor = torch.empty(B, dtype=torch.int32, device=pcm.device)
     a.pcm_in, a.pcm_out, a.n_valid, a.n_out, a.factor_out = pcm.data_ptr(), out.data_ptr(), n_valid.data_ptr(), n_out.data_ptr(), factor.data_ptr()
@@ -849,24 +900,18 @@ def speed_perturb(pcm, n_valid, *, factors, seed=0, first_clip=0, tokens=(), ts_
     ``ts_begin .. ts_begin + ts_max`` are rescaled IN PLACE by the row's ratio.  Returns ``(pcm_out, n_out, factor)``: the new int16 [B, N]
     (``out``, if given: int16 [B, N] that does not overlap ``pcm``), int32 [B] new lengths, int32 [B] the index taken (-1: fell back to the
     copy).  One launch on the current stream, no host read; wrong dtypes, shapes or devices raise ValueError before anything is launched."""
-    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda):
-        raise ValueError("speed_perturb: pcm must be a GPU tensor (speed_perturb_host takes CPU tensors)")
     a, out, n_out, factor, keep = _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_max, out, True)
-    if a.B:
-        N.call("oasr_speed_perturb", C.byref(a), N.STREAM, device=pcm.device)
+    _pcm_call("speed_perturb", a, pcm, True)
     return out, n_out, factor
 
 
 def speed_perturb_host(pcm, n_valid, *, factors, seed=0, first_clip=0, tokens=(), ts_begin=50363, ts_max=1500, out=None):
     """``speed_perturb`` on CPU tensors through the library's host twin (oasr_speed_perturb_host: the same rule from the same text, no GPU).
     Here the lengths are readable, so an ``n_valid`` outside [0, N] raises ValueError."""
-    if not (isinstance(pcm, torch.Tensor) and not pcm.is_cuda):
-        raise ValueError("speed_perturb_host: pcm must be a CPU tensor")
     a, out, n_out, factor, keep = _speed_args(pcm, n_valid, factors, seed, first_clip, tokens, ts_begin, ts_max, out, False)
-    if a.B:
-        if int(n_valid.min()) < 0 or int(n_valid.max()) > a.N:
-            raise ValueError(f"speed_perturb_host: n_valid outside [0, N = {a.N}]")
-        N.call("oasr_speed_perturb_host", C.byref(a))
+    if a.B and (int(n_valid.min()) < 0 or int(n_valid.max()) > a.N):
+        raise ValueError(f"speed_perturb_host: n_valid outside [0, N = {a.N}]")
+    _pcm_call("speed_perturb", a, pcm, False)
     return out, n_out, factor
 
 
@@ -900,8 +945,7 @@ def speed_table(P, Q):
 def noise_policy(prob, snr_db):
     """The ``oasr_noise`` block of a policy, refused here (ValueError) for what the library would refuse (OASR_EINVAL): ``prob`` in [0, 1]
     (kept as round(prob * 65536): the chance of a clip to be drawn), ``snr_db`` = (lo, hi), whole dB with -10 <= lo <= hi <= 50."""
-    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:  # (a NaN fails the comparison)
-        raise ValueError(f"noise_mix: prob must be a number in [0, 1], got {prob!r}")
+    prob_q16 = _prob_q16("noise_mix", prob)
     try:
         lo, hi = snr_db
     except (TypeError, ValueError):
@@ -910,51 +954,21 @@ def noise_policy(prob, snr_db):
         raise ValueError(f"noise_mix: snr_db must be a pair of integers (whole dB), got {snr_db!r}")
     if not N.Noise.SNR_MIN <= lo <= hi <= N.Noise.SNR_MAX:
         raise ValueError(f"noise_mix: snr_db needs {N.Noise.SNR_MIN} <= lo <= hi <= {N.Noise.SNR_MAX}, got {snr_db!r}")
-    return N.Noise(int(round(prob * 65536)), lo, hi)
+    return N.Noise(prob_q16, lo, hi)
 
 
 def _noise_args(pcm, n_valid, bank, prob, snr_db, seed, first_clip, out, cuda):
     """Checks and converts the operands of ``noise_mix`` / ``noise_mix_host``: (NoiseArgs, pcm_out, row, snr, gain, keep-alive)."""
     what = "noise_mix" if cuda else "noise_mix_host"
-
-    def rows(t, nm, shape=None):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int16 and t.dim() == 2):
-            raise ValueError(f"{what}: {nm} must be a 2-D torch.int16 tensor")
-        if t.is_cuda != cuda or t.device != pcm.device:
-            raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor on the device of pcm")
-        if shape is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{what}: {nm} must be {list(shape)}, got {tuple(t.shape)}")
-        if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-            raise ValueError(f"{what}: {nm} needs unit column stride and rows that do not overlap")
-        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
-
-    if not isinstance(pcm, torch.Tensor):
-        raise ValueError(f"{what}: pcm must be a 2-D torch.int16 tensor")
-    ld_in = rows(pcm, "pcm")
-    ld_bank = rows(bank, "bank")
-    B, n = pcm.shape
+    ld_in, B, n = _pcm_in(what, pcm, n_valid, cuda)
+    ld_bank = _rows_ld(what, bank, "bank", pcm, cuda)
     M, L = bank.shape
-    if not (isinstance(n_valid, torch.Tensor) and n_valid.dtype == torch.int32 and n_valid.dim() == 1 and n_valid.numel() == B
-            and n_valid.is_contiguous() and n_valid.device == pcm.device):
-        raise ValueError(f"{what}: n_valid must be a contiguous int32 [{B}] on the device of pcm")
-    if not 1 <= n <= N.NoiseArgs.MAX_N or B > N.NoiseArgs.MAX_ROWS:
-        raise ValueError(f"{what}: pcm [B, N] with B <= 65535 and 1 <= N <= 2^26, got {tuple(pcm.shape)}")
     if not (1 <= L <= N.NoiseArgs.MAX_N and 1 <= M <= N.NoiseArgs.MAX_ROWS):
         raise ValueError(f"{what}: bank [M, L] with 1 <= M <= 65535 and 1 <= L <= 2^26, got {tuple(bank.shape)}")
     a = N.NoiseArgs()
     a.policy = noise_policy(prob, snr_db)
     a.seed, a.first_clip = _u64("seed", seed, what), _u64("first_clip", first_clip, what)
-    if out is None:
-        out = torch.empty(B, n, dtype=torch.int16, device=pcm.device)
-    ld_out = rows(out, "out", (B, n))
-    if B:
-        def span(t, ld, r, c):
-            return t.data_ptr(), t.data_ptr() + 2 * ((r - 1) * ld + c)
-        (lo_i, hi_i), (lo_o, hi_o), (lo_b, hi_b) = span(pcm, ld_in, B, n), span(out, ld_out, B, n), span(bank, ld_bank, M, L)
-        if lo_i < hi_o and lo_o < hi_i and not (lo_i == lo_o and ld_in == ld_out):
-            raise ValueError(f"{what}: out overlaps pcm without being pcm itself (in place: the same tensor)")
-        if lo_b < hi_o and lo_o < hi_b:
-            raise ValueError(f"{what}: out overlaps the bank")
+    out, ld_out = _pcm_out(what, pcm, ld_in, out, cuda, in_place=True, bank=bank, ld_bank=ld_bank)
     row = torch.empty(B, dtype=torch.int32, device=pcm.device)
     snr = torch.empty(B, dtype=torch.int32, device=pcm.device)
     gain = torch.empty(B, dtype=torch.int64, device=pcm.device)
@@ -975,24 +989,15 @@ def noise_mix(pcm, n_valid, bank, *, prob, snr_db, seed=0, first_clip=0, out=Non
     int16 [B, N] (``out``, if given: int16 [B, N] that is ``pcm`` itself -- in place -- or does not overlap it), int32 [B] bank rows (-1: not
     mixed), int32 [B] SNRs (-128: not mixed), int64 [B] gains (0: not mixed).  Two launches on the current stream, no host read; wrong
     dtypes, shapes or devices raise ValueError before anything is launched."""
-    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda):
-        raise ValueError("noise_mix: pcm must be a GPU tensor (noise_mix_host takes CPU tensors)")
     a, out, row, snr, gain, keep = _noise_args(pcm, n_valid, bank, prob, snr_db, seed, first_clip, out, True)
-    if a.B:
-        need = N.lib().oasr_noise_workspace_bytes(a.B, a.N)
-        ws = _workspace("noise_mix", pcm.device, need)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        N.call("oasr_noise_mix", C.byref(a), N.STREAM, device=pcm.device)
+    _pcm_call("noise_mix", a, pcm, True, lambda: N.lib().oasr_noise_workspace_bytes(a.B, a.N))
     return out, row, snr, gain
 
 
 def noise_mix_host(pcm, n_valid, bank, *, prob, snr_db, seed=0, first_clip=0, out=None):
     """``noise_mix`` on CPU tensors through the library's host twin (oasr_noise_mix_host: the same rule from the same text, no GPU)."""
-    if not (isinstance(pcm, torch.Tensor) and not pcm.is_cuda):
-        raise ValueError("noise_mix_host: pcm must be a CPU tensor")
     a, out, row, snr, gain, keep = _noise_args(pcm, n_valid, bank, prob, snr_db, seed, first_clip, out, False)
-    if a.B:
-        N.call("oasr_noise_mix_host", C.byref(a))
+    _pcm_call("noise_mix", a, pcm, False)
     return out, row, snr, gain
 
 
@@ -1012,54 +1017,22 @@ def noise_plan(prob, snr_db, seed, clip, M, L):
 def reverb_policy(prob):
     """The ``oasr_reverb`` block of a policy, refused here (ValueError) for what the library would refuse (OASR_EINVAL): ``prob`` in [0, 1]
     (kept as round(prob * 65536): the chance of a clip to be drawn)."""
-    if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:  # (a NaN fails the comparison)
-        raise ValueError(f"reverb: prob must be a number in [0, 1], got {prob!r}")
-    return N.Reverb(int(round(prob * 65536)))
+    return N.Reverb(_prob_q16("reverb", prob))
 
 
 def _reverb_args(pcm, n_valid, bank, delay, prob, seed, first_clip, out, cuda):
     """Checks and converts the operands of ``reverb`` / ``reverb_host``: (ReverbArgs, pcm_out, row, keep-alive)."""
     what = "reverb" if cuda else "reverb_host"
-
-    def rows(t, nm, shape=None):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int16 and t.dim() == 2):
-            raise ValueError(f"{what}: {nm} must be a 2-D torch.int16 tensor")
-        if t.is_cuda != cuda or t.device != pcm.device:
-            raise ValueError(f"{what}: {nm} must be a {'GPU' if cuda else 'CPU'} tensor on the device of pcm")
-        if shape is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{what}: {nm} must be {list(shape)}, got {tuple(t.shape)}")
-        if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-            raise ValueError(f"{what}: {nm} needs unit column stride and rows that do not overlap")
-        return t.stride(0) if t.shape[0] > 1 else t.shape[1]
-
-    if not isinstance(pcm, torch.Tensor):
-        raise ValueError(f"{what}: pcm must be a 2-D torch.int16 tensor")
-    ld_in = rows(pcm, "pcm")
-    ld_rir = rows(bank, "bank")
-    B, n = pcm.shape
+    ld_in, B, n = _pcm_in(what, pcm, n_valid, cuda)
+    ld_rir = _rows_ld(what, bank, "bank", pcm, cuda)
     R, K = bank.shape
-    for t, nm, rows_ in ((n_valid, "n_valid", B), (delay, "delay", R)):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == rows_ and t.is_contiguous()
-                and t.device == pcm.device):
-            raise ValueError(f"{what}: {nm} must be a contiguous int32 [{rows_}] on the device of pcm")
-    if not 1 <= n <= N.ReverbArgs.MAX_N or B > N.ReverbArgs.MAX_ROWS:
-        raise ValueError(f"{what}: pcm [B, N] with B <= 65535 and 1 <= N <= 2^26, got {tuple(pcm.shape)}")
+    _i32_vec(what, delay, "delay", R, pcm)
     if not (1 <= K <= N.ReverbArgs.MAX_K and 1 <= R <= N.ReverbArgs.MAX_ROWS):
         raise ValueError(f"{what}: bank [R, K] with 1 <= R <= 65535 and 1 <= K <= 8192, got {tuple(bank.shape)}")
     a = N.ReverbArgs()
     a.policy = reverb_policy(prob)
     a.seed, a.first_clip = _u64("seed", seed, what), _u64("first_clip", first_clip, what)
-    if out is None:
-        out = torch.empty(B, n, dtype=torch.int16, device=pcm.device)
-    ld_out = rows(out, "out", (B, n))
-    if B:
-        def span(t, ld, r, c):
-            return t.data_ptr(), t.data_ptr() + 2 * ((r - 1) * ld + c)
-        (lo_i, hi_i), (lo_o, hi_o), (lo_b, hi_b) = span(pcm, ld_in, B, n), span(out, ld_out, B, n), span(bank, ld_rir, R, K)
-        if lo_i < hi_o and lo_o < hi_i:
-            raise ValueError(f"{what}: out overlaps pcm (the operator works out of place)")
-        if lo_b < hi_o and lo_o < hi_b:
-            raise ValueError(f"{what}: out overlaps the bank")
+    out, ld_out = _pcm_out(what, pcm, ld_in, out, cuda, bank=bank, ld_bank=ld_rir)
     row = torch.empty(B, dtype=torch.int32, device=pcm.device)
     a.pcm_in, a.pcm_out, a.n_valid, a.rir, a.delay, a.row_out = (pcm.data_ptr(), out.data_ptr(), n_valid.data_ptr(), bank.data_ptr(),
                                                                  delay.data_ptr(), row.data_ptr())
@@ -1078,24 +1051,15 @@ def reverb(pcm, n_valid, bank, delay, *, prob, seed=0, first_clip=0, out=None):
     given: int16 [B, N] that does not overlap ``pcm``) and int32 [B] bank rows (-1: copied).  Two launches on the current stream (the bank
     expanded into int8 matrix-core operands, then the convolution), no host read; wrong dtypes, shapes or devices raise ValueError before
     anything is launched."""
-    if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda):
-        raise ValueError("reverb: pcm must be a GPU tensor (reverb_host takes CPU tensors)")
     a, out, row, keep = _reverb_args(pcm, n_valid, bank, delay, prob, seed, first_clip, out, True)
-    if a.B:
-        need = N.lib().oasr_reverb_workspace_bytes(a.R, a.K)
-        ws = _workspace("reverb", pcm.device, need)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        N.call("oasr_reverb", C.byref(a), N.STREAM, device=pcm.device)
+    _pcm_call("reverb", a, pcm, True, lambda: N.lib().oasr_reverb_workspace_bytes(a.R, a.K))
     return out, row
 
 
 def reverb_host(pcm, n_valid, bank, delay, *, prob, seed=0, first_clip=0, out=None):
     """``reverb`` on CPU tensors through the library's host twin (oasr_reverb_host: the same rule from the same text, no GPU)."""
-    if not (isinstance(pcm, torch.Tensor) and not pcm.is_cuda):
-        raise ValueError("reverb_host: pcm must be a CPU tensor")
     a, out, row, keep = _reverb_args(pcm, n_valid, bank, delay, prob, seed, first_clip, out, False)
-    if a.B:
-        N.call("oasr_reverb_host", C.byref(a))
+    _pcm_call("reverb", a, pcm, False)
     return out, row
 
 
