@@ -699,6 +699,77 @@ size_t oasr_reverb_workspace_bytes(int R, int K);
 int oasr_reverb(const oasr_reverb_args*, void* stream);
 int oasr_reverb_host(const oasr_reverb_args*);
 int oasr_reverb_plan(const struct oasr_reverb* policy, uint64_t seed, uint64_t clip, int R, int* drawn, int* row);
+/* Telephone channel: each drawn clip band-limited to 300 - 3400 Hz at 8 kHz, passed through a drawn G.711 codec and brought back to 16 kHz,
+ * on int16 PCM AHEAD of oasr_log_mel and after oasr_noise_mix -- the channel carries the noise too (csrc/telephone.hip; the rule itself:
+ * csrc/telephone_core.h).  Entry points only: OASR_ABI_VERSION is unchanged, and a binding checks oasr_sizeof_telephone_args like
+ * oasr_sizeof_reverb_args.  The operator is an integer function of its operands: floating point enters only where the HOST builds the two
+ * tap tables (oasr_telephone_tables), once.
+ *
+ * Operands: pcm_in / pcm_out int16 [B, N], row strides ld_in / ld_out >= N (samples), rows at any even address; the two must not overlap (an
+ * output sample reads up to 95 input samples on either side: in place is not offered).  n_valid int32 [B]: each row's leading non-padding
+ * samples.  1 <= B <= 65535, 1 <= N <= 2^26.  Report: codec_out int32 [B], or NULL.
+ * Policy: prob_q16 in [0, 65536] (the chance of a clip to be drawn, in 1 / 65536); n_codecs in [1, 8] entries of codecs, each one of
+ * OASR_TELEPHONE_LINEAR (0), _MULAW (1), _ALAW (2) -- repeats act as weights; bandpass 1, or 0 for material that is narrow-band already.
+ *
+ * Draws per clip, with mix() and h = mix(mix(seed) ^ clip), clip = first_clip + row, as at oasr_spec_augment (the SAME h; kind 6 keeps the
+ * draws apart from kinds 1 .. 5 of the masks, speed perturbation, noise mixing and reverberation), t = 6 << 16:
+ *     drawn = mix(h ^ t) % 65536 < prob_q16        codec = codecs[mix(h ^ (t | 1)) % n_codecs]
+ * Tables, built by the host in double precision, sinc(t) = sin(pi t) / (pi t), sinc(0) = 1:
+ *     h[k] = floor(c * 32768 + 0.5),  k = -64 .. 64,   c = (lp(3400)[k] - lp(300)[k]) * (0.5 + 0.5 cos(pi k / 65)),
+ *            lp(f)[k] = (2 f / 16000) * sinc(2 f k / 16000)                      (129 taps, symmetric, no sum fix-up; sum |h| = 76960)
+ *     u[j] = floor(sinc(t) * (0.5 + 0.5 cos(pi t / 16)) * 32768 + 0.5),  j = 0 .. 31,  t = (j - 15) - 0.5;  then 32768 - sum u is added to
+ *            the first largest tap, so that the phase sums to exactly 2^15                                      (sum |u| = 81604)
+ * Samples of a drawn clip with 1 <= n_valid <= N:   x(i) = pcm_in[row][i] for 0 <= i < n_valid, else 0;   M = ceil(n_valid / 2);
+ *     z[m]     = clamp((sum_{k = -64}^{64} h[k] * x(2 m - k) + 2^14) >> 15, -32768, 32767)  for 0 <= m < M        (exact sum, arithmetic shift)
+ *                with bandpass = 0:  z[m] = x(2 m)
+ *     c[m]     = q_codec(z[m])  for 0 <= m < M,  0 elsewhere
+ *     y[2 m]   = c[m]
+ *     y[2 m+1] = clamp((sum_{j = 0}^{31} u[j] * c[m + j - 15] + 2^14) >> 15, -32768, 32767)  where 2 m + 1 < n_valid
+ *     y[n]     = pcm_in[row][n]  for n_valid <= n < N
+ * Both sums exceed 32 bits (|sum| up to 76960 * 2^15 and 81604 * 2^15): they are exact all the same.  The filters are symmetric about the
+ * sample they produce (zero phase), so lengths, n_valid and timestamp tokens do not change.
+ * Codecs -- the G.711 quantisers as expand(compress(x)) on the 16-bit value, in closed form, s = x < 0, q = s ? -y : y:
+ *     linear   q(x) = x
+ *     mu-law   a = min(s ? -x : x, 32635) + 132;   e = floor(log2 a) - 7;   m = (a >> (e + 3)) & 15;   y = (((m << 3) + 132) << e) - 132
+ *     A-law    a = s ? -x - 1 : x;   v = a >> 3;   g = v < 32 ? 0 : floor(log2 v) - 4;   m = g < 2 ? (v >> 1) & 15 : (v >> g) & 15;
+ *              y = g == 0 ? (m << 4) + 8 : ((m << 4) + 264) << (g - 1)
+ *     (mu-law: 255 levels inside +-32124, q(0) = q(-1) = 0, |q(x) - x| <= 644;  A-law: 256 levels inside +-32256, q(0) = 8, q(-1) = -8,
+ *     |q(x) - x| <= 512;  both monotone and idempotent)
+ * A clip that is not drawn, or whose n_valid is outside [1, N], is copied bit for bit and reports codec_out = -1; any other reports its codec.
+ *
+ * oasr_telephone: device pointers, ONE launch on `stream`, never synchronises, no workspace, nothing comes back to the host.  The plan is
+ * evaluated on the device; lengths live there, so the host cannot refuse them.  Everything else that is wrong is OASR_EINVAL before a launch.
+ * oasr_telephone_host: HOST function (no GPU call, host pointers), the same rule from the same text.
+ * oasr_telephone_plan: HOST function: (drawn, codec) of ONE clip (each output may be NULL); it needs no audio.
+ * oasr_telephone_tables: HOST function: the library's h (as h[k + 64]) and u (each may be NULL).
+ * oasr_telephone_quantize_host: HOST function: out[i] = q_codec(in[i]) for i < n (n >= 0; in may be out). */
+#define OASR_TELEPHONE_MAX_CODECS 8
+#define OASR_TELEPHONE_LINEAR 0
+#define OASR_TELEPHONE_MULAW 1
+#define OASR_TELEPHONE_ALAW 2
+struct oasr_telephone { /* the policy; no typedef, as with `struct oasr_reverb`: the plain name oasr_telephone is the entry point below */
+  int32_t prob_q16, n_codecs;
+  int32_t codecs[OASR_TELEPHONE_MAX_CODECS];
+  int32_t bandpass;
+};
+typedef struct oasr_telephone_args {
+  const int16_t* pcm_in;
+  int16_t* pcm_out;
+  const int32_t* n_valid;
+  int32_t* codec_out;
+  int64_t ld_in, ld_out;
+  uint64_t seed, first_clip;
+  int32_t B, N;
+  struct oasr_telephone policy;
+  int32_t reserved;
+} oasr_telephone_args;
+size_t oasr_sizeof_telephone(void);
+size_t oasr_sizeof_telephone_args(void);
+int oasr_telephone(const oasr_telephone_args*, void* stream);
+int oasr_telephone_host(const oasr_telephone_args*);
+int oasr_telephone_plan(const struct oasr_telephone* policy, uint64_t seed, uint64_t clip, int* drawn, int* codec);
+int oasr_telephone_tables(int32_t h[129], int32_t u[32]);
+int oasr_telephone_quantize_host(const int16_t* in, int16_t* out, int64_t n, int codec);
 int oasr_cross_entropy(void* logits_bf16, int64_t ld, int V, const int64_t* targets, int64_t rows, int64_t ignore, float gscale,
                        int32_t* n_valid_dev, float* row_loss, float* loss_out, int write_grad, void* stream);
 /* The same operator with the regularisers of oasr_train_step_args (label_smoothing, z_loss: the formula there; gscale takes the place of

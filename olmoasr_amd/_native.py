@@ -115,6 +115,20 @@ class ReverbArgs(C.Structure):  # include/oasr.h: oasr_reverb_args
                 ("K", C.c_int32), ("policy", Reverb), ("reserved", C.c_int32)]
 
 
+class Telephone(C.Structure):  # include/oasr.h: struct oasr_telephone
+    MAX_CODECS = 8  # OASR_TELEPHONE_MAX_CODECS
+    LINEAR, MULAW, ALAW = 0, 1, 2  # OASR_TELEPHONE_LINEAR, _MULAW, _ALAW
+    BP_TAPS, UP_TAPS = 129, 32  # the tables of oasr_telephone_tables
+    _fields_ = [("prob_q16", C.c_int32), ("n_codecs", C.c_int32), ("codecs", C.c_int32 * 8), ("bandpass", C.c_int32)]
+
+
+class TelephoneArgs(C.Structure):  # include/oasr.h: oasr_telephone_args
+    MAX_N, MAX_ROWS = 1 << 26, 65535
+    _fields_ = [("pcm_in", C.c_void_p), ("pcm_out", C.c_void_p), ("n_valid", C.c_void_p), ("codec_out", C.c_void_p), ("ld_in", C.c_int64),
+                ("ld_out", C.c_int64), ("seed", C.c_uint64), ("first_clip", C.c_uint64), ("B", C.c_int32), ("N", C.c_int32),
+                ("policy", Telephone), ("reserved", C.c_int32)]
+
+
 class TrainStepArgs(C.Structure):  # include/oasr.h: oasr_train_step_args
     _fields_ = [(n, C.c_void_p) for n in ("mel", "xa", "tokens", "targets", "text_len", "span_host", "mel_clip_max", "loss_out", "logits_out",
                                           "pred_out", "seg_events")] + \
@@ -137,6 +151,8 @@ STRUCT_SIZES = [
     ("oasr_sizeof_noise_args", NoiseArgs),
     ("oasr_sizeof_reverb", Reverb),  # came with oasr_reverb
     ("oasr_sizeof_reverb_args", ReverbArgs),
+    ("oasr_sizeof_telephone", Telephone),  # came with oasr_telephone
+    ("oasr_sizeof_telephone_args", TelephoneArgs),
     ("oasr_sizeof_train_step_args", TrainStepArgs),  # last grown by label_smoothing / z_loss / loss_parts_*
     ("oasr_sizeof_score_args", ScoreArgs),  # came with oasr_score, oasr_score_rows and oasr_score_reduce
 ]
@@ -267,6 +283,13 @@ def _declare(lib):
         "oasr_reverb": (i32, [C.POINTER(ReverbArgs), vp]),
         "oasr_reverb_host": (i32, [C.POINTER(ReverbArgs)]),
         "oasr_reverb_plan": (i32, [C.POINTER(Reverb), C.c_uint64, C.c_uint64, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "oasr_sizeof_telephone": (sz, []),
+        "oasr_sizeof_telephone_args": (sz, []),
+        "oasr_telephone": (i32, [C.POINTER(TelephoneArgs), vp]),
+        "oasr_telephone_host": (i32, [C.POINTER(TelephoneArgs)]),
+        "oasr_telephone_plan": (i32, [C.POINTER(Telephone), C.c_uint64, C.c_uint64, C.POINTER(i32), C.POINTER(i32)]),
+        "oasr_telephone_tables": (i32, [vp, vp]),
+        "oasr_telephone_quantize_host": (i32, [vp, vp, i64, i32]),
         "oasr_test_argmax_rows": (i32, [vp, i32, i64, i32, i64, vp, vp, i32, i32, vp, vp]),
         "oasr_cross_entropy": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, vp]),
         "oasr_cross_entropy_ex": (i32, [vp, i64, i32, vp, i64, i64, f32, vp, vp, vp, i32, f32, f32, vp, vp]),

@@ -37,7 +37,17 @@ Reverberation convolves a clip with a room impulse response from a bank, between
 
 The bank is the only place floating point enters, on the host, once; the convolution is an exact integer sum (on the int8 matrix cores),
 shifted back by the direct-path delay and cut at the clip's length, so lengths and timestamps stay.  It draws from the same hash stream
-(kind 5): ``Reverb.plan`` gives a clip's draw without a GPU and without audio."""
+(kind 5): ``Reverb.plan`` gives a clip's draw without a GPU and without audio.
+
+The telephone channel comes last, after the noise -- the channel carries the noise too -- and ahead of ``ops.log_mel`` (``ops.telephone``,
+csrc/telephone.hip):
+
+    phone = augment.TelephoneChannel(prob=0.3, codecs=("mulaw", "alaw", "linear"))
+    pcm, codec = phone.apply(pcm, n_out, seed, first_clip=stream_id_of_row_0)
+
+A drawn clip is band-passed to 300 - 3400 Hz at 8 kHz, companded by a drawn G.711 codec and interpolated back to 16 kHz, by zero-phase
+integer filters: lengths and timestamps stay.  The two tap tables are the only place floating point enters, on the host, once.  It draws
+from the same hash stream (kind 6): ``TelephoneChannel.plan`` gives a clip's draw without a GPU and without audio."""
 import math
 from dataclasses import dataclass
 
@@ -178,6 +188,41 @@ class Reverb:
         """How many of the B clips at stream ids first_clip .. are drawn, from the plan alone.  A drawn clip whose length is outside [1, N] is
         copied all the same: that takes the lengths to know."""
         return sum(self.plan(seed, (first_clip + b) & _U64, R)[0] for b in range(B))
+
+
+TELEPHONE_CODECS = ("linear", "mulaw", "alaw")  # by the library's numbers 0, 1, 2
+
+
+@dataclass(frozen=True)
+class TelephoneChannel:
+    prob: float = 0.3                            # the chance of a clip to go through the channel (kept in 1 / 65536)
+    codecs: tuple = ("mulaw", "alaw", "linear")  # 1 .. 8 names, one drawn per clip; repeats act as weights
+    bandpass: bool = True                        # False: material that is narrow-band already, only decimated and companded
+
+    def __post_init__(self):
+        from . import ops
+        pol = ops.telephone_policy(self.prob, self.codecs, self.bandpass)
+        object.__setattr__(self, "codecs", tuple(TELEPHONE_CODECS[pol.codecs[i]] for i in range(pol.n_codecs)))
+
+    def apply(self, pcm, n_valid, seed, first_clip=0, out=None):
+        """int16 [B, N] on the GPU -> (pcm_out, codec), out of place; row b takes stream id first_clip + b."""
+        from . import ops
+        return ops.telephone(pcm, n_valid, prob=self.prob, codecs=self.codecs, bandpass=self.bandpass, seed=seed, first_clip=first_clip, out=out)
+
+    def plan(self, seed, clip):
+        """(drawn, codec name) of stream id ``clip``, from the library's host function: no GPU needed."""
+        from . import ops
+        d, c = ops.telephone_plan(self.prob, self.codecs, seed, clip, self.bandpass)
+        return d, TELEPHONE_CODECS[c]
+
+    def drawn(self, seed, first_clip, B):
+        """Per codec, how many of the B clips at stream ids first_clip .. are drawn, from the plan alone: {"linear": .., "mulaw": ..,
+        "alaw": ..}.  A drawn clip whose length is outside [1, N] is copied all the same: that takes the lengths to know."""
+        counts = {name: 0 for name in TELEPHONE_CODECS}
+        for b in range(B):
+            d, name = self.plan(seed, (first_clip + b) & _U64)
+            counts[name] += int(d)
+        return counts
 
 
 def rir_bank(arrays, K=None):

@@ -238,6 +238,10 @@ extern "C" size_t oasr_reverb_workspace_bytes(int R, int K) {
 }
 extern "C" int oasr_reverb(const oasr_reverb_args* a, void* stream) { return launch_reverb(a, (hipStream_t)stream); }
 
+extern "C" size_t oasr_sizeof_telephone(void) { return sizeof(struct oasr_telephone); }
+extern "C" size_t oasr_sizeof_telephone_args(void) { return sizeof(oasr_telephone_args); }
+extern "C" int oasr_telephone(const oasr_telephone_args* a, void* stream) { return launch_telephone(a, (hipStream_t)stream); }
+
 extern "C" int oasr_test_span_tables(const int32_t* span_host, int B, int S, const int64_t* targets, int32_t* rows_out, int32_t* span_out,
                                      int64_t* targets_rows_out, int64_t* active_rows_out, void* stream) {
   OASR_REQUIRE(active_rows_out, "oasr_test_span_tables: null");

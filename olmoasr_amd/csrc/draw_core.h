@@ -1,5 +1,5 @@
 // The seeded per-clip draw stream of the augmentation operators (include/oasr.h at oasr_spec_augment, oasr_speed_perturb, oasr_noise_mix,
-// oasr_reverb): the ONE text that the device kernels and the host twins share.  Plain C++: no HIP header is needed to include this file.
+// oasr_reverb, oasr_telephone): the ONE text that the device kernels and the host twins share.  Plain C++: no HIP header is needed to include this file.
 //
 // Everything is unsigned 64-bit integer arithmetic with wrap-around; no floating point enters a draw.  What a clip draws is a pure function
 // of (seed, clip stream id, kind, slot): it does not depend on the batch the clip sits in or on how many calls came before.
@@ -10,8 +10,9 @@
 
 // The registry of kinds: each operator draws under a kind of its own, so no two operators read the same value of a clip's stream.  A new
 // operator takes the next number; the numbers below are part of what a seed means and never change.
-enum { DRAW_FREQ_MASK = 1, DRAW_TIME_MASK = 2, DRAW_SPEED = 3, DRAW_NOISE = 4, DRAW_REVERB = 5 };
-static_assert(DRAW_FREQ_MASK == 1 && DRAW_TIME_MASK == 2 && DRAW_SPEED == 3 && DRAW_NOISE == 4 && DRAW_REVERB == 5, "the kinds are fixed");
+enum { DRAW_FREQ_MASK = 1, DRAW_TIME_MASK = 2, DRAW_SPEED = 3, DRAW_NOISE = 4, DRAW_REVERB = 5, DRAW_TELEPHONE = 6 };
+static_assert(DRAW_FREQ_MASK == 1 && DRAW_TIME_MASK == 2 && DRAW_SPEED == 3 && DRAW_NOISE == 4 && DRAW_REVERB == 5 && DRAW_TELEPHONE == 6,
+              "the kinds are fixed");
 
 // splitmix64's finalizer on z + golden ratio
 OASR_HD uint64_t draw_mix(uint64_t z) {

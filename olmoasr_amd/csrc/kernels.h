@@ -374,6 +374,12 @@ struct oasr_reverb_args;
 size_t reverb_workspace_bytes(int R, int K);
 int launch_reverb(const oasr_reverb_args* a, hipStream_t s);
 
+// ---- telephone channel (telephone.hip; the contract: include/oasr.h at oasr_telephone, the rule: telephone_core.h) ------------------------
+// pcm_out = each drawn clip of pcm_in band-passed to 8 kHz, companded by its drawn G.711 codec and interpolated back (else a copy); one
+// launch, plan on the device, tables from the host half (telephone_host.cpp) as kernel arguments
+struct oasr_telephone_args;
+int launch_telephone(const oasr_telephone_args* a, hipStream_t s);
+
 // ---- LoRA adapters in weight space (lora.hip) -----------------------------------------------------------------
 // out = W0 + scale * B . A  (W0 [rows][cols] fp32, A [r][cols], B [rows][r]; k sum in ascending order): exactly one of out32 (fp32, may be w0
 // itself) / out16 (bf16, the rounding of launch_cast_f32_bf16)

@@ -1,4 +1,4 @@
-// Device row I/O of the int16 PCM kernels (speed.hip, noise.hip, reverb.hip): eight samples at a time.  The kernels lay their tiles on the
+// Device row I/O of the int16 PCM kernels (speed.hip, noise.hip, reverb.hip, telephone.hip): eight samples at a time.  The kernels lay their tiles on the
 // 16-byte grid of the OUTPUT row's address (a row may start at any even address), so every store is one aligned 16-byte store but for a
 // row's first and last few samples.  The input row sits at another offset from that grid, so its eight samples come by one 16-byte load
 // that is only 2-byte aligned: global memory takes it as it comes, and a wave still covers one contiguous kilobyte.

@@ -790,7 +790,7 @@ def _prob_q16(who, prob):
     return int(round(prob * 65536))
 
 
-# ---- the PCM operators (speed_perturb, noise_mix, reverb): what their operand checks and their entry points have in common -------------
+# ---- the PCM operators (speed_perturb, noise_mix, reverb, telephone): what their operand checks and their entry points have in common -------------
 def _rows_ld(what, t, nm, pcm, cuda, dtype=torch.int16, shape=None):
     """The row stride of ``t``: a 2-D ``dtype`` matrix (of ``shape``, if given) with unit column stride and rows that do not overlap, on
     the device of ``pcm``."""
@@ -1072,6 +1072,102 @@ def reverb_plan(prob, seed, clip, R):
     d, r = C.c_int(), C.c_int()
     N.call("oasr_reverb_plan", C.byref(pol), _u64("seed", seed, "reverb_plan"), _u64("clip", clip, "reverb_plan"), R, C.byref(d), C.byref(r))
     return bool(d.value), r.value
+
+
+TELEPHONE_CODECS = {"linear": N.Telephone.LINEAR, "mulaw": N.Telephone.MULAW, "alaw": N.Telephone.ALAW}
+
+
+def _telephone_codec(who, c):
+    """A codec by name ("linear", "mulaw", "alaw") or by the library's number (0, 1, 2), as the number."""
+    if isinstance(c, str) and c in TELEPHONE_CODECS:
+        return TELEPHONE_CODECS[c]
+    if isinstance(c, int) and not isinstance(c, bool) and c in TELEPHONE_CODECS.values():
+        return c
+    raise ValueError(f"{who}: a codec must be one of {sorted(TELEPHONE_CODECS)} (or 0, 1, 2), got {c!r}")
+
+
+def telephone_policy(prob, codecs, bandpass=True):
+    """The ``struct oasr_telephone`` block of a policy, refused here (ValueError) for what the library would refuse (OASR_EINVAL): ``prob``
+    in [0, 1] (kept as round(prob * 65536): the chance of a clip to be drawn), ``codecs`` 1 .. 8 of "linear" | "mulaw" | "alaw" (or 0 | 1 |
+    2; repeats act as weights), ``bandpass`` a bool."""
+    prob_q16 = _prob_q16("telephone", prob)
+    if isinstance(codecs, (str, bytes)) or not hasattr(codecs, "__iter__"):
+        raise ValueError(f"telephone: codecs must be a sequence of codec names, got {codecs!r}")
+    ids = [_telephone_codec("telephone", c) for c in codecs]
+    if not 1 <= len(ids) <= N.Telephone.MAX_CODECS:
+        raise ValueError(f"telephone: between 1 and {N.Telephone.MAX_CODECS} codecs, got {len(ids)}")
+    if not isinstance(bandpass, bool):
+        raise ValueError(f"telephone: bandpass must be a bool, got {bandpass!r}")
+    pol = N.Telephone()
+    pol.prob_q16, pol.n_codecs, pol.bandpass = prob_q16, len(ids), int(bandpass)
+    for i, c in enumerate(ids):
+        pol.codecs[i] = c
+    return pol
+
+
+def _telephone_args(pcm, n_valid, prob, codecs, bandpass, seed, first_clip, out, cuda):
+    """Checks and converts the operands of ``telephone`` / ``telephone_host``: (TelephoneArgs, pcm_out, codec, keep-alive)."""
+    what = "telephone" if cuda else "telephone_host"
+    ld_in, B, n = _pcm_in(what, pcm, n_valid, cuda)
+    a = N.TelephoneArgs()
+    a.policy = telephone_policy(prob, codecs, bandpass)
+    a.seed, a.first_clip = _u64("seed", seed, what), _u64("first_clip", first_clip, what)
+    out, ld_out = _pcm_out(what, pcm, ld_in, out, cuda)
+    codec = torch.empty(B, dtype=torch.int32, device=pcm.device)
+    a.pcm_in, a.pcm_out, a.n_valid, a.codec_out = pcm.data_ptr(), out.data_ptr(), n_valid.data_ptr(), codec.data_ptr()
+    a.ld_in, a.ld_out, a.B, a.N = ld_in, ld_out, B, n
+    return a, out, codec, (pcm, n_valid)
+
+
+def telephone(pcm, n_valid, *, prob, codecs=("mulaw", "alaw", "linear"), bandpass=True, seed=0, first_clip=0, out=None):
+    """The telephone channel on int16 PCM at 16 kHz on the GPU (include/oasr.h: oasr_telephone; the rule: csrc/telephone_core.h): ``pcm``
+    int16 [B, N] (unit column stride, any row stride >= N), ``n_valid`` int32 [B] = each row's leading non-padding samples.  Row ``b`` draws
+    -- from stream id ``first_clip + b`` (mod 2^64) under ``seed``, the hash stream of ``spec_augment_``, kind 6 -- whether it goes through
+    the channel (``prob``) and one of ``codecs``; its first ``n_valid`` samples are band-passed to 300 - 3400 Hz at 8 kHz by a 129-tap
+    integer filter (``bandpass=False``: every second sample is taken as it is), companded by the G.711 quantiser drawn ("mulaw", "alaw", or
+    "linear": none), and interpolated back to 16 kHz by a 32-tap integer filter; both filters are zero-phase, so lengths and timestamps
+    stay.  A row that is not drawn or has ``n_valid`` outside [1, N] is copied.  Returns ``(pcm_out, codec)``: int16 [B, N] (``out``, if
+    given: int16 [B, N] that does not overlap ``pcm``) and int32 [B] codecs (0 linear, 1 mu-law, 2 A-law; -1: copied).  One launch on the
+    current stream, no host read; wrong dtypes, shapes or devices raise ValueError before anything is launched."""
+    a, out, codec, keep = _telephone_args(pcm, n_valid, prob, codecs, bandpass, seed, first_clip, out, True)
+    _pcm_call("telephone", a, pcm, True)
+    return out, codec
+
+
+def telephone_host(pcm, n_valid, *, prob, codecs=("mulaw", "alaw", "linear"), bandpass=True, seed=0, first_clip=0, out=None):
+    """``telephone`` on CPU tensors through the library's host twin (oasr_telephone_host: the same rule from the same text, no GPU)."""
+    a, out, codec, keep = _telephone_args(pcm, n_valid, prob, codecs, bandpass, seed, first_clip, out, False)
+    _pcm_call("telephone", a, pcm, False)
+    return out, codec
+
+
+def telephone_plan(prob, codecs, seed, clip, bandpass=True):
+    """What ``telephone`` draws for stream id ``clip``, from the library's host function (oasr_telephone_plan; no GPU, no audio):
+    ``(drawn, codec)`` -- the codec is the one the clip would take, drawn or not."""
+    pol = telephone_policy(prob, codecs, bandpass)
+    d, c = C.c_int(), C.c_int()
+    N.call("oasr_telephone_plan", C.byref(pol), _u64("seed", seed, "telephone_plan"), _u64("clip", clip, "telephone_plan"), C.byref(d), C.byref(c))
+    return bool(d.value), c.value
+
+
+def telephone_tables():
+    """The library's Q15 tap tables (oasr_telephone_tables; host): ``(h, u)`` -- the band-pass int32 [129] as h[k + 64], k = -64 .. 64, and
+    the interpolator's odd phase int32 [32], which sums to 32768."""
+    h, u = torch.empty(N.Telephone.BP_TAPS, dtype=torch.int32), torch.empty(N.Telephone.UP_TAPS, dtype=torch.int32)
+    N.call("oasr_telephone_tables", h, u)
+    return h, u
+
+
+def telephone_quantize_host(x, codec):
+    """The G.711 quantiser ``codec`` ("linear" | "mulaw" | "alaw") as expand(compress(x)) on a contiguous int16 CPU tensor of any shape,
+    through the library's host function (oasr_telephone_quantize_host): a new tensor."""
+    c = _telephone_codec("telephone_quantize_host", codec)
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.int16 and not x.is_cuda and x.is_contiguous()):
+        raise ValueError("telephone_quantize_host: x must be a contiguous int16 CPU tensor")
+    out = torch.empty_like(x)
+    if x.numel():
+        N.call("oasr_telephone_quantize_host", x, out, x.numel(), c)
+    return out
 
 
 def pick_tokens(logits, mask=None, mask2=None, want_logprob=True):

@@ -91,6 +91,12 @@ NATIVE_FLAGS = dict(  # additions of this implementation
     # row, or an object array of 1-D float responses) turns it on; --reverb_prob (default 0.5) is a clip's chance to be reverberated.  Drawn
     # from --seed and the step counter (spec_offset), like the masks, the speed factors and the noise.
     rir_bank=None, reverb_prob=None,
+    # The telephone channel on the int16 clips of every TRAINING micro-batch, after noise mixing -- the channel carries the noise too -- and ahead
+    # of the log-mel (olmoasr_amd/augment.py, csrc/telephone.hip): --telephone_prob P (a clip's chance to go through the channel) turns it on;
+    # --telephone_codecs (default mulaw,alaw,linear) lists the G.711 codecs one is drawn from, repeats acting as weights, and
+    # --telephone_bandpass (default True) keeps or drops the 300 - 3400 Hz band-pass ahead of the codec.  Drawn from --seed and the step
+    # counter (spec_offset), like the masks, the speed factors, the room responses and the noise.
+    telephone_prob=None, telephone_codecs=None, telephone_bandpass=None,
     # Held-out loss (OLMoASR.score, csrc/score.hip: forward only, no fp32 logits, no gradient write).  --val_freq N (0 = off: step and log
     # records unchanged) scores a validation set every N optimizer steps, after the step: with --synthetic the --n_val indices
     # n_synthetic + 8 + i (disjoint from every training shard and from evaluate()'s clips), else the shards under --val_samples_dicts_dir
@@ -201,6 +207,26 @@ def reverb_policy(args):
         raise SystemExit(f"--reverb_prob: {e}")
 
 
+def telephone_policy(args):
+    """--telephone_prob, --telephone_codecs and --telephone_bandpass -> augment.TelephoneChannel, or None without --telephone_prob."""
+    if args.telephone_prob is None:
+        for f in ("telephone_codecs", "telephone_bandpass"):
+            if args[f] is not None:
+                raise SystemExit(f"--{f} given without --telephone_prob: give the chance of a clip to go through the channel to turn it on")
+        return None
+    over = {"prob": args.telephone_prob}
+    if args.telephone_codecs is not None:
+        c = args.telephone_codecs
+        over["codecs"] = tuple(t.strip() for t in c.split(",")) if isinstance(c, str) else tuple(c) if isinstance(c, (tuple, list)) else c
+    if args.telephone_bandpass is not None:
+        over["bandpass"] = args.telephone_bandpass
+    from olmoasr_amd import augment
+    try:
+        return augment.TelephoneChannel(**over)
+    except ValueError as e:
+        raise SystemExit(f"--telephone_prob / --telephone_codecs / --telephone_bandpass: {e}")
+
+
 def load_rir_bank(path):
     """The bank of --rir_bank as (int16 [R, K] Q15 taps, int32 [R] direct-path delays) on the CPU, from a 2-D float array (one response per
     row) or an object array (or list) of 1-D float responses: augment.rir_bank scales each to unit energy, K = min(8192, the longest)."""
@@ -297,6 +323,7 @@ def parse_args(argv=None):
     args.speed_policy = speed_policy(args)
     args.noise_policy = noise_policy(args)
     args.reverb_policy = reverb_policy(args)
+    args.telephone_policy = telephone_policy(args)
     if args.train_error_counts not in ERROR_COUNTS:
         raise SystemExit(f"--train_error_counts must be one of {' | '.join(ERROR_COUNTS)}, got {args.train_error_counts!r}")
     if args.train_error_counts == "device" and not args.span_backward:
@@ -694,6 +721,10 @@ def main(argv=None):
         rir_bank, rir_delay = (t.to(dev) for t in load_rir_bank(args.rir_bank))
         if rank == 0:
             print(json.dumps({"event": "reverb", "bank": list(rir_bank.shape), "prob": reverb.prob, "seed": spec_seed}), flush=True)
+    phone = args.telephone_policy
+    if phone is not None and rank == 0:
+        print(json.dumps({"event": "telephone", "prob": phone.prob, "codecs": list(phone.codecs), "bandpass": phone.bandpass, "seed": spec_seed}),
+              flush=True)
     if regularised and rank == 0:
         print(json.dumps({"event": "loss_regularisers", "label_smoothing": args.label_smoothing, "z_loss": args.z_loss}), flush=True)
     device_counts = args.train_error_counts == "device"
@@ -710,6 +741,7 @@ def main(argv=None):
         speed_counts = [0] * (len(speed.factors) + 1) if speed is not None else None  # this rank's clips per factor (last entry: fell back to the copy): from the host plan too
         noise_drawn = noise_snr_sum = 0  # this rank's clips that drew noise in this step and the sum of their SNRs: from the host plan too
         reverb_drawn = 0  # this rank's clips that drew a room response in this step: from the host plan too
+        phone_counts = {}  # this rank's clips that drew the telephone channel in this step, per codec: from the host plan too
         for i in range(accum):
             pcm, ti, ty, tl = next(loader)
             cursor += args.train_batch_size  # (position in this rank's epoch order; a short last batch also ends the epoch)
@@ -738,6 +770,11 @@ def main(argv=None):
                     pcm = noise.apply(pcm, n_cur, noise_bank, spec_seed, first)[0]
                 d_, s_ = noise.drawn(spec_seed, first, int(pcm.shape[0]), *noise_bank.shape)
                 noise_drawn, noise_snr_sum = noise_drawn + d_, noise_snr_sum + s_
+            if phone is not None:  # last on the PCM: the channel carries the noise too (out of place: a new pcm tensor; lengths and timestamps stay)
+                first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
+                pcm = phone.apply(pcm, n_cur, spec_seed, first)[0]
+                for name, c in phone.drawn(spec_seed, first, int(pcm.shape[0])).items():
+                    phone_counts[name] = phone_counts.get(name, 0) + c
             if policy is not None:  # masks go on the FINALIZED log-mel, so the span step takes it finalized as well (mel_clip_max=None)
                 mel, clip_max = ops.log_mel(pcm), None
                 first = spec_offset(global_step, i, accum, world_size, rank, args.train_batch_size) & ((1 << 64) - 1)
@@ -801,6 +838,8 @@ def main(argv=None):
                     rec.update(noise_drawn=noise_drawn, noise_snr_db_mean=round(noise_snr_sum / noise_drawn, 3) if noise_drawn else None)
                 if reverb is not None:
                     rec["reverb_drawn"] = reverb_drawn
+                if phone is not None:
+                    rec.update(telephone_drawn=sum(phone_counts.values()), telephone_codec_counts=phone_counts)
                 if regularised:
                     rec.update(train_nll=parts[0] / world_size, train_lse_sq=parts[1] / world_size)
                 if preds:
