@@ -27,7 +27,7 @@ int oasr_gemm_set_variant(int v);
  * XCD (B <= 4), 3 / 4 = that team as 32 / 64 workgroups spread over the chip, 5 = the chip-wide engine (one sequence; more: as 2).
  * 0-4 are bit-identical; 5 agrees with them to the fp32 rounding of differently ordered K sums (tests/test_gpu_decode_step.py). */
 int oasr_decode_set_ln_fold(int mode);
-/* tests / A-B: side streams of the supervised-span step (oasr_train_step with span_host; csrc/engine_run.h: Runner::side_mode).  Bit 0: the decoder
+/* tests / A-B: side streams of the supervised-span step (oasr_train_step with span_host; csrc/engine_side.h: SideMode).  Bit 0: the decoder
  * backward's weight gradients over the R active rows, bit 2: the cross-attention key|value weight gradient and d(xa) -- run on lowest-priority
  * streams beside the data-gradient chain; bit 1: the key|value projections of the decoder forward likewise; bit 3: without segment events leave
  * the key|value gradients in flight across blocks.  -1 = the library default.  Gradients differ by fp32 atomic order only
@@ -79,6 +79,16 @@ int oasr_profile_gemm_records(char* buf, int cap);
 int oasr_gemm_route_debug(int M, int N, int K, int ta, int tb, int a_view, int b_view, int split_k, int atomic, int atomic_on_pp, int outputs,
                           int sides, long long ldc, long long ldr, long long ldu, int misalign, int colsum, int colsum_scratch, int forced_path,
                           int pp_schedule, int geom_env, char* symbol, int cap, int* post);
+/* tests (CPU, tests/test_train_plan_cpu.py): the host decisions of the training engine (csrc/train_plan.h) on plain integers -- nothing launched.
+ * wgrad_plan: how the engine launches the weight gradient dW[N, K] += dy[M, N]^T . x[M, K] over M token rows (view: x is a conv-window view):
+ *   *split_k and *atomic_on_pp as oasr_test_gemm takes them.  OASR_EINVAL (nothing written) for a dimension < 1 or a null output.
+ * block_needs: which parts of one transformer block's backward run.  asks, bit 0 need_dx_in (the block's input gradient is wanted), 1 need_xa
+ *   (d(xa) is wanted), 2 the block has a cross-attention, then "a tensor of the group needs a gradient": 3 self-attention + attn_ln, 4 cross-attention
+ *   + cross_attn_ln, 5 mlp.0 + mlp_ln, 6 cross_attn_ln, 7 attn_ln, 8 the cross key | value weights.  Returns, bit 0 the MLP section (everything past
+ *   the mlp.2 weight gradient), 1 the cross-attention section, 2 the self-attention section, 3 the cross key|value side (its weight gradient / d(xa)),
+ *   4 / 5 the data gradient through cross_attn_ln / attn_ln; -1 for asks outside [0, 512). */
+int oasr_train_wgrad_plan_debug(long long M, int N, int K, int view, int* split_k, int* atomic_on_pp);
+int oasr_train_block_needs_debug(int asks);
 int oasr_profile_gemm_collect(double* ms4, double* flops4, int64_t* count4, char* by_symbol /* "symbol\tlaunches\tms\tflops\n"... or NULL */, int cap);
 int oasr_probe_lds_oob(const void* src_u16 /*[512]*/, void* dst_u16 /*[512]*/, void* stream);
 int oasr_probe_tr16(const void* src_bf16 /*[16][64]*/, void* dst_bf16 /*[64 lanes][4]*/, void* stream);

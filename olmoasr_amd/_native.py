@@ -238,6 +238,8 @@ def _declare(lib):
         "oasr_test_gemm": (i32, [C.POINTER(GemmArgs), vp, i32, i32, i32, i32, vp]),
         "oasr_profile_gemm_records": (i32, [C.c_char_p, i32]),
         "oasr_gemm_route_debug": (i32, [i32] * 11 + [i32, C.c_longlong, C.c_longlong, C.c_longlong] + [i32] * 6 + [C.c_char_p, i32, C.POINTER(i32)]),
+        "oasr_train_wgrad_plan_debug": (i32, [C.c_longlong, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "oasr_train_block_needs_debug": (i32, [i32]),
         "oasr_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, vp]),
         "oasr_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
         "oasr_attention_fwd": (i32, [C.POINTER(AttnArgs), vp]),

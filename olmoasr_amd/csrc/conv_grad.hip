@@ -1,4 +1,4 @@
-// conv1 input gradient: d(mel) of the encoder stage's backward (engine_run.h, backward_encoder).
+// conv1 input gradient: d(mel) of the encoder stage's backward (engine_bwd.h, backward_encoder).
 //
 // conv1 runs as a GEMM over overlapping windows of the time-major mel with the packed kernel w1p [d][256] (column k*n_mels + c = tap k of
 // channel c).  Its data gradient comes out of one dgrad GEMM as the window columns dcol [B*T1][256] = d(u1) . w1p; this kernel folds them

@@ -1,5 +1,5 @@
 // Context lifetime of the engine: parameter layout (Builder, oasr_create*), binding, the compute copies of the weights (shadow refresh, LoRA merge),
-// the trainability mask and the optimizer entries.  The schedule itself is engine_run.h; its entry points are engine_step.hip / engine_decode.hip.
+// the trainability mask and the optimizer entries.  The schedule itself is engine_fwd.h / engine_bwd.h (gathered by engine_run.h); its entry points are engine_step.hip / engine_decode.hip.
 #include "engine_ctx.h"
 
 namespace {

@@ -54,7 +54,7 @@ struct oasr_ctx {
   DecLayerOffsets dec_l0 = {};       // decoder layer 0's tensor offsets (the one-launch step engines derive every layer's from them)
   int64_t dec_lstride = 0, dec_astride = 0;  // layer l = dec::layer_at(dec_l0, l, dec_lstride, dec_astride)
   bool dec_regular = false;          // ... holds for every decoder block (false: irregular layout, one-launch engines off)
-  // Side stream of the span step's decoder backward (Runner::wgrad_side): created on first use, lowest priority, so its weight-gradient
+  // Side streams of the span step (engine_side.h): created on first use, lowest priority, so its weight-gradient
   // workgroups fill the compute units the main stream's launches leave idle
   struct Side {
     hipStream_t stream = nullptr;  // the R-row weight gradients of the decoder backward
@@ -62,6 +62,16 @@ struct oasr_ctx {
     hipEvent_t fork[4] = {nullptr, nullptr, nullptr, nullptr}, join[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> kv_ready;  // [L_dec]: layer i's key|value projection has been written (forward)
     unsigned nf = 0, nj = 0;
+    void destroy() {  // whatever was created (a half-built one included: engine_side.h, SideStreams::side_begin)
+      for (hipEvent_t e : fork)
+        if (e) (void)hipEventDestroy(e);
+      for (hipEvent_t e : join)
+        if (e) (void)hipEventDestroy(e);
+      for (hipEvent_t e : kv_ready)
+        if (e) (void)hipEventDestroy(e);
+      if (stream) (void)hipStreamDestroy(stream);
+      if (big) (void)hipStreamDestroy(big);
+    }
   };
   mutable Side side;
   // set by oasr_decode_check when the one-launch decoder step (decode_xcd.hip) reported a poisoned team barrier: its 32 workgroups must be
@@ -114,14 +124,7 @@ struct oasr_ctx {
   float* Gt(int64_t off) const { return tr(off) ? grads + off : nullptr; }  // gradient of a tensor, null when it is frozen
   ~oasr_ctx() {
     if (runs_dev) (void)hipFree(runs_dev);
-    for (hipEvent_t e : side.fork)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : side.join)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : side.kv_ready)
-      if (e) (void)hipEventDestroy(e);
-    if (side.stream) (void)hipStreamDestroy(side.stream);
-    if (side.big) (void)hipStreamDestroy(side.big);
+    side.destroy();
   }
   // compute copy of the weight at arena offset `off`: the bf16 shadow, or -- fp32 validation -- the master weights themselves (with
   // adapters: their fp32 effective copy).  An adapted tensor's compute copy is its effective weight W0 + s * B . A.
@@ -168,7 +171,7 @@ struct Arena {
     if (_rc) return _rc; \
   } while (0)
 
-// Plans of the training step (Engine::make_plan): the fused step's, or one stage's of the staged autograd entries
+// Plans of the training step (engine_plan.h: make_plan): the fused step's, or one stage's of the staged autograd entries
 enum { STAGE_ALL = 0, STAGE_ENC = 1, STAGE_DEC = 2 };
 
 int check_bound(const oasr_ctx* c, bool need_grads) {

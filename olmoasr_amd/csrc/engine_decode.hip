@@ -90,7 +90,7 @@ template <typename T>
 static int oasr_decode_begin_impl(oasr_ctx* c, const void* xa, int B, void* kv_cache, void* stream) {
   RC(check_bound(c, false));
   OASR_REQUIRE(xa && kv_cache && B > 0, "oasr_decode_begin: bad args");
-  typename Engine<T>::Runner r{c, (hipStream_t)stream, B, 1, nullptr};
+  Runner<T> r{c, (hipStream_t)stream, B, 1, nullptr};
   const int d = c->d;
   // the one-launch step engines' control words, flags and packets live in the cache's tail (decode_step_core.h: KvCtrl)
   OASR_CHECK_HIP(hipMemsetAsync(kv_ctrl(c, kv_cache, B), 0, OASR_KV_TAIL_BYTES, (hipStream_t)stream));
@@ -179,7 +179,7 @@ static int oasr_decode_step_impl(oasr_ctx* c, const int64_t* tokens_last, int B,
   constexpr bool bf16 = std::is_same<T, bf16_t>::value;
   const int d = c->d, S_max = c->S_max;
   hipStream_t st = (hipStream_t)stream;
-  typename Engine<T>::Runner r{c, st, B, 1, nullptr};
+  Runner<T> r{c, st, B, 1, nullptr};
   StepWs<T> w(c, B, workspace, workspace_bytes);
   // token + positional embedding of position pos: S = 1 per sequence, positional row offset by pos
   RC(launch_embedding_fwd(tokens_last, c->P(c->tok_emb), c->P(c->dec_pos) + (size_t)pos * d, w.x, B, 1, d, c->V, st));

@@ -2,12 +2,12 @@
 // one Step<T> (engine_run.h) per call, and the order in which the Runner's halves are issued.
 #include "engine_run.h"
 
-// Runner::side_mode of the span step.  7 = the decoder backward's R-row weight gradients, the cross-attention key|value gradients AND the
+// Runner::side_mode of the span step (engine_side.h: SideMode).  7 = the decoder backward's R-row weight gradients, the cross-attention key|value gradients AND the
 // forward's key|value projections on the lowest-priority side streams: -1.4..-1.55 % of the step against no side streams, -0.7 % against mode 5
 // (same-box A/Bs, profiles/r05_side_streams.txt; round 6 re-measured: profiles/r06_side_streams.txt).  The 48 forward projections share the
 // dominant forward kernel's symbol; as filler their begin-to-end spans are queueing times, so the GEMM launch statistics carry the lane a
-// launch ran on (gemm_profile_lane, set by Runner::OnStream) and bench.py's `roofline` / scripts/rocprof_summary.py price main-stream launches only.
-constexpr int SIDE_STREAMS_DEFAULT = 7;
+// launch ran on (gemm_profile_lane, set by SideStreams::OnStream) and bench.py's `roofline` / scripts/rocprof_summary.py price main-stream launches only.
+constexpr int SIDE_STREAMS_DEFAULT = SIDE_WGRAD | SIDE_KV_FWD | SIDE_KV_BWD;
 
 template <typename T>
 static size_t plan_bytes(const oasr_ctx* c, int B, int S, bool train, int stage) {
@@ -108,12 +108,12 @@ static int span_side_streams() {
     const char* e = oasr_experiment_env("OASR_SIDE_STREAMS");
     return e ? atoi(e) : -1;
   }();
-  return env >= 0 ? (env & 15) : SIDE_STREAMS_DEFAULT;
+  return env >= 0 ? (env & SIDE_ALL) : SIDE_STREAMS_DEFAULT;
 }
 extern "C" int oasr_span_side_streams(void) { return span_side_streams(); }
 extern "C" int oasr_span_set_side_streams(int mode) {
   OASR_HOOK_GATE("oasr_span_set_side_streams");
-  g_side_streams = mode < 0 ? -1 : (mode & 15);
+  g_side_streams = mode < 0 ? -1 : (mode & SIDE_ALL);
   return OASR_OK;
 }
 
@@ -133,8 +133,7 @@ extern "C" int oasr_span_set_side_streams(int mode) {
 //   * the backward of the decoder (dgrad / wgrad GEMMs, LayerNorm, attention, cross-entropy gradient, embedding scatter) runs on the
 //     leading R = sum_b ceil64(span[b]) rows only -- on the synthetic lengths 1/3 of the 448 * B.
 // The results differ from the plain step's only by fp32 summation order (weight gradients sum over fewer, re-ordered token rows).
-// A shape the row table cannot chunk takes the plain step (same results).
-static bool span_chunkable(const oasr_ctx* c, int B) { return (c->S_max % 64) == 0 && c->S_max <= 64 * OASR_ROWTAB && B <= 512; }
+// A shape the row table cannot chunk takes the plain step (same results): span_chunkable, train_plan.h.
 
 // Every refusal of oasr_train_step, before anything is launched or dereferenced: the arguments, then the workspace size, then the context's state.
 static int train_step_check(const oasr_ctx* c, const oasr_train_step_args* a, const void* workspace, size_t workspace_bytes) {
@@ -154,7 +153,7 @@ static int train_step_check(const oasr_ctx* c, const oasr_train_step_args* a, co
   }
   OASR_REQUIRE(!a->xa || (!a->mel_clip_max && !a->logits_out), "oasr_train_step: mel_clip_max / logits_out do not apply to the step from a given xa");
   // pred_out is indexed through the row table: no plain-step fall-back with it
-  OASR_REQUIRE(!a->pred_out || span_chunkable(c, a->B),
+  OASR_REQUIRE(!a->pred_out || span_chunkable(c->S_max, a->B),
                "pred_out needs the chunk-row table: n_text_ctx = %d must be a multiple of 64 (<= %d) and B = %d <= 512", c->S_max, 64 * OASR_ROWTAB, a->B);
   RC(check_ce_reg("oasr_train_step", a->label_smoothing, a->z_loss));
   OASR_REQUIRE(!a->loss_parts_out || a->loss_parts_rows, "oasr_train_step: loss_parts_out needs loss_parts_rows (f32 [2, B * S] of per-row scratch the caller owns)");
@@ -217,12 +216,12 @@ static int train_step_impl(oasr_ctx* c, const oasr_train_step_args& a, bool chun
     RC(launch_loss_reduce(reg.parts, ce_rows, p.n_valid, a.inv_accum, a.loss_parts_out, a.accumulate_loss, st));
     RC(launch_loss_reduce(reg.parts + Md, ce_rows, p.n_valid, a.inv_accum, a.loss_parts_out + 1, a.accumulate_loss, st));
   }
-  return train_backward<T>(c, r, p, a.tokens, B, S, a.seg_events);
+  return r.train_backward(p, a.tokens, a.seg_events);
 }
 extern "C" size_t oasr_sizeof_train_step_args(void) { return sizeof(oasr_train_step_args); }
 extern "C" int oasr_train_step(oasr_ctx* c, const oasr_train_step_args* a, void* workspace, size_t workspace_bytes, void* stream) {
   RC(train_step_check(c, a, workspace, workspace_bytes));
-  return OASR_BY_DTYPE(c, train_step_impl, c, *a, a->span_host && span_chunkable(c, a->B), workspace, workspace_bytes, stream);
+  return OASR_BY_DTYPE(c, train_step_impl, c, *a, a->span_host && span_chunkable(c->S_max, a->B), workspace, workspace_bytes, stream);
 }
 
 // ---- the same micro-step cut at the logits, for torch.autograd (OLMoASR.forward in training mode, olmoasr/model.py:856-887 followed
@@ -243,7 +242,7 @@ static int oasr_train_bwd_impl(oasr_ctx* c, const int64_t* tokens, const int32_t
                                void* workspace, size_t workspace_bytes, void* stream) {
   Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true);
   RC(launch_dlogits_from_f32(dlogits, c->V, (long)B * S, c->Vp, s.p.logits, s.r.st));
-  return train_backward<T>(c, s.r, s.p, tokens, B, S, ev);
+  return s.r.train_backward(s.p, tokens, ev);
 }
 extern "C" int oasr_train_fwd(oasr_ctx* c, const float* mel, const int64_t* tokens, const int32_t* text_len, int B, int S, float* logits_out,
                               void* workspace, size_t workspace_bytes, void* stream) {
@@ -266,7 +265,7 @@ extern "C" int oasr_train_bwd(oasr_ctx* c, const int64_t* tokens, const int32_t*
 // Each stage has a workspace plan of its own (OASR_MODE_TRAIN_ENC / _DEC) that holds one forward's saved activations until its backward.
 // The forwards are the fused training forward's (train = true: the MLP epilogue saves GELU'(u)), cut at xa: encode then decode runs the
 // kernels of oasr_train_fwd on the same inputs, plus one copy of xa into the decoder's plan.  The backwards are the two halves of
-// train_backward, started from the caller's d(logits) / d(xa); a requested input gradient (d(xa), d(mel)) is computed even where the mask
+// Runner::train_backward, started from the caller's d(logits) / d(xa); a requested input gradient (d(xa), d(mel)) is computed even where the mask
 // would prune it, and an all-frozen mask is accepted when one is requested.
 template <typename T>
 static int oasr_train_encode_impl(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -279,10 +278,10 @@ static int oasr_train_encode_bwd_impl(oasr_ctx* c, const void* dxa, int B, float
                                       void* stream) {
   RC(backward_check(c, dmel_out != nullptr));
   Step<T> s(c, workspace, workspace_bytes, stream, B, 1, nullptr, true, STAGE_ENC);
-  RC(backward_begin<T>(c, s.r, s.p));
+  RC(s.r.backward_begin(s.p));
   int seg = 0;
-  RC(backward_encoder<T>(c, s.r, s.p, (const T*)dxa, B, nullptr, seg, dmel_out));
-  return backward_finish<T>(c, s.r, s.p, nullptr, seg, STAGE_ENC);
+  RC(s.r.backward_encoder(s.p, (const T*)dxa, nullptr, seg, dmel_out));
+  return s.r.backward_finish(s.p, nullptr, seg, STAGE_ENC);
 }
 template <typename T>
 static int oasr_train_decode_impl(oasr_ctx* c, const int64_t* tokens, const void* xa, const int32_t* text_len, int B, int S, float* logits_out,
@@ -298,12 +297,12 @@ static int oasr_train_decode_bwd_impl(oasr_ctx* c, const int64_t* tokens, const 
   RC(backward_check(c, dxa_out != nullptr));
   Step<T> s(c, workspace, workspace_bytes, stream, B, S, text_len, true, STAGE_DEC);
   RC(launch_dlogits_from_f32(dlogits, c->V, (long)B * S, c->Vp, s.p.logits, s.r.st));
-  RC(backward_begin<T>(c, s.r, s.p));
+  RC(s.r.backward_begin(s.p));
   int seg = 0;
-  RC(backward_decoder<T>(c, s.r, s.p, tokens, B, S, nullptr, seg, dxa_out != nullptr));
+  RC(s.r.backward_decoder(s.p, tokens, nullptr, seg, dxa_out != nullptr));
   // d(xa) in the compute dtype, summed over the decoder layers in block_bwd's order (top layer first)
   if (dxa_out) RC(copy_xa<T>(c, dxa_out, s.p.gxa, B, s.r.st));
-  return backward_finish<T>(c, s.r, s.p, nullptr, seg, STAGE_DEC);
+  return s.r.backward_finish(s.p, nullptr, seg, STAGE_DEC);
 }
 extern "C" int oasr_train_encode(oasr_ctx* c, const float* mel, int B, void* xa_out, void* workspace, size_t workspace_bytes, void* stream) {
   RC(check_bound(c, true));

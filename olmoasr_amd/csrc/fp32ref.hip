@@ -1,6 +1,6 @@
 // fp32 VALIDATION kernels: the float overloads of the launchers in kernels.h.
 //
-// compute_dtype = OASR_DTYPE_F32 runs the SAME engine schedule (engine_run.h: forward, loss, hand-written backward,
+// compute_dtype = OASR_DTYPE_F32 runs the SAME engine schedule (engine_fwd.h / engine_bwd.h: forward, loss, hand-written backward,
 // gradient arena, optimizer) with fp32 activations, fp32 operands, fp32 accumulation and exact-erf GELU -- the
 // reference's precision="float32" path (scripts/training/train_timestamps.py:2128,2220-2224; olmoasr/model.py:39,97-101).
 // Its purpose is parity, not speed: it separates "bf16 rounding" from "bug" by holding logits to 1e-3 abs and gradients

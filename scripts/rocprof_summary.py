@@ -3,7 +3,7 @@ either the rocpd SQLite database (default output of rocprofv3 in ROCm 7.2) or *_
 
   python scripts/rocprof_summary.py trace_kernel_trace.csv [--by-queue]
 
---by-queue (csv only): one row per (kernel, queue) -- with the span step's side streams (csrc/engine_run.h Runner::side_mode) launches
+--by-queue (csv only): one row per (kernel, queue) -- with the span step's side streams (csrc/engine_side.h SideMode) launches
 of one symbol run on different HIP streams = hardware queues, and a lowest-priority launch's begin-to-end span includes waiting for
 compute units: its average is a queueing time, not a kernel time.  The header also prints the UNION of all dispatch intervals (the
 time at least one kernel was running) beside their sum: sum - union = overlapped kernel time."""

@@ -1,6 +1,6 @@
 """Frozen-parameter fine-tuning (``requires_grad_(False)``, e.g. Whisper's frozen-encoder recipe): a frozen parameter gets no gradient
 (``.grad is None``), the optimizer leaves it alone, the clip norm covers the trainable gradients only, and the backward does not run the
-work that only served frozen tensors (oasr_set_trainable, the pruned backward of csrc/engine_run.h).  Every check runs in the fp32
+work that only served frozen tensors (oasr_set_trainable, the pruned backward of csrc/engine_bwd.h).  Every check runs in the fp32
 validation mode against the fp32 oracle (the bounds of test_gpu_fp32_mode.py) and on the bf16 engine (the bounds of test_gpu_model.py)."""
 import ctypes
 import os

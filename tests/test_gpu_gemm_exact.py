@@ -580,7 +580,7 @@ def test_gelu_sweep_every_finite_bf16(path):
 #    span step keeps 18,944 = 64 x 296; 18,752 = 64 x 293 is a span-step row count with M % 256 == 64)
 # ======================================================================================================================================
 def wgrad_config(tokens, N, K):
-    """(split_k, atomic_on_pp) as Runner::wgrad (csrc/engine_run.h) configures dW[N, K] over ``tokens`` rows: the split that minimises
+    """(split_k, atomic_on_pp) as Runner::wgrad (csrc/engine_gemm.h, csrc/train_plan_host.cpp) configures dW[N, K] over ``tokens`` rows: the split that minimises
     (K-tiles per split + 16 + split) x waves of the 768 resident 256 x 128 workgroups, or the ping-pong kernel's table -- 192k tokens:
     [1024 x 1024] split 16, [4096 x 1024] 8, [1024 x 4096] 4, [2048 x 1024] 8; 57k tokens: the two 4:1 shapes split 4."""
     tiles, kt = ((N + 255) // 256) * ((K + 127) // 128), (tokens + 63) // 64

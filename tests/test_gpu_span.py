@@ -213,7 +213,7 @@ def test_span_step_equals_plain_step(variant, B, dtype):
 
 @pytest.mark.parametrize("variant,B,dtype", [("tiny", 6, "bfloat16"), ("base", 9, "bfloat16"), ("tiny", 4, "float32")])
 def test_span_step_side_streams_change_nothing_but_the_summation_order(variant, B, dtype, monkeypatch):
-    """The span step's side streams (csrc/engine_run.h Runner::side_mode: weight gradients over the active rows, the cross-attention
+    """The span step's side streams (csrc/engine_side.h SideMode: weight gradients over the active rows, the cross-attention
     key|value projections and their gradients on lowest-priority streams beside the main chain) against the single-stream step:
     same loss (the forward's arithmetic does not change), gradients equal up to the order of the fp32 atomics --
     with and without per-segment events (the events force the key|value gradients' join at every block: the DDP path), twice in a
